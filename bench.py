@@ -16,9 +16,12 @@ One "step" = one pass of the hot path over one batch of synthetic input.
 with the child's status; under torchrun it is one of the ranks. `--gpus` must equal WORLD_SIZE.
 
 Contract: W untimed warm-up steps, then exactly K timed steps bracketed by barrier + torch.cuda.synchronize() on
-both sides, MAX over ranks, one JSON line from rank 0. Extra objects: `roofline` (dominant kernel = the
-encoder-linear GEMMs, timed live with HIP events on the launch stream), `cpu_baseline` (the oracle on the host
-cores, rank 0, N = 1) and `pcie_inclusive` (the same step with H2D of the frames and D2H of the maps inside).
+both sides, MAX over ranks, one JSON line from rank 0. A plain run does only that (set-up, warm-up, the K steps, the
+line). `--full` adds the extra objects: `roofline` / `attention_kernel` (dominant kernels, timed with HIP events on
+the launch stream), `cpu_baseline` (the oracle on the host cores, rank 0, N = 1), `pcie_inclusive` (the same step
+with H2D of the frames and D2H of the maps inside) and, for N > 1, `phases` and `single_gpu_same_workload`.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32; a fixed, seeded sample
+when the whole output is larger than 48 MB) so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -94,6 +97,30 @@ def _cpu_model() -> str:
     return "unknown"
 
 
+DUMP_MAX_BYTES = 48 * 2**20    # a larger output is dumped as a seeded sample of DUMP_SAMPLE elements
+DUMP_SAMPLE = 8 * 2**20
+
+
+def _dump_outputs(outs, out_dir):
+    """outs {name: tensor | ndarray} -> out_dir/<name>.npy as float32 (float64 kept). An output over DUMP_MAX_BYTES is
+    written as DUMP_SAMPLE of its flattened elements at indices drawn with a fixed seed from its element count alone,
+    so the same shape gives the same sample on every run and every build."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in outs.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().float().cpu().numpy() if v.dtype != torch.float64 else v.detach().cpu().numpy()
+        v = np.asarray(v)
+        if v.dtype != np.float64:
+            v = v.astype(np.float32)
+        if v.nbytes > DUMP_MAX_BYTES:
+            idx = np.sort(np.random.default_rng(1234).integers(0, v.size, DUMP_SAMPLE))
+            v = v.reshape(-1)[idx]
+            name += "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -105,6 +132,11 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=8, help="streams per GPU (stream workload)")
     ap.add_argument("--encoder", default="vitl")
     ap.add_argument("--precision", default=None, help="f16x3 (default, parity-green) | f16 | bf16x3 | bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / attention kernel figures, the CPU baseline, "
+                         "the PCIe-inclusive rate, and for N > 1 the per-phase diagnostic step and the one-GPU comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, <= 48 MB per output)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--no-pcie", action="store_true")
@@ -139,7 +171,11 @@ def spawn_ranks(a) -> int:
 
 class _StubVideoModel:
     """Stand-in for VideoDepthAnything in `--stub` runs: a per-pixel temporal mix, so that the frame-sharded
-    path really needs its all-to-all; CPU tensors only."""
+    path really needs its all-to-all; CPU tensors only. `clips` counts the clips this rank started to encode; with
+    `clip_offset` set, the n-th clip's depth carries n * clip_offset (before stitching), so a result shows which step made it."""
+
+    clips = 0
+    clip_offset = 0.0
 
     def preprocess_frames(self, frames, input_size):
         import torch
@@ -173,6 +209,7 @@ class _StubVideoModel:
     # chunked form of encode_frames (vdn/dist.py TapExchange: a chunk's taps travel while the next chunk is encoded)
     def tap_planes(self, x):
         import torch
+        self.clips += 1
         k, c, H, W = x.shape
         self._planes = [torch.empty((k * H * W, c), dtype=torch.float32)]
         return self._planes, H * W, (H, W)
@@ -191,7 +228,7 @@ class _StubVideoModel:
             ex = FrameShardExchange(T, group)
             y = shard_core(ex, [planes[0].contiguous()], H * W,
                            lambda pl, D: [self._mix(pl[0].reshape(ex.T, D, c)).reshape(ex.T * D, c)])[0].reshape(Tl, H * W, c)
-        return y.mean(-1).abs().reshape(Tl, H, W) + 0.25
+        return y.mean(-1).abs().reshape(Tl, H, W) + 0.25 + self.clips * self.clip_offset
 
     def infer_video_depth(self, frames, fps, input_size=518):
         from vdn.dist import infer_video_depth_sharded
@@ -245,6 +282,7 @@ def main():
         assert a.workload == "video", "--stub rehearses the multi-rank video driver only"
         H = W = 28
         model, prec_name = _StubVideoModel(), "stub"
+        model.clip_offset = 1e-3   # the step a dumped result came from is visible in it (tests/test_dist.py)
         frames_per_step = a.video_frames
     else:
         import vdn
@@ -314,7 +352,9 @@ def main():
 
     step_ms = []   # per-step HIP-event durations of the last timed() call
 
-    def timed(nsteps, events, fn=None):
+    last_out = []   # what the last step of a timed(..., keep_last=True) call returned
+
+    def timed(nsteps, events, fn=None, keep_last=False):
         fn = fn or step
         for rt in runtimes():
             rt.timing = [] if events else None
@@ -325,7 +365,10 @@ def main():
             if not a.stub:   # HIP events on the stream the step is issued on (lanes fork from and join into it)
                 s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 s_ev.record()
-            fn()
+            r = fn()
+            if keep_last:
+                last_out[:] = [r]
+            del r
             if not a.stub:
                 e_ev.record()
                 marks.append((s_ev, e_ev))
@@ -352,9 +395,15 @@ def main():
     # with the other lane's) and recording ~240 event pairs per step costs the timed region ~3 %: the timed
     # region then runs without events, and the roofline figures come from K more steps of the same workload
     # issued on ONE lane right after it (same memory bank: the lanes share one ring, still full).
-    want_events = (not a.no_kernel_events) and not a.stub
-    dt, ev = timed(a.steps, want_events and lanes == 1)
+    want_events = a.full and (not a.no_kernel_events) and not a.stub
+    clips0 = model.clips if a.stub else None
+    dt, ev = timed(a.steps, want_events and lanes == 1, keep_last=a.dump_outputs is not None)
+    clips_timed = model.clips - clips0 if a.stub else None
     step_ms_main = list(step_ms)
+    if a.dump_outputs is not None:   # before anything else runs the model again
+        if rank == 0:
+            _dump_outputs({"depth": last_out[0]}, a.dump_outputs)
+        last_out.clear()
     strong = a.workload == "video"
     fps = frames_per_step * a.steps * (1 if strong else n_gpus) / dt
     dt1 = None
@@ -396,6 +445,8 @@ def main():
                                      "8-bit score cross terms, P V products per term = attention_pv_products (1: V as one fp16 plane "
                                      "rounded to nearest; measured 2e-5..9e-5 end to end against the 1e-3 tolerance)"},
     }
+    if a.stub:   # clips the stand-in encoded on this rank before and inside the timed region
+        out["config"]["stub_clips"] = {"before_timed": clips0, "timed": clips_timed}
     if not a.stub:
         from vdn import _abi
         out["config"]["attention_pv_products"] = int(model._engines()["rt"].pv_products)
@@ -452,7 +503,7 @@ def main():
 
     # ---------------- where an N-GPU step spends its time: one more DIAGNOSTIC step with the device synchronised at every phase
     # boundary (not the timed region), seconds per phase as MAX over ranks, bytes as SUM over ranks
-    if strong and dist is not None:
+    if a.full and strong and dist is not None:
         st = {}
         infer_video_depth_sharded(model, video, 24, input_size=H, all_ranks=False, stats=st)
         keys = ["preprocess", "encode", "tap_exchange_wait", "heads", "gather", "stitch", "to_host"]
@@ -470,7 +521,7 @@ def main():
                                  "was left of the exchange after the last encoder chunk"}
 
     # ---------------- the same workload on ONE GPU (rank 0 alone) next to the N-GPU number of the strong-scaling run
-    if strong and dist is not None and not a.stub:
+    if a.full and strong and dist is not None and not a.stub:
         if rank == 0:
             model.infer_video_depth(video, 24, input_size=H)
             torch.cuda.synchronize(dev)
@@ -484,7 +535,7 @@ def main():
         dist.barrier()
 
     # ---------------- PCIe-inclusive rate: host frames in (H2D) and host maps out (D2H) inside the step
-    if a.workload == "stream" and not a.no_pcie and not a.stub:
+    if a.full and a.workload == "stream" and not a.no_pcie and not a.stub:
         xh = x.cpu().pin_memory()
         oh = torch.empty((frames_per_step, H, W), dtype=torch.float32).pin_memory()
 
@@ -508,7 +559,7 @@ def main():
         model.set_precision(prec_name)
 
     # ---------------- CPU baseline: the oracle on the host cores, rank 0, N == 1, steady state
-    if rank == 0 and n_gpus == 1 and not a.no_cpu_baseline and not a.stub:
+    if a.full and rank == 0 and n_gpus == 1 and not a.no_cpu_baseline and not a.stub:
         from oracle import ref_cpu as O
         sd_cpu = {k: v.detach().float().cpu() for k, v in model.state_dict().items()}
         # the GPU box gives one GPU a 16-core CPU share: oversubscribing all visible cores is slower

@@ -175,7 +175,7 @@ def test_bench_gpus_2_spawns_two_ranks():
     and reports them; a --gpus / WORLD_SIZE mismatch is an error, not a silent single-rank run."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--steps", "1", "--warmup", "0",
-           "--video-frames", "50"]
+           "--video-frames", "50", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -189,3 +189,31 @@ def test_bench_gpus_2_spawns_two_ranks():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub"], env=env,
                        capture_output=True, text=True, timeout=120)
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr
+
+
+def test_bench_plain_run_steps_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run puts exactly --steps clips through the stand-in inside the timed region (after --warmup
+    clips), measures nothing behind --full, and --dump-outputs writes what the LAST timed step returned: the stand-in
+    adds n * 1e-3 to every map of its n-th clip, so a dump of a warm-up or an earlier step would be off by a multiple
+    of 1e-3. Two runs with the same arguments dump the same arrays."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+
+    def run(name, warmup, steps):
+        d = tmp_path / name
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--steps", str(steps), "--warmup",
+               str(warmup), "--video-frames", "50", "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert j["steps"] == steps and j["warmup"] == warmup and j["ms_per_step"] > 0 and j["value"] > 0
+        assert j["config"]["stub_clips"] == {"before_timed": warmup, "timed": steps}
+        assert not {"phases", "single_gpu_same_workload", "roofline", "cpu_baseline", "pcie_inclusive"} & set(j)
+        assert sorted(os.listdir(d)) == ["depth.npy"]
+        return np.load(d / "depth.npy")
+
+    a, b, first = run("a", 1, 3), run("b", 1, 3), run("first", 0, 1)
+    assert a.dtype == np.float32 and a.shape == (50, 28, 28)
+    assert np.array_equal(a, b)
+    # clip 4 (the third timed step after one warm-up), not clip 1: the stitcher's scale / shift alignment bends the
+    # offset by < 5e-5, far less than the 1e-3 between neighbouring steps
+    assert np.allclose(a - first, 3e-3, rtol=0, atol=2e-4)

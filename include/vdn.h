@@ -350,6 +350,31 @@ int vdn_depth_tail(int dt, const float* x, int B, int IH, int IW, int C, const v
                    const float* bias2, const float* w1, float b1, float* depth, int OH, int OW, int relu,
                    vdn_stream stream);
 
+/* Depth + normal model (models/video_depth_model.py:64-119 with the VideoDepthAnythingHeadV2 head of
+ * models/video_depth_head_v2_sangyu.py). Tokens are frame-major channel-last rows [B*S*h*w, C].
+ * vdn_dn_attn     — nn.MultiheadAttention(C, heads, batch_first) self-attention (video_depth_head_v2_sangyu.py:67,
+ *                   with the rearranges of :120,:122 (spatial) and :173,:175 (temporal)): qkv half [rows, 3C] = the
+ *                   packed in_proj output (q | k | v, head h at columns h*dh.. of each), out half [rows, C]. Sequence
+ *                   (g1 < n1, g0 < n0) is the L rows g1*s1 + g0*s0 + j*estride, j < L: spatial = (L = h*w, estride 1,
+ *                   n0 1, n1 B*S, s1 h*w), temporal = (L = S, estride h*w, n0 h*w, s0 1, n1 B, s1 S*h*w). Head dim
+ *                   C/heads in {12, 24, 48, 96}; online softmax, any L. qkv_lo / out_lo: split planes (both or neither).
+ * vdn_dn_prologue — the features the head consumes, in one launch per level (video_depth_model.py:89-103,
+ *                   video_depth_head_v2_sangyu.py:272-276): token[(f*hw + p), c] = a[f][c*hw + p] (+ b[f][c*hw + p])
+ *                   (+ ape[f % S][c]); a / b f32 per frame [C*hw] (the trunk's NHWC buffers read flat = the `.view`
+ *                   reinterpretation; the head's own [B,S,C,h,w] input), b / ape optional. Writes out_f (f32 [rows, C])
+ *                   and / or the half planes out_h (+ out_lo) in `dt`.
+ * vdn_dn_tail     — conv3x3 (Cin -> 3, pad 1) + bias of the f32 NHWC map x [F, IH, IW, Cin] (final_upscale_layer's
+ *                   last conv, :249), bilinear resize (align_corners) to (OH, OW) when it differs (video_depth_model.py:
+ *                   107-110), then raw f32 [F, 3, OH, OW] (optional, the head's result) and / or depth f32 [F, OH, OW]
+ *                   = relu?(ch0 (+ depth_in)) with normal f32 [F, 3, OH, OW] = (-ch1, -ch2, 1) (:112-123).
+ *                   w f32 [3, Cin, 3, 3] as nn.Conv2d stores it, bias f32 [3]; Cin <= 128.                          */
+int vdn_dn_attn(int dt, const void* qkv, const void* qkv_lo, void* out, void* out_lo, int rows, int C, int heads, int L,
+                int estride, int n0, int s0, int n1, int s1, float scale, vdn_stream stream);
+int vdn_dn_prologue(int dt, const float* a, const float* b, int frames, int C, int hw, const float* ape, int S, float* out_f,
+                    void* out_h, void* out_lo, vdn_stream stream);
+int vdn_dn_tail(const float* x, int F, int IH, int IW, int Cin, const float* w, const float* bias, int OH, int OW,
+                const float* depth_in, int relu, float* raw, float* depth, float* normal, vdn_stream stream);
+
 /* One-time weight packing ON THE DEVICE, so that a host in any language can feed the library from the reference's
  * fp32 parameter tensors as torch.nn stores them (vdn/pack.py is a thin caller of these). `w` is the contiguous fp32
  * parameter, (hi, lo) the [rows, ldb] planes vdn_gemm reads (lo may be NULL for the 1-product modes): K contiguous,

@@ -18,4 +18,10 @@ def __getattr__(name):
     if name == "VideoDepthAnything":
         from .video_depth import VideoDepthAnything
         return VideoDepthAnything
+    if name == "VideoDepthAnythingHeadV2":
+        from .video_depth_head_v2_sangyu import VideoDepthAnythingHeadV2
+        return VideoDepthAnythingHeadV2
+    if name == "VideoDepthEstimationModel":
+        from .video_depth_model import VideoDepthEstimationModel
+        return VideoDepthEstimationModel
     raise AttributeError(name)

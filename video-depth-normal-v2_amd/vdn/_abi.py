@@ -107,6 +107,10 @@ EXPORTS = {
     "vdn_refine_scale": (C.c_int, [fp, fp, C.c_int, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, fp, fp, vp]),
     "vdn_refine_pack": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_refine_finish": (C.c_int, [fp, fp, C.c_float, C.c_float, C.c_float, C.c_int, fp, C.c_size_t, vp]),
+    "vdn_dn_attn": (C.c_int, [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                              C.c_int, C.c_float, vp]),
+    "vdn_dn_prologue": (C.c_int, [C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, vp, vp, vp]),
+    "vdn_dn_tail": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, fp, C.c_int, fp, fp, fp, vp]),
     "vdn_stitch_workspace_bytes": (C.c_size_t, []),
     "vdn_stitch_fit": (C.c_int, [fp, fp, C.c_size_t, vp, fp, vp]),
     "vdn_stitch_apply": (C.c_int, [fp, fp, fp, fp, fp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

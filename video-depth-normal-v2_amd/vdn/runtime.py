@@ -313,6 +313,29 @@ class Runtime:
         self._launch(abi.lib.vdn_refine_finish, self._p(scaled), depth.data_ptr(), w, b, max_depth, int(residual), out.data_ptr(),
                      depth.numel())
 
+    def dn_attn(self, qkv, out, rows: int, Cn: int, heads: int, L: int, estride: int, n0: int, s0: int, n1: int, s1: int,
+                scale: float):
+        """Grouped self-attention of the depth + normal head (include/vdn.h vdn_dn_attn): qkv [rows, 3C], out [rows, C]."""
+        (qh, ql), (oh, ol) = _hl(qkv), _hl(out)
+        self._launch(abi.lib.vdn_dn_attn, self.dt, qh.data_ptr(), ql, oh.data_ptr(), ol, rows, Cn, heads, L, estride, n0, s0,
+                     n1, s1, scale, tag="dn_attn", flop=4.0 * n0 * n1 * L * L * Cn)
+
+    def dn_prologue(self, a: torch.Tensor, b: Optional[torch.Tensor], frames: int, Cn: int, hw: int, ape=None, S: int = 1,
+                    out_f=None, out_h=None):
+        """Trunk features (f32, per frame a flat [C*hw] array) -> token rows [frames*hw, C] (include/vdn.h vdn_dn_prologue)."""
+        for t in (a, b):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == frames * Cn * hw), t
+        oh, ol = _hl(out_h) if out_h is not None else (None, None)
+        self._launch(abi.lib.vdn_dn_prologue, self.dt, a.data_ptr(), self._p(b), frames, Cn, hw, self._p(ape), S,
+                     self._p(out_f), self._p(oh), ol)
+
+    def dn_tail(self, x, F: int, IH: int, IW: int, Cn: int, w, bias, OH: int, OW: int, depth_in=None, relu: bool = False,
+                raw=None, depth=None, normal=None):
+        """conv3x3 Cin->3 + bias [-> resize] -> raw and / or (depth, normal) (include/vdn.h vdn_dn_tail)."""
+        assert x.dtype == torch.float32 and x.is_contiguous()
+        self._launch(abi.lib.vdn_dn_tail, x.data_ptr(), F, IH, IW, Cn, w.data_ptr(), bias.data_ptr(), OH, OW, self._p(depth_in),
+                     int(relu), self._p(raw), self._p(depth), self._p(normal))
+
     def patchify(self, img, rows, B: int, H: int, W: int, ldk: int):
         rows, rl = _hl(rows)
         self._launch(abi.lib.vdn_patchify, self.dt, img.data_ptr(), rows.data_ptr(), rl, B, H, W, ldk)

@@ -227,3 +227,31 @@ def heavy_overlay(sd, prefix: str = "pretrained."):
         for j, gain in units:
             w1[j] *= gain; b1[j] *= gain
     return sd
+
+
+# ---------------------------------------------------------------------------------------------
+# stand-in trunk of the depth + normal model (vdn.VideoDepthEstimationModel): the reference's Hiera trunk comes from
+# torch.hub, which needs the network, so fixtures and tests inject this deterministic module in its place.
+def dn_trunk(sizes=((56, 56), (28, 28), (14, 14), (7, 7)), channels=(96, 192, 384, 768)):
+    """nn.Module: x [N, 3, H, W] -> (None, [tanh(Linear(3 -> C_l)(adaptive_avg_pool(x, size_l))) as NHWC [N, h, w, C_l]]).
+    Its parameters are `proj.{l}.weight` / `proj.{l}.bias` (zeros until a state dict is loaded, like every holder here)."""
+    import torch
+    import torch.nn as nn
+    import torch.nn.functional as F
+
+    class DNTrunk(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.sizes = [tuple(s) for s in sizes]
+            self.proj = nn.ModuleList([nn.Linear(3, c) for c in channels])
+            for p in self.proj.parameters():
+                nn.init.zeros_(p)
+
+        def forward(self, x):
+            feats = []
+            for s, lin in zip(self.sizes, self.proj):
+                p = F.adaptive_avg_pool2d(x.float(), s).permute(0, 2, 3, 1)
+                feats.append(torch.tanh(lin(p)).contiguous())
+            return None, feats
+
+    return DNTrunk()

@@ -138,6 +138,18 @@ def test_product_refuses_cpu():
         m.forward(torch.zeros(1, 3, 28, 28))
 
 
+def test_cross_term_activation_needs_cross_term_weight():
+    """Runtime.gemm refuses on the host a KT activation whose weight has no X8 planes (no launch: the check comes first)."""
+    from vdn import _abi, pack
+    from vdn.runtime import HL, KT, Runtime
+    rt = Runtime.__new__(Runtime)   # no device: gemm must raise before it touches one
+    a = KT(torch.zeros(64, 64, dtype=torch.float16), torch.zeros(2, 64, 64, dtype=torch.uint8))
+    w = HL(torch.zeros(64, 64, dtype=torch.float16), torch.zeros(64, 64, dtype=torch.float16))
+    for weight in (pack.Linear(w), w):
+        with pytest.raises(_abi.VdnError, match="KT"):
+            rt.gemm(a, weight, 64, 64, 64)
+
+
 def test_rope_table_and_pack_geometry():
     """Host-visible pieces of the packing ABI (the packers themselves run on the device: tests/test_gpu_ops.py)."""
     from vdn import _abi, pack

@@ -5,6 +5,10 @@ Data layout in HBM (everything channels-last, resident for the whole forward):
   GEMM operands / activations between convs                                      half [rows, C]
   attention operands   Q,K  half [B*heads, tpad, 64];  V^T half [B*heads, 64, tpad]
   memory bank          per layer ring of projected+rotated K / V^T (6 slots), written once per frame
+Every sequence is written once for both GEMM kernels. A linear that can take the 8-bit cross-term kernel (csrc/gemm_x8.hip;
+DESIGN.md §3) holds its weight as a pack.Linear, and the activations around it come from Runtime.operand: split planes, or for
+a call with enough rows (Runtime.x8_rows) the K-tile-major form (runtime.KT). layernorm, gemm and flash_attn read the form off
+the operand.
 Every function cites the reference code it stands for (paths relative to the reference root).
 """
 from __future__ import annotations
@@ -17,7 +21,7 @@ import torch
 
 from . import _abi as abi
 from . import pack
-from .runtime import Runtime, ceil_to
+from .runtime import HL, Runtime, ceil_to
 
 GELU, RELU = abi.ACT_GELU, abi.ACT_RELU
 PATCH = 14
@@ -37,11 +41,18 @@ class EncoderEngine:
         self.pos = pack.f32(mod.pos_embed).reshape(-1, self.C)  # [1+37*37, C]
         self.blocks = []
         self.hidden = cfg.get("swiglu") or 4 * self.C   # FFN width: Mlp 4C, or the SwiGLU hidden size of ViT-g
+        # 8-bit cross terms for the four linears of a block (csrc/gemm_x8.hip): K-tile-major weight planes made
+        # once here, in the order of the kernel that writes each linear's input. SwiGLU has no cross-term path.
+        self.x8 = rt.x8_capable(self.C) and not cfg.get("swiglu")
+
+        def lin(w, order):
+            return pack.Linear(pack.linear(w, h), order if self.x8 else None)
+
         for b in mod.blocks:
             blk = dict(
                 n1w=pack.f32(b.norm1.weight), n1b=pack.f32(b.norm1.bias),
-                wqkv=pack.linear(b.attn.qkv.weight, h), bqkv=pack.f32(b.attn.qkv.bias),
-                wproj=pack.linear(b.attn.proj.weight, h), bproj=pack.f32(b.attn.proj.bias),
+                wqkv=lin(b.attn.qkv.weight, pack.ORDER_NATURAL), bqkv=pack.f32(b.attn.qkv.bias),
+                wproj=lin(b.attn.proj.weight, pack.ORDER_ATTN), bproj=pack.f32(b.attn.proj.bias),
                 ls1=pack.f32(b.ls1.gamma),
                 n2w=pack.f32(b.norm2.weight), n2b=pack.f32(b.norm2.bias),
                 ls2=pack.f32(b.ls2.gamma))
@@ -53,19 +64,11 @@ class EncoderEngine:
                 blk["wfc1"], blk["bfc1"] = pack.geglu(torch.cat([w12[Hd:], w12[:Hd]]), torch.cat([b12[Hd:], b12[:Hd]]), h)
                 blk["wfc2"], blk["bfc2"] = pack.linear(b.mlp.w3.weight, h), pack.f32(b.mlp.w3.bias)
             else:
-                blk["wfc1"], blk["bfc1"] = pack.linear(b.mlp.fc1.weight, h), pack.f32(b.mlp.fc1.bias)
-                blk["wfc2"], blk["bfc2"] = pack.linear(b.mlp.fc2.weight, h), pack.f32(b.mlp.fc2.bias)
+                blk["wfc1"], blk["bfc1"] = lin(b.mlp.fc1.weight, pack.ORDER_NATURAL), pack.f32(b.mlp.fc1.bias)
+                blk["wfc2"], blk["bfc2"] = lin(b.mlp.fc2.weight, pack.ORDER_GEMM), pack.f32(b.mlp.fc2.bias)
             self.blocks.append(blk)
         self.nw, self.nb = pack.f32(mod.norm.weight), pack.f32(mod.norm.bias)
         self._pos_cache = {}
-        # 8-bit cross terms for the four linears of a block (csrc/gemm_x8.hip): fp16 split planes only, K-tile-major
-        # weight planes made once here. VDN_X8=0 keeps the three-fp16-product kernels.
-        self.x8 = (rt.split and rt.half == torch.float16 and not cfg.get("swiglu") and self.C % 64 == 0
-                   and os.environ.get("VDN_X8", "1") != "0")
-        if self.x8:
-            for blk in self.blocks:
-                blk["x8"] = {k: pack.X8(blk[k], o) for k, o in (("wqkv", pack.ORDER_NATURAL), ("wproj", pack.ORDER_ATTN),
-                                                                   ("wfc1", pack.ORDER_NATURAL), ("wfc2", pack.ORDER_GEMM))}
         # per-layer precision budget (include/vdn.h x8_terms; profiles/r03_precision_budget.md): VDN_X8_TERMS = "fc2=1,proj=1@12-23"
         # drops a cross term of the named linears (1: A_lo W_hi^T, 2: A_hi W_lo^T), optionally for blocks a..b only
         self.x8_terms = [dict(qkv=0, proj=0, fc1=0, fc2=0) for _ in self.blocks]
@@ -116,49 +119,28 @@ class EncoderEngine:
         vt = rt.hbuf("enc_vt", (Bf * Hh, 64, npad), zero=True)
         q8, k8 = rt.qk8("enc_q8", Bf * Hh, npad), rt.qk8("enc_k8", Bf * Hh, npad)  # e5m2 planes for the score cross terms
         Hd = self.hidden
-        heads = dict(dst=[rt.qk_dst(q, q8), rt.qk_dst(k, k8), rt.v_dst(vt)], dst8=[q8, k8, None], transposed=[0, 0, 1], heads=Hh, tokens=N, tpad=npad)
+        heads = rt.head_split([(q, q8), (k, k8)], vt, Hh, N, npad)
         outs, last_f32 = [], None
         readout = getattr(self, "readout", None)   # ReadoutEngine when the head was built with use_clstoken
         probe = getattr(self, "probe", None)   # tests only: callable(block index, fp32 token stream [M, C]); -1 = input of block 0
         if probe is not None:
             probe(-1, tok)
-        # 8-bit cross-term path: large batches only (its kernel has 256 x 256 tiles: M >= 4096 keeps every launch near a
-        # round of the chip or more), with the default attention (the only producer of the 8-bit output planes)
-        use8 = self.x8 and M >= int(os.environ.get("VDN_X8_MIN_ROWS", "4096")) and q8 is not None and rt.pv_products != 3
-        if use8:
-            from .runtime import HL
-            # activations between the linears as K-tile-major planes: fp16 hi + the 6-bit rows of hi and remainder — no fp16 lo plane
-            hn_k, hn8 = HL(rt.buf("enc_ln_kt", (M, C), rt.half)), rt.buf("enc_ln8", (2, M, C), torch.uint8)
-            att_k, att8 = HL(rt.buf("enc_att_kt", (M, C), rt.half)), rt.buf("enc_att8", (2, M, C), torch.uint8)
-            f1_k, f18 = HL(rt.buf("enc_fc1_kt", (M, Hd), rt.half)), rt.buf("enc_fc18", (2, M, Hd), torch.uint8)
-            kt = dict(a_kt=True, w_kt=True)
-        else:
-            hn, att, f1 = rt.hbuf("enc_ln", (M, C)), rt.hbuf("enc_att", (M, C)), rt.hbuf("enc_fc1", (M, Hd))
+        # 8-bit cross-term path: large batches only, with the default attention (the only producer of the 8-bit output planes).
+        # Its activations between the linears are K-tile-major planes: fp16 hi + the 6-bit rows of hi and remainder — no fp16 lo plane
+        use8 = self.x8 and rt.x8_rows(M) and q8 is not None and rt.pv_products != 3
+        hn, att, f1 = rt.operand("enc_ln", (M, C), use8), rt.operand("enc_att", (M, C), use8), rt.operand("enc_fc1", (M, Hd), use8)
         for i, b in enumerate(self.blocks):
-            if use8:
-                x8, xt = b["x8"], self.x8_terms[i]
-                rt.layernorm(tok, M, C, b["n1w"], b["n1b"], 1e-6, out_h=hn_k, out8=hn8, kt=True)
-                rt.gemm(hn_k, HL(x8["wqkv"].hi), M, 3 * C, C, bias=b["bqkv"], store=abi.ST_HEADS, heads=heads, tag="enc_linear",
-                        a8=hn8, w8=x8["wqkv"].p8, x8_terms=xt["qkv"], **kt)
-                rt.flash_attn(q, k, vt, att_k, Bf, Hh, N, npad, N, npad, 64 ** -0.5, tag="enc_attn", q8=q8, k8=k8, out8=att8, out_kt=True)
-                rt.gemm(att_k, HL(x8["wproj"].hi), M, C, C, bias=b["bproj"], gamma=b["ls1"], res1=tok, out=tok, tag="enc_linear",
-                        a8=att8, w8=x8["wproj"].p8, x8_terms=xt["proj"], **kt)
-                rt.layernorm(tok, M, C, b["n2w"], b["n2b"], 1e-6, out_h=hn_k, out8=hn8, kt=True)
-                rt.gemm(hn_k, HL(x8["wfc1"].hi), M, Hd, C, bias=b["bfc1"], act=GELU, out=f1_k, out8=f18, out_kt=True, tag="enc_linear",
-                        a8=hn8, w8=x8["wfc1"].p8, x8_terms=xt["fc1"], **kt)
-                rt.gemm(f1_k, HL(x8["wfc2"].hi), M, C, Hd, bias=b["bfc2"], gamma=b["ls2"], res1=tok, out=tok, tag="enc_linear",
-                        a8=f18, w8=x8["wfc2"].p8, x8_terms=xt["fc2"], **kt)
+            xt = self.x8_terms[i]
+            rt.layernorm(tok, M, C, b["n1w"], b["n1b"], 1e-6, out_h=hn)
+            rt.gemm(hn, b["wqkv"], M, 3 * C, C, bias=b["bqkv"], store=abi.ST_HEADS, heads=heads, tag="enc_linear", x8_terms=xt["qkv"])
+            rt.flash_attn(q, k, vt, att, Bf, Hh, N, npad, N, npad, 64 ** -0.5, tag="enc_attn", q8=q8, k8=k8)
+            rt.gemm(att, b["wproj"], M, C, C, bias=b["bproj"], gamma=b["ls1"], res1=tok, out=tok, tag="enc_linear", x8_terms=xt["proj"])
+            rt.layernorm(tok, M, C, b["n2w"], b["n2b"], 1e-6, out_h=hn)
+            if self.cfg.get("swiglu"):
+                rt.gemm(hn, b["wfc1"], M, 2 * Hd, C, bias=b["bfc1"], store=abi.ST_GEGLU, act=abi.ACT_SILU, out=f1, tag="enc_linear")
             else:
-                rt.layernorm(tok, M, C, b["n1w"], b["n1b"], 1e-6, out_h=hn)
-                rt.gemm(hn, b["wqkv"], M, 3 * C, C, bias=b["bqkv"], store=abi.ST_HEADS, heads=heads, tag="enc_linear")
-                rt.flash_attn(q, k, vt, att, Bf, Hh, N, npad, N, npad, 64 ** -0.5, tag="enc_attn", q8=q8, k8=k8)
-                rt.gemm(att, b["wproj"], M, C, C, bias=b["bproj"], gamma=b["ls1"], res1=tok, out=tok, tag="enc_linear")
-                rt.layernorm(tok, M, C, b["n2w"], b["n2b"], 1e-6, out_h=hn)
-                if self.cfg.get("swiglu"):
-                    rt.gemm(hn, b["wfc1"], M, 2 * Hd, C, bias=b["bfc1"], store=abi.ST_GEGLU, act=abi.ACT_SILU, out=f1, tag="enc_linear")
-                else:
-                    rt.gemm(hn, b["wfc1"], M, Hd, C, bias=b["bfc1"], act=GELU, out=f1, tag="enc_linear")
-                rt.gemm(f1, b["wfc2"], M, C, Hd, bias=b["bfc2"], gamma=b["ls2"], res1=tok, out=tok, tag="enc_linear")
+                rt.gemm(hn, b["wfc1"], M, Hd, C, bias=b["bfc1"], act=GELU, out=f1, tag="enc_linear", x8_terms=xt["fc1"])
+            rt.gemm(f1, b["wfc2"], M, C, Hd, bias=b["bfc2"], gamma=b["ls2"], res1=tok, out=tok, tag="enc_linear", x8_terms=xt["fc2"])
             if probe is not None:
                 probe(i, tok)
             if i in self.taps:
@@ -220,10 +202,16 @@ class TemporalEngine:
         blk = tt.transformer_blocks[0]
         self.gnw, self.gnb = pack.f32(tt.norm.weight), pack.f32(tt.norm.bias)
         self.w_in, self.b_in = pack.linear(tt.proj_in.weight, h), pack.f32(tt.proj_in.bias)
+        # the LayerNorm-fed linears (q|k|v of both attention blocks, the gated feed-forward's first layer: 14 of the module's
+        # 22 c^2 products per row) on the cross-term kernel when a window brings >= 4096 rows; the others take their input from
+        # kernels that write no 6-bit rows (GroupNorm, the attention over frames, the gated epilogue)
+        self.x8 = rt.x8_capable(c)
+        x8_order = pack.ORDER_NATURAL if self.x8 else None
         self.att = []
         for i in range(2):
             a = blk.attention_blocks[i]
             wqkv, _ = pack.cat_proj([a.to_q.weight, a.to_k.weight, a.to_v.weight], [None, None, None], [0, 0, 0], h)
+            wqkv = pack.Linear(wqkv, x8_order)
             rope = not hasattr(a, "pos_encoder")   # pe = 'rope' (motion_module.py:236-240): q / k rotated by frame index, no additive term
             if rope:
                 Tm = a.max_len
@@ -245,15 +233,8 @@ class TemporalEngine:
                 pe_v=(pe64 @ a.to_v.weight.detach().double().t()).float().contiguous(),
                 wo=pack.linear(a.to_out[0].weight, h), bo=pack.f32(a.to_out[0].bias)))
         self.fnw, self.fnb = pack.f32(blk.ff_norm.weight), pack.f32(blk.ff_norm.bias)
-        self.wg, self.bg = pack.geglu(blk.ff.net[0].proj.weight, blk.ff.net[0].proj.bias, h)
-        # the LayerNorm-fed linears (q|k|v of both attention blocks, the gated feed-forward's first layer: 14 of the module's
-        # 22 c^2 products per row) on the cross-term kernel when a window brings >= 4096 rows; the others take their input from
-        # kernels that write no 6-bit rows (GroupNorm, the attention over frames, the gated epilogue)
-        self.x8 = rt.split and rt.half == torch.float16 and c % 64 == 0 and os.environ.get("VDN_X8", "1") != "0"
-        if self.x8:
-            for at in self.att:
-                at["x8"] = pack.X8(at["wqkv"], pack.ORDER_NATURAL)
-            self.xg = pack.X8(self.wg, pack.ORDER_NATURAL)
+        wg, self.bg = pack.geglu(blk.ff.net[0].proj.weight, blk.ff.net[0].proj.bias, h)
+        self.wg = pack.Linear(wg, x8_order)
         self.wf2, self.bf2 = pack.linear(blk.ff.net[2].weight, h), pack.f32(blk.ff.net[2].bias)
         self.w_out, self.b_out = pack.linear(tt.proj_out.weight, h), pack.f32(tt.proj_out.bias)
 
@@ -272,31 +253,17 @@ class TemporalEngine:
         hs = rt.fbuf("tm_h", (M, c))
         rt.gemm(g, self.w_in, M, c, c, bias=self.b_in, out=hs)
         # (the kernel takes launches of >= 2^20 outputs: narrow modules of small windows stay on the three-product kernels)
-        use8 = self.x8 and M >= int(os.environ.get("VDN_X8_MIN_ROWS", "4096")) and M * 3 * c >= (1 << 20)
-        if use8:
-            from .runtime import HL
-            n_k, n8 = HL(rt.buf("tm_n_kt", (M, c), rt.half)), rt.buf("tm_n8", (2, M, c), torch.uint8)
-            kt = dict(a8=n8, a_kt=True, w_kt=True)
-        else:
-            n = rt.hbuf("tm_n", (M, c))
+        n = rt.operand("tm_n", (M, c), self.x8 and rt.x8_rows(M) and M * 3 * c >= (1 << 20))
         qkv = rt.hbuf("tm_qkv", (M, 3 * c))
         a = rt.hbuf("tm_a", (M, c))
         for at in self.att:
-            if use8:
-                rt.layernorm(hs, M, c, at["nw"], at["nb"], 1e-5, out_h=n_k, out8=n8, kt=True, addtab=at["pe"], tab_div=D, tab_mod=T)
-                rt.gemm(n_k, HL(at["x8"].hi), M, 3 * c, c, out=qkv, w8=at["x8"].p8, **kt)
-            else:
-                rt.layernorm(hs, M, c, at["nw"], at["nb"], 1e-5, out_h=n, addtab=at["pe"], tab_div=D, tab_mod=T)
-                rt.gemm(n, at["wqkv"], M, 3 * c, c, out=qkv)
+            rt.layernorm(hs, M, c, at["nw"], at["nb"], 1e-5, out_h=n, addtab=at["pe"], tab_div=D, tab_mod=T)
+            rt.gemm(n, at["wqkv"], M, 3 * c, c, out=qkv)
             rt.temporal_attn(qkv, a, B, T, D, c, 8, (c // 8) ** -0.5, rope_cs=at["rope_cs"])
             rt.gemm(a, at["wo"], M, c, c, bias=at["bo"], res1=hs, out=hs)
         gg = rt.hbuf("tm_gg", (M, 4 * c))
-        if use8:
-            rt.layernorm(hs, M, c, self.fnw, self.fnb, 1e-5, out_h=n_k, out8=n8, kt=True)
-            rt.gemm(n_k, HL(self.xg.hi), M, 8 * c, c, bias=self.bg, store=abi.ST_GEGLU, out=gg, w8=self.xg.p8, **kt)
-        else:
-            rt.layernorm(hs, M, c, self.fnw, self.fnb, 1e-5, out_h=n)
-            rt.gemm(n, self.wg, M, 8 * c, c, bias=self.bg, store=abi.ST_GEGLU, out=gg)
+        rt.layernorm(hs, M, c, self.fnw, self.fnb, 1e-5, out_h=n)
+        rt.gemm(n, self.wg, M, 8 * c, c, bias=self.bg, store=abi.ST_GEGLU, out=gg)
         hh = rt.hbuf("tm_hh", (M, c))
         rt.gemm(gg, self.wf2, M, c, 4 * c, bias=self.bf2, res1=hs, out=hh)
         return hh
@@ -350,7 +317,6 @@ class TemporalEngine:
         that tests/test_dist.py drives under gloo). Buffers are consumed in stream order, so plain local
         references keep them alive long enough."""
         from .dist import shard_core
-        from .runtime import HL
         Tl = exch.Tl
         g = self.gn(x, Tl, HW)
 
@@ -522,6 +488,13 @@ class MemoryEngine:
         self.rt, self.C, self.heads, self.max_len = rt, C, C // 64, max_len
         h = rt.prec
         ma = mod.memory_attention
+        # 8-bit cross terms for the plain linears of the memory attention and the memory encoder (as in EncoderEngine)
+        self.x8 = rt.x8_capable(C)
+
+        def lin(w, order):
+            return pack.Linear(w, order if self.x8 else None)
+
+        NAT, GEMM, ATTN = pack.ORDER_NATURAL, pack.ORDER_GEMM, pack.ORDER_ATTN
         self.layers = []
         for l in ma.layers:
             sa, ca = l.self_attn, l.cross_attn_image
@@ -533,10 +506,11 @@ class MemoryEngine:
                 n1w=pack.f32(l.norm1.weight), n1b=pack.f32(l.norm1.bias),
                 n2w=pack.f32(l.norm2.weight), n2b=pack.f32(l.norm2.bias),
                 n3w=pack.f32(l.norm3.weight), n3b=pack.f32(l.norm3.bias),
-                wqkv=wqkv, bqkv=bqkv, wso=pack.linear(sa.out_proj.weight, h), bso=pack.f32(sa.out_proj.bias),
-                wq=wq, bq=bq, wkv=wkv, bkv=bkv, wco=pack.linear(ca.out_proj.weight, h), bco=pack.f32(ca.out_proj.bias),
-                w1=pack.linear(l.linear1.weight, h), b1=pack.f32(l.linear1.bias),
-                w2=pack.linear(l.linear2.weight, h), b2=pack.f32(l.linear2.bias)))
+                wqkv=lin(wqkv, NAT), bqkv=bqkv, wso=lin(pack.linear(sa.out_proj.weight, h), ATTN), bso=pack.f32(sa.out_proj.bias),
+                wq=lin(wq, NAT), bq=bq, wkv=lin(wkv, NAT), bkv=bkv,
+                wco=lin(pack.linear(ca.out_proj.weight, h), ATTN), bco=pack.f32(ca.out_proj.bias),
+                w1=lin(pack.linear(l.linear1.weight, h), NAT), b1=pack.f32(l.linear1.bias),
+                w2=lin(pack.linear(l.linear2.weight, h), GEMM), b2=pack.f32(l.linear2.bias)))
         self.nw, self.nb = pack.f32(ma.norm.weight), pack.f32(ma.norm.bias)
         self.curr_pos = pack.f32(mod.curr_pos_enc).reshape(-1)
         self.no_mem = mod.no_mem_embed.detach().float().reshape(1, -1)
@@ -555,17 +529,8 @@ class MemoryEngine:
             self.cx.append(dict(
                 wdw=b.dwconv.weight.detach().float().reshape(C, 49).t().contiguous(), bdw=pack.f32(b.dwconv.bias),
                 nw=pack.f32(b.norm.weight), nb=pack.f32(b.norm.bias),
-                w1=pack.linear(b.pwconv1.weight, h), b1=pack.f32(b.pwconv1.bias),
-                w2=pack.linear(b.pwconv2.weight, h), b2=pack.f32(b.pwconv2.bias), g=pack.f32(b.gamma)))
-        # 8-bit cross terms for the plain linears of the memory attention and the memory encoder (as in EncoderEngine)
-        self.x8 = rt.split and rt.half == torch.float16 and C % 64 == 0 and os.environ.get("VDN_X8", "1") != "0"
-        if self.x8:
-            for L in self.layers:
-                L["x8"] = {k: pack.X8(L[k], o) for k, o in (("wqkv", pack.ORDER_NATURAL), ("wso", pack.ORDER_ATTN), ("wq", pack.ORDER_NATURAL),
-                                                            ("wco", pack.ORDER_ATTN), ("w1", pack.ORDER_NATURAL), ("w2", pack.ORDER_GEMM),
-                                                            ("wkv", pack.ORDER_NATURAL))}
-            for cx in self.cx:
-                cx["x8"] = {"w1": pack.X8(cx["w1"], pack.ORDER_NATURAL), "w2": pack.X8(cx["w2"], pack.ORDER_GEMM)}
+                w1=lin(pack.linear(b.pwconv1.weight, h), NAT), b1=pack.f32(b.pwconv1.bias),
+                w2=lin(pack.linear(b.pwconv2.weight, h), GEMM), b2=pack.f32(b.pwconv2.bias), g=pack.f32(b.gamma)))
         # Bank state shared by every lane copy of this engine (DepthAnythingV2._stream_lanes): ONE ring for the whole
         # batch, lane i of n works on batch rows [i B/n, (i+1) B/n) of it, so laned and single-lane calls see the
         # same memory and `count` advances once per forward (commit()).
@@ -649,37 +614,14 @@ class MemoryEngine:
             k8s = [rt.qk8(f"nomem_k8{l}", B * Hh, pp) for l in range(len(self.layers))]
             for l, L in enumerate(self.layers):
                 rt.gemm(a_nm, L["wkv"], M, 2 * C, C, bias=L["bkv"], store=abi.ST_HEADS,
-                        heads=dict(dst=[rt.qk_dst(ks[l], k8s[l]), rt.v_dst(vs[l])], dst8=[k8s[l], None], transposed=[0, 1], rope=[1, 0], rope_cs=cs,
-                                   rope_mod=P, heads=Hh, tokens=P, tpad=pp))
+                        heads=rt.head_split([(ks[l], k8s[l])], vs[l], Hh, P, pp, rope_cs=cs, rope_mod=P))
         else:
             nk, nk_pad = S * P, tp
-        sh = dict(dst=[rt.qk_dst(q, q8), rt.qk_dst(k, k8), rt.v_dst(vt)], dst8=[q8, k8, None], transposed=[0, 0, 1], rope=[1, 1, 0], rope_cs=cs, rope_mod=P, heads=Hh,
-                  tokens=P, tpad=pp)
-        qh = dict(dst=[rt.qk_dst(q, q8)], dst8=[q8], transposed=[0], rope=[1], rope_cs=cs, rope_mod=P, heads=Hh, tokens=P, tpad=pp)
-        use8 = self.x8 and M >= int(os.environ.get("VDN_X8_MIN_ROWS", "4096")) and q8 is not None and rt.pv_products != 3
-        if use8:   # K-tile-major fp16 hi + planes of 6-bit rows between the linears (no fp16 lo plane), as in EncoderEngine.run
-            from .runtime import HL
-            n_k, n8 = HL(rt.buf("ma_n_kt", (M, C), rt.half)), rt.buf("ma_n8", (2, M, C), torch.uint8)
-            att_k, att8 = HL(rt.buf("ma_att_kt", (M, C), rt.half)), rt.buf("ma_att8", (2, M, C), torch.uint8)
-            h2_k, h28 = HL(rt.buf("ma_h2_kt", (M, 2 * C), rt.half)), rt.buf("ma_h28", (2, M, 2 * C), torch.uint8)
-            kt = dict(a_kt=True, w_kt=True)
-            for l, L in enumerate(self.layers):
-                x8 = L["x8"]
-                rt.layernorm(x, M, C, L["n1w"], L["n1b"], 1e-5, out_h=n_k, out8=n8, kt=True)
-                rt.gemm(n_k, HL(x8["wqkv"].hi), M, 3 * C, C, bias=L["bqkv"], store=abi.ST_HEADS, heads=sh, a8=n8, w8=x8["wqkv"].p8, **kt)
-                rt.flash_attn(q, k, vt, att_k, B, Hh, P, pp, P, pp, 0.125, q8=q8, k8=k8, out8=att8, out_kt=True)
-                rt.gemm(att_k, HL(x8["wso"].hi), M, C, C, bias=L["bso"], res1=x, out=x, a8=att8, w8=x8["wso"].p8, **kt)
-                rt.layernorm(x, M, C, L["n2w"], L["n2b"], 1e-5, out_h=n_k, out8=n8, kt=True, addvec=self.curr_pos, alpha=1.0)
-                rt.gemm(n_k, HL(x8["wq"].hi), M, C, C, bias=L["bq"], store=abi.ST_HEADS, heads=qh, a8=n8, w8=x8["wq"].p8, **kt)
-                rt.flash_attn(q, ks[l], vs[l], att_k, B, Hh, P, pp, nk, nk_pad, 0.125, q8=q8, k8=k8s[l], out8=att8, out_kt=True)
-                rt.gemm(att_k, HL(x8["wco"].hi), M, C, C, bias=L["bco"], res1=x, out=x, a8=att8, w8=x8["wco"].p8, **kt)
-                rt.layernorm(x, M, C, L["n3w"], L["n3b"], 1e-5, out_h=n_k, out8=n8, kt=True)
-                rt.gemm(n_k, HL(x8["w1"].hi), M, 2 * C, C, bias=L["b1"], act=GELU, out=h2_k, out8=h28, out_kt=True, a8=n8, w8=x8["w1"].p8, **kt)
-                rt.gemm(h2_k, HL(x8["w2"].hi), M, C, 2 * C, bias=L["b2"], res1=x, out=x, a8=h28, w8=x8["w2"].p8, **kt)
-            out = rt.hbuf("mem_out", (M, C))
-            rt.layernorm(x, M, C, self.nw, self.nb, 1e-5, out_h=out)
-            return out
-        n, att, h2 = rt.hbuf("ma_n", (M, C)), rt.hbuf("ma_att", (M, C)), rt.hbuf("ma_h2", (M, 2 * C))   # split planes of the 3-product path
+        sh = rt.head_split([(q, q8), (k, k8)], vt, Hh, P, pp, rope_cs=cs, rope_mod=P)
+        qh = rt.head_split([(q, q8)], None, Hh, P, pp, rope_cs=cs, rope_mod=P)
+        # cross-term path: K-tile-major fp16 hi + planes of 6-bit rows between the linears (no fp16 lo plane), as in EncoderEngine.run
+        use8 = self.x8 and rt.x8_rows(M) and q8 is not None and rt.pv_products != 3
+        n, att, h2 = rt.operand("ma_n", (M, C), use8), rt.operand("ma_att", (M, C), use8), rt.operand("ma_h2", (M, 2 * C), use8)
         for l, L in enumerate(self.layers):
             rt.layernorm(x, M, C, L["n1w"], L["n1b"], 1e-5, out_h=n)
             rt.gemm(n, L["wqkv"], M, 3 * C, C, bias=L["bqkv"], store=abi.ST_HEADS, heads=sh)
@@ -712,40 +654,21 @@ class MemoryEngine:
         x = rt.fbuf("me_x", (M, C))
         rt.gemm(mem_out, self.wpix, M, C, C, bias=self.bpix, rowadd=m2, out=x)
         d = rt.fbuf("me_dw", (M, C))
-        use8 = self.x8 and M >= int(os.environ.get("VDN_X8_MIN_ROWS", "4096"))
-        if use8:
-            from .runtime import HL
-            n_k, n8 = HL(rt.buf("me_n_kt", (M, C), rt.half)), rt.buf("me_n8", (2, M, C), torch.uint8)
-            h4_k, h48 = HL(rt.buf("me_h4_kt", (M, 4 * C), rt.half)), rt.buf("me_h48", (2, M, 4 * C), torch.uint8)
-            feat = None   # the memory feature stays in the fp32 stream x and goes straight to the projections' operand planes
-        else:
-            n, h4, feat = rt.hbuf("me_n", (M, C)), rt.hbuf("me_h4", (M, 4 * C)), rt.hbuf("mem_feat", (M, C))
-        for j, cx in enumerate(self.cx):
+        # Cross-term path: every ConvNeXt block runs in place on the fp32 stream x, and one pass turns x into the A operand of the
+        # pushed frame's key / value projections. Otherwise the last block writes that operand, the mem_feat split planes.
+        use8 = self.x8 and rt.x8_rows(M)
+        n, h4, feat = rt.operand("me_n", (M, C), use8), rt.operand("me_h4", (M, 4 * C), use8), rt.operand("mem_feat", (M, C), use8)
+        for cx in self.cx:
             rt.dwconv7(x, d, B, ph, pw, C, cx["wdw"], cx["bdw"])
-            if use8:
-                x8 = cx["x8"]
-                rt.layernorm(d, M, C, cx["nw"], cx["nb"], 1e-6, out_h=n_k, out8=n8, kt=True)
-                rt.gemm(n_k, HL(x8["w1"].hi), M, 4 * C, C, bias=cx["b1"], act=GELU, out=h4_k, out8=h48, out_kt=True, a8=n8, w8=x8["w1"].p8,
-                        a_kt=True, w_kt=True)
-                rt.gemm(h4_k, HL(x8["w2"].hi), M, C, 4 * C, bias=cx["b2"], gamma=cx["g"], res1=x, out=x, a8=h48, w8=x8["w2"].p8, a_kt=True, w_kt=True)
-                continue
             rt.layernorm(d, M, C, cx["nw"], cx["nb"], 1e-6, out_h=n)
             rt.gemm(n, cx["w1"], M, 4 * C, C, bias=cx["b1"], act=GELU, out=h4)
-            rt.gemm(h4, cx["w2"], M, C, 4 * C, bias=cx["b2"], gamma=cx["g"], res1=x, out=(x if j == 0 else feat))
+            rt.gemm(h4, cx["w2"], M, C, 4 * C, bias=cx["b2"], gamma=cx["g"], res1=x,
+                    out=(feat if cx is self.cx[-1] and not use8 else x))
+        if use8:
+            rt.pack_x8_f32(x, feat.hi, feat.p8)
         ks, vs, k8s, tp = self._bank(B, P)
         slot = self.state["count"] % self.max_len  # commit() advances the count once every lane has pushed
         cs = self._rope_for(int(math.sqrt(P)))
-        if use8:
-            # the four key / value projections of the pushed frame on the cross-term kernel: one pass turns the fp32 memory feature
-            # into their A operand (K-tile-major hi plane + 6-bit rows); its two ConvNeXt blocks both ran in place on x
-            feat_k, feat8 = HL(rt.buf("mem_feat_kt", (M, C), rt.half)), rt.buf("mem_feat8", (2, M, C), torch.uint8)
-            rt.pack_x8_f32(x, feat_k.hi, feat8)
         for l, L in enumerate(self.layers):
-            hd = dict(dst=[rt.qk_dst(ks[l], k8s[l]), rt.v_dst(vs[l])], dst8=[k8s[l], None], transposed=[0, 1], rope=[1, 0], rope_cs=cs, rope_mod=P,
-                      heads=Hh, tokens=P, tok_off=slot * P, tpad=tp)
-            if use8:
-                xw = L["x8"]["wkv"]
-                rt.gemm(feat_k, HL(xw.hi), M, 2 * C, C, bias=L["bkv"], store=abi.ST_HEADS, heads=hd, a8=feat8, w8=xw.p8, a_kt=True, w_kt=True)
-            else:
-                rt.gemm(feat, L["wkv"], M, 2 * C, C, bias=L["bkv"], store=abi.ST_HEADS, heads=hd)
-        return feat
+            rt.gemm(feat, L["wkv"], M, 2 * C, C, bias=L["bkv"], store=abi.ST_HEADS,
+                    heads=rt.head_split([(ks[l], k8s[l])], vs[l], Hh, P, tp, rope_cs=cs, rope_mod=P, tok_off=slot * P))

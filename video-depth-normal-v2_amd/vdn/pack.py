@@ -204,6 +204,17 @@ class X8:
                                       self.p8.data_ptr(), 1, order, _stream(w.hi)), "vdn_pack_x8")
 
 
+class Linear:
+    """A packed linear weight as Runtime.gemm takes it: `hl`, the split planes of the three-product kernels (what linear /
+    cat_proj / geglu return), and `x8`, the cross-term planes in the stream `order` of the kernel that writes this linear's
+    input, or None (order None: the engine cannot use that kernel). The activation's form picks the plane set per launch.
+    Holds no Runtime: lane copies of an engine share it."""
+    __slots__ = ("hl", "x8")
+
+    def __init__(self, hl, order: Optional[int] = None):
+        self.hl, self.x8 = hl, (None if order is None else X8(hl, order))
+
+
 def rope_table(side_y: int, side_x: int, dim: int = 64, theta: float = 10000.0, device=None) -> torch.Tensor:
     """(cos, sin) of sam2 compute_axial_cis (position_encoding.py:192-201): f32 [side_y*side_x, dim/2, 2].
     Pairs 0..dim/4-1 rotate with the x coordinate, dim/4..dim/2-1 with y."""

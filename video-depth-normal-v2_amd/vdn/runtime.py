@@ -16,6 +16,7 @@ import torch
 
 from . import _abi as abi
 from ._abi import F16, BF16, F32
+from .pack import Linear, Prec
 
 _TDT = {torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32}
 _POISON = bool(int(__import__("os").environ.get("VDN_POISON", "0")))
@@ -63,11 +64,21 @@ class HL:
         return self
 
 
+class KT:
+    """An activation in the cross-term GEMM's operand form (include/vdn.h A8 / a_kt): `hi`, the fp16 hi plane
+    K-tile-major, and `p8`, u8 [2, rows, K], the 6-bit rows of hi and of the remainder. There is no fp16 lo plane. Written by
+    the LayerNorm, attention and GELU epilogues or by pack_x8 / pack_x8_f32; Runtime.operand hands it out."""
+    __slots__ = ("hi", "p8")
+
+    def __init__(self, hi: torch.Tensor, p8: torch.Tensor):
+        self.hi, self.p8 = hi, p8
+
+
 def _hl(t):
-    """(hi tensor, lo pointer or None) of an HL or a plain tensor."""
+    """(hi tensor, lo pointer or None) of an HL, a KT or a plain tensor."""
     if isinstance(t, HL):
         return t.hi, (None if t.lo is None else t.lo.data_ptr())
-    return t, None
+    return (t.hi, None) if isinstance(t, KT) else (t, None)
 
 
 class Runtime:
@@ -77,7 +88,6 @@ class Runtime:
         self.device = device
         self.half = half
         self.split = split
-        from .pack import Prec
         self.prec = Prec(half, split)
         self.dt = _TDT[half]
         self.zeros = torch.zeros(256, dtype=torch.uint8, device=device)
@@ -104,6 +114,24 @@ class Runtime:
         hi = self.buf(name, shape, self.half, zero)
         return HL(hi, self.buf(name + "#lo", shape, self.half, zero) if self.split else None)
 
+    def operand(self, name: str, shape, x8: bool = False):
+        """An activation between two linears, by name: the split planes of hbuf, or with `x8` (this call takes the cross-term
+        kernel) the KT form, under the arena keys name_kt and name8."""
+        if not x8:
+            return self.hbuf(name, shape)
+        return KT(self.buf(name + "_kt", shape, self.half), self.buf(name + "8", (2, *shape), torch.uint8))
+
+    def x8_capable(self, Cn: int) -> bool:
+        """Can an engine whose linears are Cn wide use the cross-term kernel (csrc/gemm_x8.hip)? fp16 split planes only;
+        VDN_X8=0 keeps the three-fp16-product kernels."""
+        return self.split and self.half == torch.float16 and Cn % 64 == 0 and os.environ.get("VDN_X8", "1") != "0"
+
+    @staticmethod
+    def x8_rows(M: int) -> bool:
+        """Does a call with M rows take it? Its tiles are 256 x 256: M >= 4096 keeps every launch near a round of the chip
+        or more."""
+        return M >= int(os.environ.get("VDN_X8_MIN_ROWS", "4096"))
+
     def to_half(self, x: torch.Tensor) -> HL:
         return HL.from_float(x, self.half, self.split)
 
@@ -129,6 +157,14 @@ class Runtime:
         if self.pv_products == 3:
             return t   # the 3-product P V kernel (flash_attn_kernel<.., false, false>) takes its score cross terms from the fp16 lo planes
         return HL(t.hi, None) if (t8 is not None and t.lo is not None) else t
+
+    def head_split(self, qk, vt, heads: int, tokens: int, tpad: int, rope_cs=None, rope_mod: int = 0, tok_off: int = 0) -> dict:
+        """`heads=` of an ST_HEADS gemm: `qk`, the (planes, 8-bit planes) pairs of its Q / K-like splits in order, then `vt`,
+        the V^T planes of the last split, or None. With a RoPE table the Q / K splits are rotated."""
+        nv = int(vt is not None)
+        return dict(dst=[self.qk_dst(t, t8) for t, t8 in qk] + [self.v_dst(vt) for _ in range(nv)], dst8=[t8 for _, t8 in qk] + [None] * nv,
+                    transposed=[0] * len(qk) + [1] * nv, rope=[int(rope_cs is not None)] * len(qk) + [0] * nv, rope_cs=rope_cs,
+                    rope_mod=rope_mod, heads=heads, tokens=tokens, tok_off=tok_off, tpad=tpad)
 
     def fbuf(self, name, shape, zero=False):
         return self.buf(name, shape, torch.float32, zero)
@@ -161,6 +197,20 @@ class Runtime:
              row_skip: int = 0, heads: Optional[dict] = None, convt: Optional[dict] = None, tag: Optional[str] = None,
              a8: Optional[torch.Tensor] = None, w8: Optional[torch.Tensor] = None, out8: Optional[torch.Tensor] = None,
              a_kt: bool = False, w_kt: bool = False, out_kt: bool = False, x8_terms: int = 0):
+        """A, W and out may be operand objects: a pack.Linear weight follows its activation, on the cross-term kernel for a KT
+        (a8 / w8 / a_kt / w_kt filled from the two), else on its split planes, where x8_terms does not apply; a KT `out`
+        fills out8 / out_kt. The keywords give the same planes by hand (tests and tools)."""
+        if isinstance(W, Linear):
+            if not isinstance(A, KT):
+                W, x8_terms = W.hl, 0
+            elif W.x8 is None:
+                raise abi.VdnError("vdn_gemm: a cross-term (KT) activation needs a weight packed with X8 planes")
+            else:
+                a8, w8, a_kt, w_kt, W = A.p8, W.x8.p8, True, True, W.x8.hi
+        elif isinstance(A, KT):
+            raise abi.VdnError("vdn_gemm: a cross-term (KT) activation needs a pack.Linear weight")
+        if isinstance(out, KT):
+            out8, out_kt = out.p8, True
         d = abi.GemmDesc()
         d.dt = self.dt
         d.M, d.N, d.K = M, N, K
@@ -236,7 +286,10 @@ class Runtime:
     def layernorm(self, x: torch.Tensor, rows: int, Cn: int, w, b, eps: float, *, out_h=None, out_f=None, addvec=None,
                   alpha: float = 1.0, addtab=None, tab_div: int = 1, tab_mod: int = 1, out_group: int = 0, out8=None,
                   kt: bool = False):
-        """out8: u8 [2, rows, C] planes of 6-bit rows of the output for the cross-term GEMM (include/vdn.h A8); kt: K-tile-major planes."""
+        """out8: u8 [2, rows, C] planes of 6-bit rows of the output for the cross-term GEMM (include/vdn.h A8); kt: K-tile-major planes.
+        A KT `out_h` gives both."""
+        if isinstance(out_h, KT):
+            out8, kt = out_h.p8, True
         oh, ol = _hl(out_h) if out_h is not None else (None, None)
         self._launch(abi.lib.vdn_layernorm, x.data_ptr(), _TDT[x.dtype], rows, Cn, w.data_ptr(), b.data_ptr(), eps,
                      self._p(addvec), alpha, self._p(addtab), tab_div, tab_mod, out_group, self._p(oh), ol, self.dt,
@@ -246,7 +299,10 @@ class Runtime:
                    tag: Optional[str] = None, q8: Optional[torch.Tensor] = None, k8: Optional[torch.Tensor] = None,
                    out8: Optional[torch.Tensor] = None, out_kt: bool = False):
         """q8 / k8: the u8 [B*H, n_pad, 128] planes the projection wrote through heads['dst8'] (8-bit cross terms).
-        out8 / out_kt: planes of 6-bit rows of the output and the K-tile-major layout for the cross-term GEMM that follows."""
+        out8 / out_kt: planes of 6-bit rows of the output and the K-tile-major layout for the cross-term GEMM that follows;
+        a KT `out` gives both."""
+        if isinstance(out, KT):
+            out8, out_kt = out.p8, True
         (Q, ql), (K, kl), (Vt, vl), (out, ol) = _hl(Q), _hl(K), _hl(Vt), _hl(out)
         self._launch(abi.lib.vdn_flash_attn, self.dt, Q.data_ptr(), K.data_ptr(), Vt.data_ptr(), out.data_ptr(), ql, kl,
                      vl, ol, self._p(q8), self._p(k8), self._p(out8), int(out_kt), B, H, nq, nq_pad, nk, nk_pad, scale, self.pv_products, tag=tag,

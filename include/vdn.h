@@ -350,6 +350,19 @@ int vdn_depth_tail(int dt, const float* x, int B, int IH, int IW, int C, const v
                    const float* bias2, const float* w1, float b1, float* depth, int OH, int OW, int relu,
                    vdn_stream stream);
 
+/* output_conv1 of a 2x up-sampled map without the up-sampled map (depth_anything_v2/dpt.py:145 on the path_1 of
+ * util/blocks.py:144-146): Conv3x3(pad 1) o bilinear(align_corners=True) o Conv1x1 is linear with no activation in between,
+ * so the channel mixing of all nine taps runs as ONE vdn_gemm at the low resolution (weight rows t*Co + c = W_t Wo, bias
+ * W_t bo, t = 3 ky + kx; vdn/pack.py lowres_oc1) and this entry does what is left, which is memory traffic:
+ *   z f32 [B, IH, IW, 9*Co] -> out f32 [B, OH, OW, Co],
+ *   out[b, y, x, c] = bias[c] + sum over the taps t with (y + ky - 1, x + kx - 1) inside OH x OW of
+ *                     bilinear(z[b, :, :, t*Co + c]; that position), source coordinates as vdn_upsample_bilinear computes them.
+ * A tap in the zero padding drops out whole (its share of the 1x1 bias rides inside z). Co % 16 == 0. A workgroup stages the
+ * source patch of its 16 x 16 output pixels in LDS, so (IH-1)/(OH-1) must be about 1/2 or less (VDN_EUNSUPPORTED when the
+ * patch outgrows the LDS). No atomics: deterministic.                                                                     */
+int vdn_oc1_combine(const float* z, const float* bias, float* out, int B, int IH, int IW, int OH, int OW, int Co,
+                    vdn_stream stream);
+
 /* Depth + normal model (models/video_depth_model.py:64-119 with the VideoDepthAnythingHeadV2 head of
  * models/video_depth_head_v2_sangyu.py). Tokens are frame-major channel-last rows [B*S*h*w, C].
  * vdn_dn_attn     — nn.MultiheadAttention(C, heads, batch_first) self-attention (video_depth_head_v2_sangyu.py:67,

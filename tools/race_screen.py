@@ -129,6 +129,19 @@ for _ in range(reps // 4):
     diff += int(not torch.equal(d, d0))
 bad += diff
 print(f"depth_tail B=8 296->518: {diff} of {reps // 4} runs differ", flush=True)
+# output_conv1's combine pass (LDS-staged source patch, plain stores, no atomics)
+z = torch.randn(4 * 148 * 148, 9 * 128, device="cuda")
+b1 = torch.randn(128, device="cuda")
+o = torch.empty(4 * 296 * 296, 128, device="cuda")
+rt.oc1_combine(z, b1, o, 4, 148, 148, 296, 296, 128)
+o0 = o.clone()
+diff = 0
+for _ in range(reps // 4):
+    rt.oc1_combine(z, b1, o, 4, 148, 148, 296, 296, 128)
+    diff += int(not torch.equal(o, o0))
+bad += diff
+print(f"oc1_combine B=4 148->296: {diff} of {reps // 4} runs differ", flush=True)
+del z, o, o0
 t = torch.randn(10960, 1024, device="cuda")
 g, be = torch.randn(1024, device="cuda"), torch.randn(1024, device="cuda")
 oh = rt.hbuf("rs_ln", (10960, 1024))

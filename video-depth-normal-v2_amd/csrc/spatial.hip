@@ -383,6 +383,105 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const float* __restrict__ 
   }
 }
 
+// vdn_oc1_combine: conv3x3(pad 1) of a 2x bilinear up-sampling, with the channel mixing already done at the LOW resolution.
+// z [B, IH, IW, 9, Co] holds per source pixel the nine tap images Z_t (tap bias included); an output value is the sum over
+// the taps that stay inside the OH x OW map of Z_t sampled bilinearly at the tap's position — ac_coord, the expression
+// upsample_kernel uses, so the sample positions are those of the materialised map. One workgroup owns OC_T x OC_T output
+// pixels x CS channels and stages the source patch those read (11 x 11 pixels at scale 1/2) in LDS once: z crosses the
+// memory system about twice (halo) instead of 36 times.
+constexpr int OC_T = 16, OC_NT = 512;  // output tile side, threads per workgroup
+__host__ __device__ inline int oc_src0(int o, float scale, int in) {  // ac_coord's i0
+  const int i0 = (int)(scale * (float)o);
+  return i0 < in - 1 ? i0 : in - 1;
+}
+template <int CS>
+__global__ __launch_bounds__(OC_NT) void oc1_combine_kernel(const float* __restrict__ z, const float* __restrict__ bias,
+                                                          float* __restrict__ out, int IH, int IW, int OH, int OW, int Co,
+                                                          int max_pix) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sz = (float*)smem;  // [patch pixel][tap][CS]
+  constexpr int V = CS / 4;
+  const float sy = OH > 1 ? (float)(IH - 1) / (float)(OH - 1) : 0.f;
+  const float sx = OW > 1 ? (float)(IW - 1) / (float)(OW - 1) : 0.f;
+  const int slices = Co / CS, txn = (OW + OC_T - 1) / OC_T, tyn = (OH + OC_T - 1) / OC_T;
+  int bid = blockIdx.x;
+  const int cs = (bid % slices) * CS;
+  bid /= slices;
+  const int ox0 = (bid % txn) * OC_T;
+  bid /= txn;
+  const int oy0 = (bid % tyn) * OC_T, b = bid / tyn;
+  // source rows / columns that the tile's sample positions [o0 - 1, o0 + OC_T] (clipped to the map) touch
+  const int ylast = oy0 + OC_T < OH - 1 ? oy0 + OC_T : OH - 1, xlast = ox0 + OC_T < OW - 1 ? ox0 + OC_T : OW - 1;
+  const int py0 = oc_src0(oy0 > 0 ? oy0 - 1 : 0, sy, IH), px0 = oc_src0(ox0 > 0 ? ox0 - 1 : 0, sx, IW);
+  int py1 = oc_src0(ylast, sy, IH), px1 = oc_src0(xlast, sx, IW);
+  py1 = py1 < IH - 1 ? py1 + 1 : py1;
+  px1 = px1 < IW - 1 ? px1 + 1 : px1;
+  const int nph = py1 - py0 + 1, npw = px1 - px0 + 1;
+  if (nph * npw > max_pix) return;  // the host sized the LDS for every tile of this shape: never taken
+  const float* zb = z + ((size_t)b * IH * IW) * 9 * Co + cs;
+  const int total = nph * npw * 9 * V;
+  constexpr int U = 9;  // loads in flight per thread before the first LDS write: the 11 x 11 patch in one pass
+  for (int base = threadIdx.x; base < total; base += OC_NT * U) {
+    f32x4 r[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = base + u * OC_NT;
+      if (i < total) {
+        const int v = i % V, t = (i / V) % 9, p = i / (9 * V);
+        const int pr = p / npw, pc = p - pr * npw;
+        r[u] = *(const f32x4*)(zb + ((size_t)(py0 + pr) * IW + px0 + pc) * 9 * Co + t * Co + v * 4);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = base + u * OC_NT;
+      if (i < total) *(f32x4*)(sz + (size_t)i * 4) = r[u];  // i = (p * 9 + t) * V + v
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < OC_T * OC_T * V; i += OC_NT) {
+    const int v = i % V, pix = i / V;
+    const int oy = oy0 + pix / OC_T, ox = ox0 + pix % OC_T;
+    if (oy >= OH || ox >= OW) continue;
+    int xa[3], xb[3];
+    float xl[3];
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int xx = ox + kx - 1;
+      int x0 = 0, x1 = 0;
+      float l = 0.f;
+      if (xx >= 0 && xx < OW) ac_coord(xx, sx, IW, x0, x1, l);
+      xa[kx] = (x0 - px0) * 9 * CS;
+      xb[kx] = (x1 - px0) * 9 * CS;
+      xl[kx] = l;
+    }
+    f32x4 acc = *(const f32x4*)(bias + cs + v * 4);
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const int yy = oy + ky - 1;
+      if (yy < 0 || yy >= OH) continue;
+      int y0, y1;
+      float ly;
+      ac_coord(yy, sy, IH, y0, y1, ly);
+      const float* r0 = sz + (size_t)(y0 - py0) * npw * 9 * CS + v * 4;
+      const float* r1 = sz + (size_t)(y1 - py0) * npw * 9 * CS + v * 4;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int xx = ox + kx - 1;
+        if (xx < 0 || xx >= OW) continue;
+        const int t = (ky * 3 + kx) * CS;
+        const float lx = xl[kx];
+        const f32x4 a00 = *(const f32x4*)(r0 + xa[kx] + t), a01 = *(const f32x4*)(r0 + xb[kx] + t);
+        const f32x4 a10 = *(const f32x4*)(r1 + xa[kx] + t), a11 = *(const f32x4*)(r1 + xb[kx] + t);
+        // the four corner weights once per tap instead of three lerps per channel (the kernel is VALU- and LDS-heavy)
+        const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
+        acc += w00 * a00 + w01 * a01 + (w10 * a10 + w11 * a11);
+      }
+    }
+    *(f32x4*)(out + (((size_t)b * OH + oy) * OW + ox) * Co + cs + v * 4) = acc;
+  }
+}
+
 inline int grid_for(size_t work, int cap = 4096) {
   const size_t b = (work + 255) / 256;
   return (int)(b < (size_t)cap ? (b ? b : 1) : cap);
@@ -413,6 +512,38 @@ extern "C" int vdn_upsample_bilinear_f32(const float* x, float* y, int B, int IH
   if (!x || !y || B <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return VDN_EINVAL;
   hipLaunchKernelGGL(upsample_f32_kernel, dim3(grid_for((size_t)B * OH * OW)), dim3(256), 0, (hipStream_t)stream, x, y,
                      B, IH, IW, OH, OW, relu);
+  VDN_CHECK_LAUNCH();
+  return VDN_OK;
+}
+
+extern "C" int vdn_oc1_combine(const float* z, const float* bias, float* out, int B, int IH, int IW, int OH, int OW, int Co,
+                               vdn_stream stream) {
+  if (!z || !bias || !out || B <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || Co <= 0) return VDN_EINVAL;
+  if ((Co & 15) || (((uintptr_t)z | (uintptr_t)bias | (uintptr_t)out) & 15)) return VDN_EALIGN;
+  // the largest source patch any tile stages, with the kernel's own expressions
+  const float sy = OH > 1 ? (float)(IH - 1) / (float)(OH - 1) : 0.f;
+  const float sx = OW > 1 ? (float)(IW - 1) / (float)(OW - 1) : 0.f;
+  auto span = [](int O, int I, float s) {
+    int worst = 0;
+    for (int o0 = 0; o0 < O; o0 += OC_T) {
+      const int last = o0 + OC_T < O - 1 ? o0 + OC_T : O - 1;
+      int p1 = oc_src0(last, s, I);
+      p1 = p1 < I - 1 ? p1 + 1 : p1;
+      const int n = p1 - oc_src0(o0 > 0 ? o0 - 1 : 0, s, I) + 1;
+      worst = n > worst ? n : worst;
+    }
+    return worst;
+  };
+  const int max_pix = span(OH, IH, sy) * span(OW, IW, sx);
+  constexpr int CS = 16;  // 11 x 11 pixels x 9 taps x 16 channels x 4 B = 68 KiB: two workgroups per CU
+  const size_t lds = (size_t)max_pix * 9 * CS * sizeof(float);
+  if (lds > 160 * 1024) return VDN_EUNSUPPORTED;  // scale well above 1/2: not a 2x up-sampling
+  const size_t blocks = (size_t)B * ((OH + OC_T - 1) / OC_T) * ((OW + OC_T - 1) / OC_T) * (Co / CS);
+  if (blocks >= (1u << 31)) return VDN_EUNSUPPORTED;
+  static const hipError_t attr = hipFuncSetAttribute((const void*)oc1_combine_kernel<CS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (attr != hipSuccess) return -(1000 + (int)attr);
+  hipLaunchKernelGGL(oc1_combine_kernel<CS>, dim3((unsigned)blocks), dim3(OC_NT), lds, (hipStream_t)stream, z, bias, out, IH, IW, OH,
+                     OW, Co, max_pix);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

@@ -367,6 +367,12 @@ class DPTEngine:
         w2 = s.output_conv2[0].weight
         fused = h.split and w2.shape[0] == 32 and w2.shape[1] % 32 == 0 and not os.environ.get("VDN_TAIL_UNFUSED")  # A/B switch
         self.oc2_taps = pack.conv3x3_taps(w2, h) if fused else None
+        # output_conv1 in front of refinenet1's 2x resize (run()): the nine taps composed with out_conv, once per checkpoint.
+        # Only the fused tail reads an fp32 out1; VDN_OC1_HIRES forces the materialised path1 (A/B switch)
+        self.oc1_low = None
+        if fused and (features // 2) % 16 == 0 and not os.environ.get("VDN_OC1_HIRES"):
+            f1 = s.refinenet1.out_conv
+            self.oc1_low = pack.lowres_oc1(s.output_conv1.weight, f1.weight, f1.bias, h)
         self.w_last = pack.f32(s.output_conv2[2].weight).reshape(-1)
         self.b_last = float(s.output_conv2[2].bias.detach().float().item())
         self.temporal = None
@@ -400,6 +406,8 @@ class DPTEngine:
         if skip is not None:
             x = self._rcu(f["r1"], skip, Bf, H, W, f"ff{i}_s", extra=prev)
         u = self._rcu(f["r2"], x, Bf, H, W, f"ff{i}_u")
+        if size_out is None:  # run(): out_conv and the resize are taken over by the low-resolution output_conv1
+            return u
         v = rt.hbuf(f"ff{i}_v", (Bf * H * W, F))
         rt.gemm(u, f["wo"], Bf * H * W, F, F, bias=f["bo"], out=v)
         OH, OW = size_out
@@ -450,13 +458,27 @@ class DPTEngine:
             p3 = tm(3, p3, s2[0] * s2[1])
         p2 = self._fusion(2, Bf, s2, s1, p3, r2)
         s0 = (2 * s1[0], 2 * s1[1])
-        p1 = self._fusion(1, Bf, s1, s0, p2, r1)
         H, W = ph * PATCH, pw * PATCH
         if out is not None:
             assert out.shape == (Bf, H, W) and out.dtype == torch.float32 and out.is_contiguous(), (out.shape, out.dtype)
         depth = out if out is not None else rt.fbuf("depth", (Bf, H, W))
         sy, sx = (s0[0] - 1) / max(H - 1, 1), (s0[1] - 1) / max(W - 1, 1)
-        if self.oc2_taps is not None and int(17 * sy) + 3 <= 13 and int(17 * sx) + 3 <= 13:
+        fused = self.oc2_taps is not None and int(17 * sy) + 3 <= 13 and int(17 * sx) + 3 <= 13
+        if fused and self.oc1_low is not None and rt.lowres_oc1_rows(Bf * s0[0] * s0[1]):
+            # output_conv1 o resize o out_conv has no non-linearity inside (dpt.py:145, blocks.py:144-146): a channel mixing
+            # commutes with the resize tap by tap, so all nine taps' mixing (composed with out_conv) is ONE GEMM on the 4x
+            # map, 4x fewer flops than the conv on the 8x map, and the combine kernel interpolates and adds the tap images.
+            # path1 and ff1_v are never written. Small maps stay below (lowres_oc1_rows)
+            u = self._fusion(1, Bf, s1, None, p2, r1)
+            M1 = Bf * s1[0] * s1[1]
+            z = rt.fbuf("oc1_z", (M1, 9 * (F // 2)))
+            rt.gemm(u, self.oc1_low[0], M1, 9 * (F // 2), F, bias=self.oc1_low[1], out=z)
+            o1 = rt.fbuf("out1_f32", (Bf * s0[0] * s0[1], F // 2))
+            rt.oc1_combine(z, self.oc1[1], o1, Bf, s1[0], s1[1], s0[0], s0[1], F // 2)
+            rt.depth_tail(o1, self.oc2_taps, self.oc2[1], self.w_last, self.b_last, depth, Bf, s0[0], s0[1], F // 2, H, W, relu)
+            return depth
+        p1 = self._fusion(1, Bf, s1, s0, p2, r1)
+        if fused:
             # resize -> conv3x3 + ReLU -> conv1x1 (+ ReLU) without leaving the chip (the scale is 8/14 for every DPT head);
             # output_conv1 then writes ONE fp32 plane, which is what the fused kernel interpolates from
             o1 = self._conv3(p1, self.oc1[0], Bf, s0[0], s0[1], F, F // 2, "out1_f32", bias=self.oc1[1], f32_out=True)

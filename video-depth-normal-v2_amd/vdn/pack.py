@@ -105,6 +105,25 @@ def conv3x3_taps(w: torch.Tensor, half) -> torch.Tensor:
     return _pack(abi.PACK_CONV3X3_TAPS, w, co, ci, 0, half)
 
 
+def lowres_oc1_compose(w: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """output_conv1 moved in front of the 2x resize (DPTEngine.run): w [Co, F, 3, 3] (dpt.py:145), wo [F, F(,1,1)] / bo [F] the
+    1x1 out_conv of refinenet1 (blocks.py:146). Returns fp64 ([9 Co, F], [9 Co]): row t*Co + c = (W_t Wo)[c], bias W_t bo,
+    t = 3 ky + kx. The 3x3 conv's own bias is not in here: it is added once per output pixel by vdn_oc1_combine. Pure torch."""
+    co, f, kh, kw = w.shape
+    assert kh == 3 and kw == 3, w.shape
+    wt = w.detach().double().permute(2, 3, 0, 1).reshape(9 * co, f)       # rows (ky, kx, co)
+    wo64 = wo.detach().double().reshape(wo.shape[0], -1)
+    assert wo64.shape == (f, f), (w.shape, wo.shape)
+    return wt @ wo64, wt @ bo.detach().double()
+
+
+def lowres_oc1(w: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor, half) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The composite weight in the precision's planes ([9 Co, F], K padded as every linear) and its fp32 bias [9 Co]: composed
+    in fp64, then split like every other weight."""
+    wc, bc = lowres_oc1_compose(w, wo, bo)
+    return linear(wc.float(), half), bc.float().contiguous()
+
+
 def conv_transpose(w: torch.Tensor, b: torch.Tensor, half) -> Tuple[torch.Tensor, torch.Tensor]:
     from . import _abi as abi
     ci, co, k, k2 = w.shape

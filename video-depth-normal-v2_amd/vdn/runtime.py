@@ -421,6 +421,18 @@ class Runtime:
         self._launch(abi.lib.vdn_depth_tail, self.dt, x.data_ptr(), B, IH, IW, Cn, w.hi.data_ptr(), w.lo.data_ptr(),
                      w.hi.shape[1], bias2.data_ptr(), w1.data_ptr(), b1, depth.data_ptr(), OH, OW, int(relu))
 
+    @staticmethod
+    def lowres_oc1_rows(M: int) -> bool:
+        """Does a DPT head whose 8x map has M rows run output_conv1 at the low resolution (DPTEngine.run)? Small maps keep
+        the materialised path1."""
+        return M >= int(os.environ.get("VDN_OC1_LOWRES_MIN_ROWS", "65536"))
+
+    def oc1_combine(self, z: torch.Tensor, bias, out: torch.Tensor, B: int, IH: int, IW: int, OH: int, OW: int, Cn: int):
+        """z f32 [B*IH*IW, 9*Cn] (nine tap images per source pixel) -> out f32 [B*OH*OW, Cn] (include/vdn.h vdn_oc1_combine)."""
+        assert z.dtype == torch.float32 and z.is_contiguous() and z.numel() == B * IH * IW * 9 * Cn, (z.shape, z.dtype)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * OH * OW * Cn, (out.shape, out.dtype)
+        self._launch(abi.lib.vdn_oc1_combine, z.data_ptr(), bias.data_ptr(), out.data_ptr(), B, IH, IW, OH, OW, Cn)
+
     def head_out(self, feat, w, bias: float, depth, M: int, Cn: int, relu: bool):
         feat, fl = _hl(feat)
         self._launch(abi.lib.vdn_head_out, self.dt, feat.data_ptr(), fl, w.data_ptr(), bias, depth.data_ptr(), M, Cn,

@@ -183,6 +183,24 @@ typedef struct vdn_gemm_desc {
    * DESIGN.md §3 / profiles/r03_precision_budget.md; the engines pass 0 unless VDN_X8_TERMS says otherwise.           */
   int32_t x8_terms;
   const vdn_gemm_tuning* tuning;   /* NULL = the library defaults (vdn_gemm_get_tuning); else this launch's own knobs */
+  /* Sub-pixel convolution: Conv2d(3x3, pad 1, no bias) o ConvTranspose2d(kernel == stride == ck, bias) as ONE implicit GEMM on
+   * the LOW-resolution map (depth_anything_v2/dpt.py:129 resize_layers[0|1] followed by :135-136 layer1_rn / layer2_rn; no
+   * non-linearity in between). Output pixel (ck y + a, ck x + b) is phase (a, b) of source pixel (y, x); its 3x3 window on the
+   * ck-times map touches only the source neighbours (y + sy, x + sx) with sy in {-1, 0} for a == 0, {0, 1} for a == ck - 1,
+   * {0} otherwise (sx alike): 1, 2 or 4 neighbours per phase. subpix != 0 selects the mode:
+   *   a_mode = VDN_A_CONV3X3 on the source map (cstride 1, cOH == cH, cOW == cW, cC % 64 == 0, conv_korder 1);
+   *   store = VDN_ST_CONVT with ck in {2, 4}, cout % 256 == 0, N == ck*ck*cout, half output with out_lo (pixel-shuffle
+   *   scatter into NHWC [cB, cH*ck, cW*ck, cout] planes); split planes A_lo / W_lo required; K == ldb == 4 * cC.
+   *   W row n = (a*ck + b)*cout + co holds its phase's neighbours in the order (sy ascending, sx ascending) as
+   *   K = (ci/64, neighbour slot, ci%64), stored RAGGED: the first cC * (neighbours of the phase) elements of the row, the rest
+   *   of the row is never read. A workgroup walks only its phase's K.
+   *   subpix_bias f32 [ck*ck, 4, cout]: the transposed convolution's bias seen through the taps that land in neighbour slot s
+   *   of the phase (unused slots are not read). A neighbour outside the map drops out WHOLE, its bias share included (the
+   *   high-resolution pixels it would produce lie in the 3x3 conv's zero padding), so the bias of a row is the sum over the
+   *   slots whose neighbour is inside; `bias`, act, rowadd, gamma, tab, res1 / res2 must be unset.
+   * vdn/pack.py subpixel_conv builds both from the reference's parameters.                                                */
+  int32_t subpix;
+  const float* subpix_bias;
 } vdn_gemm_desc;
 
 int vdn_gemm(const vdn_gemm_desc* d, vdn_stream stream);

@@ -142,6 +142,23 @@ for _ in range(reps // 4):
 bad += diff
 print(f"oc1_combine B=4 148->296: {diff} of {reps // 4} runs differ", flush=True)
 del z, o, o0
+# sub-pixel convolution (ConvTranspose + layer_rn as one implicit GEMM; ragged K per phase on the ping-pong / lock-step loops)
+for Ci, k in ((256, 4), (512, 2)):
+    wsp = pack.subpixel_conv(torch.randn(Ci, Ci, k, k, device="cuda") / math.sqrt(Ci), torch.randn(Ci, device="cuda"),
+                             torch.randn(256, Ci, 3, 3, device="cuda") / math.sqrt(9 * Ci), rt.prec)
+    pm = rt.to_half(torch.randn(8 * 37 * 37, Ci, device="cuda"))
+    o = rt.hbuf(f"rs_sp{k}", (8 * 37 * 37 * k * k, 256))
+    args = dict(store=_abi.ST_CONVT, out=o, conv=dict(B=8, H=37, W=37, C=Ci, OH=37, OW=37, stride=1, korder=1),
+                convt=dict(k=k, cout=256, B=8, H=37, W=37), subpix_bias=wsp[1])
+    rt.gemm(pm, wsp[0], 8 * 37 * 37, k * k * 256, 4 * Ci, **args)
+    h0, l0 = o.hi.clone(), o.lo.clone()
+    diff = 0
+    for _ in range(reps // 4):
+        rt.gemm(pm, wsp[0], 8 * 37 * 37, k * k * 256, 4 * Ci, **args)
+        diff += int(not (torch.equal(o.hi, h0) and torch.equal(o.lo, l0)))
+    bad += diff
+    print(f"subpixel conv k={k} Ci={Ci} B=8 37x37: {diff} of {reps // 4} runs differ", flush=True)
+    del wsp, pm, o, h0, l0
 t = torch.randn(10960, 1024, device="cuda")
 g, be = torch.randn(1024, device="cuda"), torch.randn(1024, device="cuda")
 oh = rt.hbuf("rs_ln", (10960, 1024))

@@ -57,8 +57,17 @@ extern "C" int vdn_gemm(const vdn_gemm_desc* dp, vdn_stream stream) {
   if (d.dt != VDN_F16 && d.dt != VDN_BF16) return VDN_EUNSUPPORTED;
   if ((d.K & 7) || (d.ldb & 63) || d.ldb < d.K) return VDN_EALIGN;
   if (((uintptr_t)d.A & 15) || ((uintptr_t)d.W & 15) || ((uintptr_t)d.zeros & 15)) return VDN_EALIGN;
+  if (d.subpix) {  // sub-pixel convolution (include/vdn.h): only the 8-wave split-plane kernels walk a phase's tap list
+    if (d.subpix != 1 || d.a_mode != VDN_A_CONV3X3 || d.store != VDN_ST_CONVT || !d.subpix_bias || d.bias || d.act || d.rowadd ||
+        d.gamma || d.tab || d.res1 || d.res2 || d.relu_a || d.K != 4 * d.cC || d.ldb != d.K || d.conv_korder != 1 || d.cstride != 1)
+      return VDN_EINVAL;
+    if ((d.ck != 2 && d.ck != 4) || d.cout <= 0 || (d.cout & 255) || (d.cC & 63) || !d.A_lo || !d.W_lo || !d.out_lo ||
+        d.out_dt != d.dt || d.A8 || d.W8)
+      return VDN_EUNSUPPORTED;
+    if (((uintptr_t)d.subpix_bias | (uintptr_t)d.out) & 15) return VDN_EALIGN;
+  }
   if (d.a_mode == VDN_A_CONV3X3) {
-    if ((d.cC & 7) || d.K != 9 * d.cC || d.M != d.cB * d.cOH * d.cOW) return VDN_EINVAL;
+    if ((d.cC & 7) || d.K != (d.subpix ? 4 : 9) * d.cC || d.M != d.cB * d.cOH * d.cOW) return VDN_EINVAL;
     if (d.conv_korder && ((d.cC & 63) || d.conv_korder != 1)) return VDN_EINVAL;
     if (d.cstride != 1 && d.cstride != 2) return VDN_EUNSUPPORTED;
     if (d.cOH != (d.cH + 2 - 3) / d.cstride + 1 || d.cOW != (d.cW + 2 - 3) / d.cstride + 1) return VDN_EINVAL;

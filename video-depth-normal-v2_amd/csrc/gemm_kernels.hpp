@@ -7,7 +7,8 @@
 //   rows) is applied on the per-lane SOURCE address and again on the ds_read_b128 address
 //   (guide §5.4 rule 21)
 // * the A row can be a plain row-major row or an on-the-fly 3x3 (stride 1|2, pad 1) NHWC gather:
-//   the per-lane source pointer makes the DMA itself the im2col; padding taps read a zero page
+//   the per-lane source pointer makes the DMA itself the im2col; padding taps read a zero page; in the sub-pixel mode
+//   (ConvTranspose followed by a 3x3 conv, include/vdn.h: subpix) the same gather walks only the taps of the tile's phase
 // * everything the reference does around its Linear/Conv (bias, GELU/ReLU, LayerScale, pos-embed,
 //   residual adds, head split + RoPE, pixel-shuffle for ConvTranspose, GEGLU) happens on the
 //   fp32 accumulators before the single store.
@@ -66,10 +67,36 @@ __device__ __forceinline__ int conv_tap_offset(int tap, const vdn_gemm_desc& p) 
 
 // internal store codes (never in a descriptor): specialised epilogues, see emit4 / epi_flavour
 constexpr int VDN_STX_FC1 = 100, VDN_STX_RES = 101, VDN_STX_HEADS = 102, VDN_STX_HALF = 103, VDN_STX_RESHALF1 = 104,
-              VDN_STX_RESHALF2 = 105, VDN_STX_SPLITK = 106;
+              VDN_STX_RESHALF2 = 105, VDN_STX_SPLITK = 106, VDN_STX_SUBPIX = 107;
+
+// ---- sub-pixel convolution (include/vdn.h: subpix): which low-resolution taps a phase reads, and in what order its tiles run.
+// Phase (a, b) of a ck x ck pixel shuffle sees the source rows {-1, 0} (a == 0), {0, 1} (a == ck - 1) or {0}, columns alike.
+// `taps` = the 3x3 tap indices 3 (sy + 1) + (sx + 1) of its neighbour slots as 4-bit fields, slot 0 lowest, in the order
+// (sy, sx) ascending = the K order of the phase's weight rows; there are 1 << lg of them. All wave-uniform.
+__device__ __forceinline__ void subpix_taps(int phase, int ck, unsigned& taps, int& lg) {
+  const int a = phase / ck, b = phase - a * ck;
+  const int y0 = a == 0 ? 0 : 1, ny = (a == 0 || a == ck - 1) ? 2 : 1;
+  const int x0 = b == 0 ? 0 : 1, nx = (b == 0 || b == ck - 1) ? 2 : 1;
+  taps = 0;
+  int s = 0;
+  for (int yy = 0; yy < ny; ++yy)
+    for (int xx = 0; xx < nx; ++xx) taps |= (unsigned)(3 * (y0 + yy) + x0 + xx) << (4 * s++);
+  lg = (ny >> 1) + (nx >> 1);
+}
+// First output column of N tile `tn_i` (cout % 256 == 0: a 256-column tile lies inside one phase). The tiles of one M tile stay
+// adjacent (the source map is re-read from L2) and, for ck == 4, run the phases with the longest K first: the four corner
+// phases (4 neighbours), then the eight edge phases (2), then the four inner ones (1).
+__device__ __forceinline__ int subpix_tile(int tn_i, const vdn_gemm_desc& p, unsigned& taps, int& lg) {
+  const int tpp = p.cout >> 8;
+  const int rank = tn_i / tpp, sub = tn_i - rank * tpp;
+  const int phase = p.ck == 4 ? (int)((0xa965edb87421fc30ULL >> (4 * rank)) & 15) : rank;
+  subpix_taps(phase, p.ck, taps, lg);
+  return phase * p.cout + sub * 256;
+}
 
 // Which straight-line flavour (if any) computes exactly what descriptor `d` asks for.
 __host__ __device__ inline int epi_flavour(const vdn_gemm_desc& d) {
+  if (d.subpix) return VDN_STX_SUBPIX;
   const bool half_out = d.out_dt != VDN_F32;
   const bool plain_rows = d.store == VDN_ST_PLAIN && !d.rowadd && !d.gamma && !d.tab && d.row_group <= 0;
   if (plain_rows && half_out && d.out_lo && d.act != VDN_ACT_GELU) {
@@ -333,7 +360,7 @@ __device__ __forceinline__ void emit4(const vdn_gemm_desc& p, int m, int n, f32x
 // 64-column slab (instead of 16j + 4 fq + {0..3}).
 template <int STORE>
 constexpr bool vdn_pair8 = (STORE == VDN_STX_FC1 || STORE == VDN_STX_HALF || STORE == VDN_STX_RESHALF1 ||
-                            STORE == VDN_STX_RESHALF2 || STORE == VDN_STX_HEADS);
+                            STORE == VDN_STX_RESHALF2 || STORE == VDN_STX_HEADS || STORE == VDN_STX_SUBPIX);
 // W row (within a 64-row slab) held by LDS row 16 t + r under the paired mapping
 __device__ __forceinline__ int pair8_col(int t, int r) { return (t >> 1) * 32 + (r >> 2) * 8 + (t & 1) * 4 + (r & 3); }
 
@@ -464,6 +491,68 @@ __device__ __forceinline__ void epilogue_regs(f32x4 (&acc)[TM][TN], const vdn_ge
     for (int j = 0; j < TN; ++j)
       emit4<DT, STORE>(p, mw + i * 16 + fr, nw + j * 16 + fq * 4, acc[i][j], acc[i][j + 1 < TN ? j + 1 : j], bias4[j],
                        bias4[j + 1 < TN ? j + 1 : j], gam4[j]);
+}
+
+// Sub-pixel convolution epilogue (8-wave kernels, paired columns): the bias of a row is the sum of its phase's per-neighbour
+// shares over the neighbours inside the map, so it differs from row to row on the border ring only. Every share is loaded and
+// added to the accumulators BEFORE the first store (no load inside the store loop, see emit4), in slot order; then one 16-byte
+// store per plane and 8 columns at the pixel-shuffle address of VDN_ST_CONVT.
+template <int DT, int TM>
+__device__ __forceinline__ void epilogue_subpix(f32x4 (&acc)[TM][4], const vdn_gemm_desc& p, int mw, int nw, int lane) {
+  using H = Half<DT>;
+  using T = typename H::T;
+  using V8 = typename H::V8;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int phase = nw / p.cout, co0 = nw - phase * p.cout;  // wave-uniform: a wave's 64 columns lie inside one phase
+  const int ky = phase / p.ck, kx = phase - ky * p.ck;
+  unsigned taps;
+  int lg;
+  subpix_taps(phase, p.ck, taps, lg);
+  const int hw = p.cH * p.cW;
+  int cy[TM], cx[TM];
+  size_t ob[TM];
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    int m = mw + i * 16 + fr;
+    m = m < p.M ? m : p.M - 1;
+    const int cb = m / hw, rem = m - cb * hw;
+    cy[i] = rem / p.cW;
+    cx[i] = rem - cy[i] * p.cW;
+    ob[i] = ((((size_t)cb * (p.cH * p.ck) + cy[i] * p.ck + ky) * (p.cW * p.ck)) + cx[i] * p.ck + kx) * p.cout + co0 + fq * 8;
+  }
+  for (int s = 0; s < (1 << lg); ++s) {
+    const int tap = (taps >> (4 * s)) & 15;
+    const int sy = ((tap * 11) >> 5) - 1, sx = tap - (sy + 1) * 3 - 1;
+    const float* bs = p.subpix_bias + (size_t)(phase * 4 + s) * p.cout + co0 + fq * 8;
+    f32x4 b4[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b4[j] = *(const f32x4*)(bs + (j >> 1) * 32 + (j & 1) * 4);
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int y = cy[i] + sy, x = cx[i] + sx;
+      const float in = ((y >= 0) & (y < p.cH) & (x >= 0) & (x < p.cW)) ? 1.f : 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] += b4[j] * in;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    if (mw + i * 16 + fr >= p.M) continue;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      V8 h, l;
+#pragma unroll
+      for (int e = 0; e < 4; e += 2) {
+        T h0, h1, l0, l1;
+        split2_rtz(acc[i][2 * u][e], acc[i][2 * u][e + 1], h0, h1, l0, l1);
+        h[e] = h0; h[e + 1] = h1; l[e] = l0; l[e + 1] = l1;
+        split2_rtz(acc[i][2 * u + 1][e], acc[i][2 * u + 1][e + 1], h0, h1, l0, l1);
+        h[4 + e] = h0; h[5 + e] = h1; l[4 + e] = l0; l[5 + e] = l1;
+      }
+      *(V8*)((T*)p.out + ob[i] + u * 32) = h;
+      *(V8*)((T*)p.out_lo + ob[i] + u * 32) = l;
+    }
+  }
 }
 
 template <int DT, int TM, int TN>
@@ -863,8 +952,11 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
     tn_i = r / gm;
     tm_i = g * GM + (r - tn_i * gm);
   }
-  const int m0 = tm_i * BM, n0 = tn_i * BN;
-  const int nk_total = (AMODE == 1 || AMODE == 2) ? p.ldb / BK3 : p.K / BK3;
+  constexpr bool SUBPIX = STORE == VDN_STX_SUBPIX;  // sub-pixel convolution: the K loop walks the tap list of this tile's phase
+  unsigned sp_taps = 0;
+  int sp_lg = 0;
+  const int m0 = tm_i * BM, n0 = SUBPIX ? subpix_tile(tn_i, p, sp_taps, sp_lg) : tn_i * BN;
+  const int nk_total = SUBPIX ? (p.cC >> 6) << (sp_lg + 1) : (AMODE == 1 || AMODE == 2) ? p.ldb / BK3 : p.K / BK3;
   const int nk_slice = (STORE == VDN_STX_SPLITK) ? (nk_total + p.ksplit - 1) / p.ksplit : nk_total;
   const int kt0 = slice * nk_slice;
 
@@ -921,8 +1013,14 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
       int tap;
       if (p.conv_korder) {  // (ci/64, tap, half, ci%32): scalar decode, same for every lane of the step
         const int half = kt & 1, t2 = kt >> 1;
-        const int c64 = t2 / 9;
-        tap = t2 - c64 * 9;
+        int c64;
+        if constexpr (SUBPIX) {
+          c64 = t2 >> sp_lg;
+          tap = (sp_taps >> (4 * (t2 & ((1 << sp_lg) - 1)))) & 15;
+        } else {
+          c64 = t2 / 9;
+          tap = t2 - c64 * 9;
+        }
         ci = c64 * 64 + half * 32 + chunk * 8;
         if (ci >= p.cC) tap = 9;
       } else {
@@ -1136,6 +1234,8 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
     q.out = (float*)p.splitk_ws + (size_t)slice * p.M * p.N;
     q.ldc = p.N;
     epilogue_regs<DT, TMW, TNW, STORE, false>(acc, q, m0 + wm * (BM / 2), n0 + wn * 64, lane);
+  } else if constexpr (SUBPIX) {
+    epilogue_subpix<DT, TMW>(acc, p, m0 + wm * (BM / 2), n0 + wn * 64, lane);
   } else {
     epilogue_regs<DT, TMW, TNW, STORE, vdn_pair8<STORE>>(acc, p, m0 + wm * (BM / 2), n0 + wn * 64, lane);
   }
@@ -1213,7 +1313,10 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
     tn_i = r / gm;
     tm_i = g * GM + (r - tn_i * gm);
   }
-  const int m0 = tm_i * BM, n0 = tn_i * BN;
+  constexpr bool SUBPIX = STORE == VDN_STX_SUBPIX;  // sub-pixel convolution: the K loop walks the tap list of this tile's phase
+  unsigned sp_taps = 0;
+  int sp_lg = 0;
+  const int m0 = tm_i * BM, n0 = SUBPIX ? subpix_tile(tn_i, p, sp_taps, sp_lg) : tn_i * BN;
   const int wm = wave >> 2, wn = wave & 3;
 
   const int kt0s = SPLITK ? slice * ((((AMODE == 1 || AMODE == 2) ? p.ldb / BK3 : p.K / BK3) + p.ksplit - 1) / p.ksplit) : 0;
@@ -1293,7 +1396,14 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
           // add remain (the general path below costs ~25 VALU per piece and made the conv K step 40 %
           // slower than the plain GEMM's)
           const int half = kt & 1, t2 = kt >> 1;
-          const int c64 = t2 / 9, tap = t2 - c64 * 9;  // scalar
+          int c64, tap;  // scalar
+          if constexpr (SUBPIX) {
+            c64 = t2 >> sp_lg;
+            tap = (sp_taps >> (4 * (t2 & ((1 << sp_lg) - 1)))) & 15;
+          } else {
+            c64 = t2 / 9;
+            tap = t2 - c64 * 9;
+          }
           const int ky = (tap * 11) >> 5, kx = tap - ky * 3;
           const int off = ((ky - 1) * p.cW + (kx - 1)) * p.cC + c64 * 64 + half * 32;  // scalar, elements
           ok = (tap_ok[i] >> tap) & 1;
@@ -1352,7 +1462,7 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nk_total = CONV ? p.ldb / BK3 : p.K / BK3;
+  const int nk_total = SUBPIX ? (p.cC >> 6) << (sp_lg + 1) : CONV ? p.ldb / BK3 : p.K / BK3;
   const int nk_slice = SPLITK ? (nk_total + p.ksplit - 1) / p.ksplit : nk_total;
   const int kt0 = slice * nk_slice;
   const int nk = (nk_total - kt0) < nk_slice ? (nk_total - kt0) : nk_slice;
@@ -1444,6 +1554,8 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
     q.out = (float*)p.splitk_ws + (size_t)slice * p.M * p.N;
     q.ldc = p.N;
     epilogue_regs<DT, 2 * TQ, 4, STORE, false>(acc, q, m0 + wm * (BM / 2), n0 + wn * 64, lane);
+  } else if constexpr (SUBPIX) {
+    epilogue_subpix<DT, 2 * TQ>(acc, p, m0 + wm * (BM / 2), n0 + wn * 64, lane);
   } else {
     epilogue_regs<DT, 2 * TQ, 4, STORE, vdn_pair8<STORE>>(acc, p, m0 + wm * (BM / 2), n0 + wn * 64, lane);
   }
@@ -1504,9 +1616,9 @@ int launch_x3_big(const vdn_gemm_desc& d, hipStream_t s) {
   // plane-output flavours store 8 columns (16 bytes) per lane: rows and column counts must keep that aligned
   const bool a8 = !(d.N & 7) && !(d.ldc & 7) && !((uintptr_t)d.out & 15) && !((uintptr_t)d.out_lo & 15) && !(d.ldr1 & 7) &&
                   !(d.ldr2 & 7) && !(((uintptr_t)d.res1 | (uintptr_t)d.res1_lo | (uintptr_t)d.res2 | (uintptr_t)d.res2_lo) & 15);
-  if (!a8 && fl != VDN_STX_RES && fl != VDN_STX_HEADS) fl = d.store;
+  if (!a8 && fl != VDN_STX_RES && fl != VDN_STX_HEADS && fl != VDN_STX_SUBPIX) fl = d.store;  // (sub-pixel: validated by vdn_gemm)
   if (d.a_mode == VDN_A_CONV3X3) {
-    if (fl != VDN_STX_HALF && fl != VDN_STX_RESHALF1 && fl != VDN_STX_RESHALF2) fl = VDN_ST_PLAIN;
+    if (fl != VDN_STX_HALF && fl != VDN_STX_RESHALF1 && fl != VDN_STX_RESHALF2 && fl != VDN_STX_SUBPIX) fl = VDN_ST_PLAIN;
   } else if (fl == VDN_STX_RESHALF1 || fl == VDN_STX_RESHALF2) {
     fl = d.store;
   }
@@ -1523,6 +1635,7 @@ int launch_x3_big(const vdn_gemm_desc& d, hipStream_t s) {
           case VDN_STX_HALF: VDN_CONV_P8(VDN_STX_HALF); break;
           case VDN_STX_RESHALF1: VDN_CONV_P8(VDN_STX_RESHALF1); break;
           case VDN_STX_RESHALF2: VDN_CONV_P8(VDN_STX_RESHALF2); break;
+          case VDN_STX_SUBPIX: VDN_LAUNCH_P8(1, VDN_STX_SUBPIX); break;
           default: VDN_CONV_P8(VDN_ST_PLAIN); break;
         }
 #undef VDN_CONV_P8
@@ -1549,6 +1662,7 @@ int launch_x3_big(const vdn_gemm_desc& d, hipStream_t s) {
       case VDN_STX_HALF: VDN_CONV_BIG(VDN_STX_HALF); break;
       case VDN_STX_RESHALF1: VDN_CONV_BIG(VDN_STX_RESHALF1); break;
       case VDN_STX_RESHALF2: VDN_CONV_BIG(VDN_STX_RESHALF2); break;
+      case VDN_STX_SUBPIX: VDN_LAUNCH_BIG(1, VDN_STX_SUBPIX); break;
       default: VDN_CONV_BIG(VDN_ST_PLAIN); break;
     }
 #undef VDN_CONV_BIG
@@ -1639,6 +1753,11 @@ int launch_dt(const vdn_gemm_desc& d, hipStream_t s) {
       // only that kernel reads K-tile-major planes and writes out8 / a lo-less half output
       if (d.a_kt || d.w_kt || d.out_kt || d.out8 || !d.A_lo || !d.W_lo) return VDN_EUNSUPPORTED;
     }
+  }
+  // sub-pixel convolution: the 8-wave kernels only, whatever the size (vdn_gemm validated the shape)
+  if (d.subpix) {
+    const vdn_gemm_tuning& tu = tuning(d);
+    return big_entry<DT>(d, tu.force_bm ? tu.force_bm : pick_bm(d.M, d.N, d.cu_hint, tu), s);
   }
   // 8-wave kernels: large problems, and small ones whose deep reduction makes them split-K candidates
   const bool deep = d.splitk_ws && (d.a_mode == VDN_A_CONV3X3 ? d.ldb : d.K) >= 2048 && (long)d.M * d.N >= 32L * 1024;

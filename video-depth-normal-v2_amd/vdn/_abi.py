@@ -40,6 +40,7 @@ class GemmDesc(C.Structure):
         ("A8", vp), ("W8", vp), ("out8", vp),
         ("a_kt", i32), ("w_kt", i32), ("out_kt", i32), ("x8_terms", i32),
         ("tuning", vp),
+        ("subpix", i32), ("subpix_bias", fp),
     ]
 
 

@@ -373,6 +373,15 @@ class DPTEngine:
         if fused and (features // 2) % 16 == 0 and not os.environ.get("VDN_OC1_HIRES"):
             f1 = s.refinenet1.out_conv
             self.oc1_low = pack.lowres_oc1(s.output_conv1.weight, f1.weight, f1.bias, h)
+        # layer{1,2}_rn folded into the ConvTranspose in front of them (run()): one sub-pixel convolution on the source map per
+        # level, composed once per checkpoint. On wherever the kernel mode takes the widths (pack.subpixel_conv_ok; ViT-L);
+        # VDN_RN_HIRES forces the materialised 4x / 2x maps (A/B switch)
+        self.rn_low = [None, None]
+        if not os.environ.get("VDN_RN_HIRES"):
+            for i, k in enumerate((4, 2)):
+                if pack.subpixel_conv_ok(self.oc[i], features, k, h):
+                    rl = mod.resize_layers[i]
+                    self.rn_low[i] = pack.subpixel_conv(rl.weight, rl.bias, getattr(s, f"layer{i + 1}_rn").weight, h)
         self.w_last = pack.f32(s.output_conv2[2].weight).reshape(-1)
         self.b_last = float(s.output_conv2[2].bias.detach().float().item())
         self.temporal = None
@@ -428,12 +437,23 @@ class DPTEngine:
             pr.append(o)
         s1, s2, s3 = (4 * ph, 4 * pw), (2 * ph, 2 * pw), (ph, pw)
         s4 = ((ph + 2 - 3) // 2 + 1, (pw + 2 - 3) // 2 + 1)
-        l1 = rt.hbuf("l1", (Bf * s1[0] * s1[1], oc[0]))
-        rt.gemm(pr[0], self.rt0[0], Bf * P, 16 * oc[0], oc[0], bias=self.rt0[1], store=abi.ST_CONVT, out=l1,
-                convt=dict(k=4, cout=oc[0], B=Bf, H=ph, W=pw))
-        l2 = rt.hbuf("l2", (Bf * s2[0] * s2[1], oc[1]))
-        rt.gemm(pr[1], self.rt1[0], Bf * P, 4 * oc[1], oc[1], bias=self.rt1[1], store=abi.ST_CONVT, out=l2,
-                convt=dict(k=2, cout=oc[1], B=Bf, H=ph, W=pw))
+
+        def level(i, k, size, wT, name):
+            """resize_layers[i] (ConvTranspose k = s) then layer{i+1}_rn (3x3): as ONE sub-pixel convolution on the ph x pw map
+            where the kernel takes the widths (no non-linearity in between: every output phase is a short 3x3-neighbourhood
+            sum of the projected map; the k-times map is never written), else as written."""
+            if self.rn_low[i] is not None:
+                r = rt.hbuf(name + "_rn", (Bf * size[0] * size[1], F))
+                return rt.gemm(pr[i], self.rn_low[i][0], Bf * P, k * k * F, 4 * oc[i], store=abi.ST_CONVT, out=r,
+                               conv=dict(B=Bf, H=ph, W=pw, C=oc[i], OH=ph, OW=pw, stride=1, korder=1),
+                               convt=dict(k=k, cout=F, B=Bf, H=ph, W=pw), subpix_bias=self.rn_low[i][1])
+            l = rt.hbuf(name, (Bf * size[0] * size[1], oc[i]))
+            rt.gemm(pr[i], wT[0], Bf * P, k * k * oc[i], oc[i], bias=wT[1], store=abi.ST_CONVT, out=l,
+                    convt=dict(k=k, cout=oc[i], B=Bf, H=ph, W=pw))
+            return self._conv3(l, self.rn[i], Bf, size[0], size[1], oc[i], F, name + "_rn")
+
+        r1 = level(0, 4, s1, self.rt0, "l1")
+        r2 = level(1, 2, s2, self.rt1, "l2")
         l3 = pr[2]
         l4 = self._conv3(pr[3], self.rs3[0], Bf, ph, pw, oc[3], oc[3], "l4", stride=2, bias=self.rs3[1])
         def tm(i, x, hw):
@@ -446,8 +466,6 @@ class DPTEngine:
         if self.temporal is not None:
             l3 = tm(0, l3, s3[0] * s3[1])
             l4 = tm(1, l4, s4[0] * s4[1])
-        r1 = self._conv3(l1, self.rn[0], Bf, s1[0], s1[1], oc[0], F, "l1_rn")
-        r2 = self._conv3(l2, self.rn[1], Bf, s2[0], s2[1], oc[1], F, "l2_rn")
         r3 = self._conv3(l3, self.rn[2], Bf, s3[0], s3[1], oc[2], F, "l3_rn")
         r4 = self._conv3(l4, self.rn[3], Bf, s4[0], s4[1], oc[3], F, "l4_rn")
         p4 = self._fusion(4, Bf, s4, s3, r4)

@@ -6,6 +6,7 @@ All GEMM weights become half [N, ldb] with K contiguous and zero padded to a mul
   conv1x1   [Co,Ci,1,1]           -> [Co, Ci]
   conv3x3   [Co,Ci,3,3]           -> [Co, (ky,kx,ci)]      (matches the NHWC gather order)
   convT k=s [Ci,Co,k,k]           -> [(ky,kx,co), ci]      (pixel-shuffle epilogue order)
+  subpixel  convT [Ci,Cm,k,k] then conv3x3 [Co,Cm,3,3] -> [(phase,co), (ci/64, neighbour slot, ci%64)] ragged (subpixel_conv)
   patch     [C,3,14,14]           -> [C, (c,ky,kx)] padded 588 -> 640
   GEGLU     [8c,c] = [h ; gate]   -> 16-row blocks alternating h / gate
   RoPE q/k  rows of each head (2i, 2i+1) -> [re 0-15 | im 0-15 | re 16-31 | im 16-31]
@@ -122,6 +123,60 @@ def lowres_oc1(w: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor, half) -> Tup
     in fp64, then split like every other weight."""
     wc, bc = lowres_oc1_compose(w, wo, bo)
     return linear(wc.float(), half), bc.float().contiguous()
+
+
+def subpixel_neighbours(k: int, a: int) -> Tuple[int, ...]:
+    """Source-pixel offsets a 3-tap window centred on sub-pixel phase `a` of a k-times (k >= 2) pixel shuffle reaches:
+    floor((a + d) / k) for d in -1, 0, 1."""
+    assert k >= 2 and 0 <= a < k, (k, a)
+    return (-1, 0) if a == 0 else ((0, 1) if a == k - 1 else (0,))
+
+
+def subpixel_conv_compose(wt: torch.Tensor, bt: torch.Tensor, wr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, list]:
+    """Conv2d(3x3, pad 1, no bias) after ConvTranspose2d(kernel == stride == k) as one 3x3-neighbourhood map on the source
+    grid (DPTEngine.run; dpt.py:129 then :135-136). wt [Ci, Cm, k, k], bt [Cm] the transposed convolution, wr [Co, Cm, 3, 3].
+    Output pixel (k y + a, k x + b) = sum over the neighbours (sy, sx) of its phase that lie inside the map of
+    Wc[phase, slot] @ p[y + sy, x + sx] + beta[phase, slot]: a neighbour outside the map drops out whole, its bias share too.
+    Returns fp64 (Wc [k*k, 4, Co, Ci], beta [k*k, 4, Co], slots): phase = a*k + b; slots[phase] = the (sy, sx) of its neighbour
+    slots, sy ascending then sx ascending (1, 2 or 4 of them; the unused slots of Wc / beta are zero). Pure torch."""
+    ci, cm, k, k2 = wt.shape
+    co = wr.shape[0]
+    assert k == k2 and k >= 2 and wr.shape[1:] == (cm, 3, 3) and bt.shape == (cm,), (wt.shape, bt.shape, wr.shape)
+    wt64, bt64, wr64 = wt.detach().double(), bt.detach().double(), wr.detach().double()
+    wc = torch.zeros((k * k, 4, co, ci), dtype=torch.float64, device=wt.device)
+    beta = torch.zeros((k * k, 4, co), dtype=torch.float64, device=wt.device)
+    slots = []
+    for a in range(k):
+        for b in range(k):
+            sl = [(sy, sx) for sy in subpixel_neighbours(k, a) for sx in subpixel_neighbours(k, b)]
+            slots.append(sl)
+            for dy in range(3):
+                for dx in range(3):
+                    ya, xb = a + dy - 1, b + dx - 1
+                    s = sl.index((ya // k, xb // k))
+                    wc[a * k + b, s] += wr64[:, :, dy, dx] @ wt64[:, :, ya % k, xb % k].t()
+                    beta[a * k + b, s] += wr64[:, :, dy, dx] @ bt64
+    return wc, beta, slots
+
+
+def subpixel_conv_ok(ci: int, co: int, k: int, half) -> bool:
+    """Does vdn_gemm's sub-pixel mode (include/vdn.h: subpix) take this layer pair? Split planes, 64-channel input blocks, and
+    phases that are whole 256-column tiles (an N tile must lie inside one phase: its K loop walks that phase's tap list)."""
+    return _prec(half).split and k in (2, 4) and ci % 64 == 0 and co % 256 == 0
+
+
+def subpixel_conv(wt: torch.Tensor, bt: torch.Tensor, wr: torch.Tensor, half) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The composite in the planes vdn_gemm's sub-pixel mode reads: rows (phase, co); a row holds its phase's n neighbour
+    slots as K = (ci/64, slot, ci%64) in its first n*Ci columns, zeros up to 4*Ci (never read); and the fp32 bias shares
+    [k*k, 4, Co]. Composed in fp64, then split like every other weight."""
+    wc, beta, slots = subpixel_conv_compose(wt, bt, wr)
+    kk, _, co, ci = wc.shape
+    assert ci % 64 == 0, ci
+    rows = torch.zeros((kk, co, 4 * ci), dtype=torch.float64, device=wc.device)
+    for ph, sl in enumerate(slots):
+        n = len(sl)
+        rows[ph, :, :n * ci] = wc[ph, :n].reshape(n, co, ci // 64, 64).permute(1, 2, 0, 3).reshape(co, n * ci)
+    return linear(rows.reshape(kk * co, 4 * ci).float(), half), beta.float().contiguous()
 
 
 def conv_transpose(w: torch.Tensor, b: torch.Tensor, half) -> Tuple[torch.Tensor, torch.Tensor]:

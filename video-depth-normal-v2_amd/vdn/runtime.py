@@ -196,10 +196,13 @@ class Runtime:
              conv: Optional[dict] = None, relu_a: bool = False, store: int = abi.ST_PLAIN, row_group: int = 0,
              row_skip: int = 0, heads: Optional[dict] = None, convt: Optional[dict] = None, tag: Optional[str] = None,
              a8: Optional[torch.Tensor] = None, w8: Optional[torch.Tensor] = None, out8: Optional[torch.Tensor] = None,
-             a_kt: bool = False, w_kt: bool = False, out_kt: bool = False, x8_terms: int = 0):
+             a_kt: bool = False, w_kt: bool = False, out_kt: bool = False, x8_terms: int = 0,
+             subpix_bias: Optional[torch.Tensor] = None):
         """A, W and out may be operand objects: a pack.Linear weight follows its activation, on the cross-term kernel for a KT
         (a8 / w8 / a_kt / w_kt filled from the two), else on its split planes, where x8_terms does not apply; a KT `out`
-        fills out8 / out_kt. The keywords give the same planes by hand (tests and tools)."""
+        fills out8 / out_kt. The keywords give the same planes by hand (tests and tools). subpix_bias (with conv= on the
+        source map, convt= and store=ST_CONVT; W and the bias shares from pack.subpixel_conv, K = 4 C): the sub-pixel
+        convolution mode of include/vdn.h."""
         if isinstance(W, Linear):
             if not isinstance(A, KT):
                 W, x8_terms = W.hl, 0
@@ -274,6 +277,9 @@ class Runtime:
             d.out8 = out8.data_ptr()
         d.a_kt, d.w_kt, d.out_kt = int(a_kt), int(w_kt), int(out_kt)   # K-tile-major planes (include/vdn.h)
         d.x8_terms = int(x8_terms)
+        if subpix_bias is not None:
+            assert subpix_bias.dtype == torch.float32 and subpix_bias.is_contiguous() and subpix_bias.numel() == 4 * N, subpix_bias.shape
+            d.subpix, d.subpix_bias = 1, subpix_bias.data_ptr()
         d.cu_hint = self.cu_hint
         if abi.OVERRIDE is not None:   # per-launch kernel-selection knobs (tests / tools); the library itself is stateless
             d.tuning = C.addressof(abi.OVERRIDE)

@@ -13,6 +13,12 @@
 //   residual adds, head split + RoPE, pixel-shuffle for ConvTranspose, GEGLU) happens on the
 //   fp32 accumulators before the single store.
 //
+// Layout of this file: the pieces every main loop shares (glds16, tile_mn, frag_off64 / frag_off128, mma3, KStep /
+// kstep_decode, APiece), the fused epilogues (emit4 / emit8, epilogue_regs, epilogue_subpix, epilogue_x3), the four main
+// loops — gemm_kernel (one product per K segment), gemm_x3_kernel (128 x 128, lock-step), gemm_x3_big_kernel (BM x 256,
+// lock-step or phase-shifted), gemm_x3_p8_kernel (ping-pong); the fifth, gemm_x8_kernel, is in gemm_x8.hip — which differ
+// in their schedule only, and the launchers (with_amode / with_flavour turn the run-time choice into template arguments).
+//
 // Roofline: MFMA-bound (>= 170 flop per HBM byte on every shape of the path).
 #pragma once
 #include "common.hpp"
@@ -28,6 +34,122 @@ const vdn_gemm_tuning& tuning(const vdn_gemm_desc& d);  // gemm.hip
 constexpr int BK = 64;
 
 // ---------------------------------------------------------------------------------------------
+// Pieces every main loop shares. The kernels differ in their schedule only (lock-step, phase-shifted, ping-pong); the
+// DMA wrapper, tile order, fragment offsets, three-product block, A-row gather and K-step decode are written once here.
+
+// LDS-DMA of 16 bytes per lane (global_load_lds_dwordx4): 1 KiB per wave-instruction, lane-linear in LDS
+__device__ __forceinline__ void glds16(const void* src, void* dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst,
+                                   16, 0, 0);
+}
+
+// Tile order inside an XCD's run (8-wave kernels): groups of 4 m-tiles walk n first, so that the ~32 tiles an
+// XCD has in flight share A rows 8-fold and W columns 4-fold through its L2
+__device__ __forceinline__ void tile_mn(int tile, int tiles_m, int tiles_n, int& tm_i, int& tn_i) {
+  constexpr int GM = 4;
+  const int per_group = GM * tiles_n;
+  const int g = tile / per_group, r = tile - g * per_group;
+  const int gm = (tiles_m - g * GM) < GM ? (tiles_m - g * GM) : GM;
+  tn_i = r / gm;
+  tm_i = g * GM + (r - tn_i * gm);
+}
+
+// ds_read_b128 offset of 16-byte chunk `c` of LDS row `row` under the bank-conflict swizzle: 64-byte rows (BK = 32,
+// the split-plane kernels; c = lane >> 4; `base` = the plane's offset in the stage) and 128-byte rows (BK = 64,
+// gemm_kernel; c = 4 kk + (lane >> 4))
+__device__ __forceinline__ int frag_off64(int row, int c, int base = 0) { return base + row * 64 + ((c ^ ((0 - (row >> 2)) & 3)) << 4); }
+__device__ __forceinline__ int frag_off128(int row, int c) { return row * 128 + ((c ^ ((row >> 1) & 7)) << 4); }
+
+// hi*lo + lo*hi + hi*hi of one 16 x 16 x 32 block, smallest products first (weights are the MFMA's first operand)
+template <typename H>
+__device__ __forceinline__ f32x4 mma3(typename H::V8 bh, typename H::V8 bl, typename H::V8 ah, typename H::V8 al, f32x4 c) {
+  c = H::mfma16(bh, al, c);
+  c = H::mfma16(bl, ah, c);
+  return H::mfma16(bh, ah, c);
+}
+
+// One K step of BKS (64 | 32) columns, decoded once per wave: kt, the descriptor and the tile's sub-pixel tap list are
+// wave-uniform, so all of this is scalar work.
+struct KStep {
+  int k0;   // first K column of the step (plain rows, general conv order)
+  int tap;  // fast conv order: the 3x3 tap of the step; 9 = past the last channel block, every lane reads zeros
+  int off;  // fast conv order: element offset from the centre tap (tap + channel block)
+};
+// Fast conv order (ci/64, tap, [half,] ci % BKS), include/vdn.h conv_korder 1: the step fixes one tap and one channel block
+// for every lane. SUBPIX: the step walks the 1 << sp_lg taps of the tile's phase (subpix_taps) instead of all nine.
+template <int BKS, bool SUBPIX = false>
+__device__ __forceinline__ KStep kstep_decode(int kt, const vdn_gemm_desc& p, unsigned sp_taps = 0, int sp_lg = 0) {
+  static_assert(BKS == 32 || BKS == 64, "one or two steps per 64-channel block");
+  KStep s = {kt * BKS, 9, 0};
+  if (p.conv_korder) {
+    const int t2 = BKS == 32 ? kt >> 1 : kt, half = BKS == 32 ? kt & 1 : 0;
+    int c64;
+    if constexpr (SUBPIX) {
+      c64 = t2 >> sp_lg;
+      s.tap = (sp_taps >> (4 * (t2 & ((1 << sp_lg) - 1)))) & 15;
+    } else {
+      c64 = t2 / 9;
+      s.tap = t2 - c64 * 9;
+    }
+    if (c64 * 64 >= p.cC) s.tap = 9;
+    const int ky = (s.tap * 11) >> 5, kx = s.tap - ky * 3;
+    s.off = ((ky - 1) * p.cW + (kx - 1)) * p.cC + c64 * 64 + half * 32;
+  }
+  return s;
+}
+
+// Where one lane's 16-byte chunk of a DMA piece of A comes from: a plain row-major row, or the on-the-fly 3x3 (stride
+// 1 | 2, pad 1) NHWC gather. Set up once per piece; src() then gives the address for a K step.
+// Fast conv order: a pointer to the centre tap (plus this lane's chunk) and a 9-bit "tap lies inside the image" mask are
+// computed once; a K step then costs the wave-uniform KStep, one bit test and one 64-bit add per piece instead of the
+// ~25 VALU of index math of the general (tap, ci) order (which made the conv K step 40 % slower than the plain GEMM's).
+template <typename T, bool CONV>
+struct APiece {
+  const T* base;     // plain: the row; conv: the image
+  int iy0, ix0;      // conv: input position of tap (0, 0)
+  const T* center;   // conv: centre tap + chunk
+  unsigned ok9;      // conv: bit t = tap t lies inside the image
+  __device__ __forceinline__ void setup(int m, int chunk_elems, const vdn_gemm_desc& p) {
+    m = m < p.M ? m : p.M - 1;
+    if constexpr (CONV) {
+      const int hw = p.cOH * p.cOW;
+      const int b = m / hw, rem = m - b * hw;
+      const int oy = rem / p.cOW, ox = rem - oy * p.cOW;
+      base = (const T*)p.A + (size_t)b * p.cH * p.cW * p.cC;
+      iy0 = oy * p.cstride - 1;
+      ix0 = ox * p.cstride - 1;
+      center = base + ((ptrdiff_t)(iy0 + 1) * p.cW + (ix0 + 1)) * p.cC + chunk_elems;
+      ok9 = 0;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int iy = iy0 + t / 3, ix = ix0 + t % 3;
+        ok9 |= (unsigned)((iy >= 0) & (iy < p.cH) & (ix >= 0) & (ix < p.cW)) << t;
+      }
+    } else {
+      base = (const T*)p.A + (size_t)m * p.lda;
+    }
+  }
+  // hi-plane source of the chunk for step `ks`; !ok: padding tap or K tail, the lane reads the zero page instead
+  __device__ __forceinline__ const char* src(const KStep& ks, int chunk_elems, const vdn_gemm_desc& p, bool& ok) const {
+    const int k = ks.k0 + chunk_elems;
+    if constexpr (!CONV) {
+      ok = k < p.K;
+      return (const char*)(base + k);
+    } else if (p.conv_korder) {
+      ok = (ok9 >> ks.tap) & 1;
+      return (const char*)(center + ks.off);
+    } else {  // (tap, ci) of this lane's chunk; Cin % 8 == 0 so a chunk never straddles two taps
+      const int tap = (int)(((float)(k >> 3) + 0.5f) * (1.0f / (float)(p.cC >> 3)));
+      const int ci = k - tap * p.cC;
+      const int ky = tap / 3, kx = tap - ky * 3;
+      const int iy = iy0 + ky, ix = ix0 + kx;
+      ok = (tap < 9) & (iy >= 0) & (iy < p.cH) & (ix >= 0) & (ix < p.cW);
+      return (const char*)(base + ((size_t)iy * p.cW + ix) * p.cC + ci);
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------------------------
 // Fused fp32 epilogue. The MFMAs are issued with the WEIGHT fragment as the A operand and the
 // activation fragment as B, so an accumulator tile is C^T:
 //   acc[i][j][e]  ->  C[m = mw + 16 i + (lane & 15)][n = nw + 16 j + 4 (lane >> 4) + e]
@@ -40,30 +162,6 @@ constexpr int BK = 64;
 // LayerScale factor, loaded ONCE per wave before the first store (0 / 0 / 1 when the operand is absent): a
 // load inside the store loop waits on vmcnt, which on gfx9 also counts the stores issued before it, so
 // every group paid a full store round trip (measured: 10 us of "math" per tile round that was latency).
-// Implicit-GEMM 3x3 gather, fast path for the (ci/64, tap, ...) K order: per 16-row piece a pointer to the centre
-// tap (plus this lane's 16-byte chunk) and a 9-bit "tap lies inside the image" mask are computed once; a K step
-// then costs a wave-uniform offset, one bit test and one 64-bit add per piece instead of ~25 VALU of index math.
-struct ConvTap {
-  const void* center;
-  unsigned ok9;
-};
-template <typename T>
-__device__ __forceinline__ ConvTap conv_tap_setup(const T* image, int iy0, int ix0, int chunk_elems, const vdn_gemm_desc& p) {
-  ConvTap c;
-  c.center = image + ((ptrdiff_t)(iy0 + 1) * p.cW + (ix0 + 1)) * p.cC + chunk_elems;
-  c.ok9 = 0;
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int iy = iy0 + t / 3, ix = ix0 + t % 3;
-    c.ok9 |= (unsigned)((iy >= 0) & (iy < p.cH) & (ix >= 0) & (ix < p.cW)) << t;
-  }
-  return c;
-}
-// element offset of tap `tap` (0..8, wave-uniform) relative to the centre
-__device__ __forceinline__ int conv_tap_offset(int tap, const vdn_gemm_desc& p) {
-  const int ky = (tap * 11) >> 5, kx = tap - ky * 3;
-  return ((ky - 1) * p.cW + (kx - 1)) * p.cC;
-}
 
 // internal store codes (never in a descriptor): specialised epilogues, see emit4 / epi_flavour
 constexpr int VDN_STX_FC1 = 100, VDN_STX_RES = 101, VDN_STX_HEADS = 102, VDN_STX_HALF = 103, VDN_STX_RESHALF1 = 104,
@@ -555,6 +653,22 @@ __device__ __forceinline__ void epilogue_subpix(f32x4 (&acc)[TM][4], const vdn_g
   }
 }
 
+// Epilogue of the 8-wave split-plane kernels (64-column wave slabs), by the kernel's compile-time flavour: the raw partial
+// sums of split-K slice `slice`, the sub-pixel scatter, or a register epilogue (paired columns for the plane outputs).
+template <int DT, int TM, int STORE>
+__device__ __forceinline__ void epilogue_x3(f32x4 (&acc)[TM][4], const vdn_gemm_desc& p, int slice, int mw, int nw, int lane) {
+  if constexpr (STORE == VDN_STX_SPLITK) {
+    vdn_gemm_desc q = p;
+    q.out = (float*)p.splitk_ws + (size_t)slice * p.M * p.N;
+    q.ldc = p.N;
+    epilogue_regs<DT, TM, 4, STORE, false>(acc, q, mw, nw, lane);
+  } else if constexpr (STORE == VDN_STX_SUBPIX) {
+    epilogue_subpix<DT, TM>(acc, p, mw, nw, lane);
+  } else {
+    epilogue_regs<DT, TM, 4, STORE, vdn_pair8<STORE>>(acc, p, mw, nw, lane);
+  }
+}
+
 template <int DT, int TM, int TN>
 __device__ __forceinline__ void epilogue_dispatch(f32x4 (&acc)[TM][TN], const vdn_gemm_desc& p, int mw, int nw, int lane) {
   switch (epi_flavour(p)) {
@@ -592,25 +706,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vdn_gemm_desc p) {
   // ---- staging geometry (fixed per lane over the whole K loop)
   const int lr = lane >> 3;                                   // row inside an 8-row DMA piece
   const int chunk = (lane & 7) ^ ((((wave & 1) << 2) + (lr >> 1)) & 7);  // source 16-B chunk
-  const T* a_row[A_IT];
-  int a_iy[A_IT], a_ix[A_IT];
-  const T* A = (const T*)p.A;
+  APiece<T, CONV> a_pc[A_IT];
 #pragma unroll
-  for (int i = 0; i < A_IT; ++i) {
-    int m = m0 + (i * 4 + wave) * 8 + lr;
-    m = m < p.M ? m : p.M - 1;
-    if constexpr (CONV) {
-      const int hw = p.cOH * p.cOW;
-      const int b = m / hw, rem = m - b * hw;
-      const int oy = rem / p.cOW, ox = rem - oy * p.cOW;
-      a_row[i] = A + (size_t)b * p.cH * p.cW * p.cC;
-      a_iy[i] = oy * p.cstride - 1;
-      a_ix[i] = ox * p.cstride - 1;
-    } else {
-      a_row[i] = A + (size_t)m * p.lda;
-      a_iy[i] = a_ix[i] = 0;
-    }
-  }
+  for (int i = 0; i < A_IT; ++i) a_pc[i].setup(m0 + (i * 4 + wave) * 8 + lr, chunk * 8, p);
   const T* b_row[B_IT];
 #pragma unroll
   for (int i = 0; i < B_IT; ++i) {
@@ -618,13 +716,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vdn_gemm_desc p) {
     n = n < p.N ? n : p.N - 1;
     b_row[i] = (const T*)p.W + (size_t)n * p.ldb;
   }
-  const T* zeros = (const T*)p.zeros;
-  const float inv_cin = CONV ? 1.0f / (float)(p.cC >> 3) : 0.f;
-  ConvTap ctap[A_IT];
-  if constexpr (CONV) {
-#pragma unroll
-    for (int i = 0; i < A_IT; ++i) ctap[i] = conv_tap_setup(a_row[i], a_iy[i], a_ix[i], chunk * 8, p);
-  }
+  const char* zeros = (const char*)p.zeros;
 
   // K segments: [A_hi x W_hi] (+ [A_hi x W_lo]) (+ [A_lo x W_hi]) — the split-precision planes are
   // just further stretches of the same accumulation loop, selected by a plane byte offset.
@@ -642,56 +734,16 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vdn_gemm_desc p) {
     const int kt = kt_all - seg * nk1;
     const ptrdiff_t ad = (seg == seg_alo) ? a_delta : 0;
     const ptrdiff_t wd = (seg == seg_wlo) ? w_delta : 0;
-    const int k = kt * BK + chunk * 8;
-    if constexpr (CONV) {
-      // (tap, ci) of this lane's chunk; Cin % 8 == 0 so a chunk never straddles two taps
-      int tap, ci;
-      if (p.conv_korder) {  // (ci/64, tap, ci%64): one 64-channel block of one tap per K step
-        const int c64 = kt / 9;
-        tap = kt - c64 * 9;
-        ci = c64 * 64 + chunk * 8;
-        if (ci >= p.cC) tap = 9;
-      } else {
-        const int kc = k >> 3;
-        tap = (int)(((float)kc + 0.5f) * inv_cin);
-        ci = k - tap * p.cC;
-      }
-      const int ky = tap / 3, kx = tap - ky * 3;
-      const int fast_off = (p.conv_korder && tap < 9) ? conv_tap_offset(tap, p) + (kt / 9) * 64 : 0;
+    const KStep ks = kstep_decode<BK>(kt, p);
+    const int k = ks.k0 + chunk * 8;
 #pragma unroll
-      for (int i = 0; i < A_IT; ++i) {
-        bool ok;
-        const char* src;
-        if (p.conv_korder) {
-          ok = (tap < 9) & ((ctap[i].ok9 >> (tap < 9 ? tap : 0)) & 1);
-          src = (const char*)((const T*)ctap[i].center + fast_off) + ad;
-        } else {
-          const int iy = a_iy[i] + ky, ix = a_ix[i] + kx;
-          ok = (tap < 9) & (iy >= 0) & (iy < p.cH) & (ix >= 0) & (ix < p.cW);
-          src = (const char*)(a_row[i] + ((size_t)iy * p.cW + ix) * p.cC + ci) + ad;
-        }
-        src = ok ? src : (const char*)zeros;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(sA + (i * 4 + wave) * 1024),
-                                         16, 0, 0);
-      }
-    } else {
-      const bool ok = k < p.K;
-#pragma unroll
-      for (int i = 0; i < A_IT; ++i) {
-        const char* src = ok ? (const char*)(a_row[i] + k) + ad : (const char*)zeros;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(sA + (i * 4 + wave) * 1024),
-                                         16, 0, 0);
-      }
+    for (int i = 0; i < A_IT; ++i) {
+      bool ok;
+      const char* src = a_pc[i].src(ks, chunk * 8, p, ok);
+      glds16(ok ? src + ad : zeros, sA + (i * 4 + wave) * 1024);
     }
 #pragma unroll
-    for (int i = 0; i < B_IT; ++i) {
-      const char* src = (const char*)(b_row[i] + k) + wd;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(sB + (i * 4 + wave) * 1024),
-                                       16, 0, 0);
-    }
+    for (int i = 0; i < B_IT; ++i) glds16((const char*)(b_row[i] + k) + wd, sB + (i * 4 + wave) * 1024);
   };
 
   // ---- fragment read geometry
@@ -702,13 +754,13 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vdn_gemm_desc p) {
   for (int t = 0; t < TM; ++t) {
     const int row = wm * WTM + t * 16 + fr;
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) a_off[t][kk] = row * 128 + (((kk * 4 + fq) ^ ((row >> 1) & 7)) << 4);
+    for (int kk = 0; kk < 2; ++kk) a_off[t][kk] = frag_off128(row, kk * 4 + fq);
   }
 #pragma unroll
   for (int t = 0; t < TN; ++t) {
     const int row = wn * WTN + t * 16 + fr;
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) b_off[t][kk] = row * 128 + (((kk * 4 + fq) ^ ((row >> 1) & 7)) << 4);
+    for (int kk = 0; kk < 2; ++kk) b_off[t][kk] = frag_off128(row, kk * 4 + fq);
   }
 
   f32x4 acc[TM][TN];
@@ -774,25 +826,9 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(const vdn_gemm_desc p) {
   // staging: a 1-KiB DMA piece = 16 rows x 64 B; each wave moves pieces 2w, 2w+1 of every plane
   const int lr = lane >> 2;                                   // row inside the piece
   const int chunk = (lane & 3) ^ ((0 - (lane >> 4)) & 3);     // source 16-B chunk (row>>2 == lane>>4 mod 4)
-  const T* a_row[2];
-  int a_iy[2], a_ix[2];
-  const T* A = (const T*)p.A;
+  APiece<T, CONV> a_pc[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int m = m0 + (wave * 2 + i) * 16 + lr;
-    m = m < p.M ? m : p.M - 1;
-    if constexpr (CONV) {
-      const int hw = p.cOH * p.cOW;
-      const int b = m / hw, rem = m - b * hw;
-      const int oy = rem / p.cOW, ox = rem - oy * p.cOW;
-      a_row[i] = A + (size_t)b * p.cH * p.cW * p.cC;
-      a_iy[i] = oy * p.cstride - 1;
-      a_ix[i] = ox * p.cstride - 1;
-    } else {
-      a_row[i] = A + (size_t)m * p.lda;
-      a_iy[i] = a_ix[i] = 0;
-    }
-  }
+  for (int i = 0; i < 2; ++i) a_pc[i].setup(m0 + (wave * 2 + i) * 16 + lr, chunk * 8, p);
   const T* b_row[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -803,77 +839,31 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(const vdn_gemm_desc p) {
   const char* zeros = (const char*)p.zeros;
   const ptrdiff_t a_delta = (const char*)p.A_lo - (const char*)p.A;
   const ptrdiff_t w_delta = (const char*)p.W_lo - (const char*)p.W;
-  const float inv_cin = CONV ? 1.0f / (float)(p.cC >> 3) : 0.f;
-  ConvTap ctap[2];
-  if constexpr (CONV) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) ctap[i] = conv_tap_setup(a_row[i], a_iy[i], a_ix[i], chunk * 8, p);
-  }
 
-#define VDN_GLDS(src, dst)                                                                \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), \
-                                   (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
   auto stage = [&](int buf, int kt) {
     char* s0 = smem + buf * STAGE;
-    const int k = kt * BK3 + chunk * 8;
-    int ky = 0, kx = 0, ci = 0;
-    bool kok = k < p.K;
-    if constexpr (CONV) {
-      int tap;
-      if (p.conv_korder) {  // (ci/64, tap, half, ci%32): scalar decode, same for every lane of the step
-        const int half = kt & 1, t2 = kt >> 1;
-        const int c64 = t2 / 9;
-        tap = t2 - c64 * 9;
-        ci = c64 * 64 + half * 32 + chunk * 8;
-        if (ci >= p.cC) tap = 9;
-      } else {
-        tap = (int)(((float)(k >> 3) + 0.5f) * inv_cin);
-        ci = k - tap * p.cC;
-      }
-      ky = tap / 3;
-      kx = tap - ky * 3;
-      kok = tap < 9;
-    }
+    const KStep ks = kstep_decode<BK3>(kt, p);
+    const int k = ks.k0 + chunk * 8;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int pc = wave * 2 + i;
-      const char* src;
-      bool ok = kok;
-      if constexpr (CONV) {
-        if (p.conv_korder) {
-          const int tap = ky * 3 + kx;
-          ok = ok & ((ctap[i].ok9 >> tap) & 1);
-          src = (const char*)((const T*)ctap[i].center + (kok ? conv_tap_offset(tap, p) : 0) + (ci - chunk * 8));
-        } else {
-          const int iy = a_iy[i] + ky, ix = a_ix[i] + kx;
-          ok = ok & (iy >= 0) & (iy < p.cH) & (ix >= 0) & (ix < p.cW);
-          src = (const char*)(a_row[i] + ((size_t)iy * p.cW + ix) * p.cC + ci);
-        }
-      } else {
-        src = (const char*)(a_row[i] + k);
-      }
-      VDN_GLDS(ok ? src : zeros, s0 + pc * 1024);
-      VDN_GLDS(ok ? src + a_delta : zeros, s0 + TILE + pc * 1024);
+      bool ok;
+      const char* src = a_pc[i].src(ks, chunk * 8, p, ok);
+      glds16(ok ? src : zeros, s0 + pc * 1024);
+      glds16(ok ? src + a_delta : zeros, s0 + TILE + pc * 1024);
       const char* ws = (const char*)(b_row[i] + k);
-      VDN_GLDS(ws, s0 + 2 * TILE + pc * 1024);
-      VDN_GLDS(ws + w_delta, s0 + 3 * TILE + pc * 1024);
+      glds16(ws, s0 + 2 * TILE + pc * 1024);
+      glds16(ws + w_delta, s0 + 3 * TILE + pc * 1024);
     }
   };
-#undef VDN_GLDS
 
   const int wm = wave / WN, wn = wave % WN;
   const int fr = lane & 15, fq = lane >> 4;
   int a_off[TM], b_off[TN];
 #pragma unroll
-  for (int t = 0; t < TM; ++t) {
-    const int row = wm * WTM + t * 16 + fr;
-    a_off[t] = row * 64 + ((fq ^ ((0 - (row >> 2)) & 3)) << 4);
-  }
+  for (int t = 0; t < TM; ++t) a_off[t] = frag_off64(wm * WTM + t * 16 + fr, fq);
 #pragma unroll
-  for (int t = 0; t < TN; ++t) {
-    const int row = wn * WTN + t * 16 + fr;
-    b_off[t] = row * 64 + ((fq ^ ((0 - (row >> 2)) & 3)) << 4);
-  }
+  for (int t = 0; t < TN; ++t) b_off[t] = frag_off64(wn * WTN + t * 16 + fr, fq);
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -903,11 +893,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(const vdn_gemm_desc p) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        acc[i][j] = H::mfma16(bh[j], al[i], acc[i][j]);
-        acc[i][j] = H::mfma16(bl[j], ah[i], acc[i][j]);
-        acc[i][j] = H::mfma16(bh[j], ah[i], acc[i][j]);
-      }
+      for (int j = 0; j < TN; ++j) acc[i][j] = mma3<H>(bh[j], bl[j], ah[i], al[i], acc[i][j]);
     stage_barrier();
   }
   epilogue_dispatch<DT, TM, TN>(acc, p, m0 + wm * WTM, n0 + wn * WTN, lane);
@@ -940,18 +926,8 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
   const int ntiles = tiles_m * tiles_n;
   const int slice = (STORE == VDN_STX_SPLITK) ? (int)blockIdx.x / ntiles : 0;
   const int bid = (int)blockIdx.x - slice * ntiles;
-  // tile order inside an XCD's run: groups of 4 m-tiles walk n first, so that the ~32 tiles an
-  // XCD has in flight share A rows 8-fold and W columns 4-fold through its L2
-  int tile = xcd_remap(bid, ntiles);
   int tm_i, tn_i;
-  {
-    constexpr int GM = 4;
-    const int per_group = GM * tiles_n;
-    const int g = tile / per_group, r = tile - g * per_group;
-    const int gm = (tiles_m - g * GM) < GM ? (tiles_m - g * GM) : GM;
-    tn_i = r / gm;
-    tm_i = g * GM + (r - tn_i * gm);
-  }
+  tile_mn(xcd_remap(bid, ntiles), tiles_m, tiles_n, tm_i, tn_i);
   constexpr bool SUBPIX = STORE == VDN_STX_SUBPIX;  // sub-pixel convolution: the K loop walks the tap list of this tile's phase
   unsigned sp_taps = 0;
   int sp_lg = 0;
@@ -962,26 +938,9 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
 
   const int lr = lane >> 2;
   const int chunk = (lane & 3) ^ ((0 - (lane >> 4)) & 3);
-  const T* A = (const T*)p.A;
-  const T* a_row[2];
-  int a_iy[2], a_ix[2];
+  APiece<T, CONV> a_pc[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int pc = wave + 8 * i;
-    int m = m0 + pc * 16 + lr;
-    m = m < p.M ? m : p.M - 1;
-    if constexpr (CONV) {
-      const int hw = p.cOH * p.cOW;
-      const int b = m / hw, rem = m - b * hw;
-      const int oy = rem / p.cOW, ox = rem - oy * p.cOW;
-      a_row[i] = A + (size_t)b * p.cH * p.cW * p.cC;
-      a_iy[i] = oy * p.cstride - 1;
-      a_ix[i] = ox * p.cstride - 1;
-    } else {
-      a_row[i] = A + (size_t)m * p.lda;
-      a_iy[i] = a_ix[i] = 0;
-    }
-  }
+  for (int i = 0; i < 2; ++i) a_pc[i].setup(m0 + (wave + 8 * i) * 16 + lr, chunk * 8, p);
   const T* b_row[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -993,73 +952,27 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
   const char* zeros = (const char*)p.zeros;
   const ptrdiff_t a_delta = (const char*)p.A_lo - (const char*)p.A;
   const ptrdiff_t w_delta = (const char*)p.W_lo - (const char*)p.W;
-  const float inv_cin = CONV ? 1.0f / (float)(p.cC >> 3) : 0.f;
-  ConvTap ctap[2];
-  if constexpr (CONV) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) ctap[i] = conv_tap_setup(a_row[i], a_iy[i], a_ix[i], chunk * 8, p);
-  }
 
-#define VDN_GLDS(src, dst)                                                                \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), \
-                                   (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
   auto stage = [&](int buf, int kt) {
     char* s0 = smem + buf * STAGE;
-    kt += kt0;  // absolute K step of this slice
-    const int k = kt * BK3 + chunk * 8;
-    int ky = 0, kx = 0, ci = 0;
-    bool kok = k < p.K;
-    if constexpr (CONV) {
-      int tap;
-      if (p.conv_korder) {  // (ci/64, tap, half, ci%32): scalar decode, same for every lane of the step
-        const int half = kt & 1, t2 = kt >> 1;
-        int c64;
-        if constexpr (SUBPIX) {
-          c64 = t2 >> sp_lg;
-          tap = (sp_taps >> (4 * (t2 & ((1 << sp_lg) - 1)))) & 15;
-        } else {
-          c64 = t2 / 9;
-          tap = t2 - c64 * 9;
-        }
-        ci = c64 * 64 + half * 32 + chunk * 8;
-        if (ci >= p.cC) tap = 9;
-      } else {
-        tap = (int)(((float)(k >> 3) + 0.5f) * inv_cin);
-        ci = k - tap * p.cC;
-      }
-      ky = tap / 3;
-      kx = tap - ky * 3;
-      kok = tap < 9;
-    }
+    const KStep ks = kstep_decode<BK3, SUBPIX>(kt + kt0, p, sp_taps, sp_lg);  // absolute K step of this slice
+    const int k = ks.k0 + chunk * 8;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int pc = wave + 8 * i;
       if (pc < AP) {
-        const char* src;
-        bool ok = kok;
-        if constexpr (CONV) {
-          if (p.conv_korder) {
-            const int tap = ky * 3 + kx;
-            ok = ok & ((ctap[i].ok9 >> tap) & 1);
-            src = (const char*)((const T*)ctap[i].center + (kok ? conv_tap_offset(tap, p) : 0) + (ci - chunk * 8));
-          } else {
-            const int iy = a_iy[i] + ky, ix = a_ix[i] + kx;
-            ok = ok & (iy >= 0) & (iy < p.cH) & (ix >= 0) & (ix < p.cW);
-            src = (const char*)(a_row[i] + ((size_t)iy * p.cW + ix) * p.cC + ci);
-          }
-        } else {
-          src = (const char*)(a_row[i] + k);
-        }
-        VDN_GLDS(ok ? src : zeros, s0 + pc * 1024);
-        VDN_GLDS(ok ? src + a_delta : zeros, s0 + A_TILE + pc * 1024);
+        bool ok;
+        const char* src = a_pc[i].src(ks, chunk * 8, p, ok);
+        glds16(ok ? src : zeros, s0 + pc * 1024);
+        glds16(ok ? src + a_delta : zeros, s0 + A_TILE + pc * 1024);
       }
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int pc = wave + 8 * i;
       const char* ws = (const char*)(b_row[i] + k);
-      VDN_GLDS(ws, s0 + 2 * A_TILE + pc * 1024);
-      VDN_GLDS(ws + w_delta, s0 + 2 * A_TILE + W_TILE + pc * 1024);
+      glds16(ws, s0 + 2 * A_TILE + pc * 1024);
+      glds16(ws + w_delta, s0 + 2 * A_TILE + W_TILE + pc * 1024);
     }
   };
   // plain rows: per-lane source pointers advance by 64 B per K step (no per-step address math)
@@ -1067,7 +980,7 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
   const char* wp[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    ap[i][0] = (const char*)(a_row[i] + chunk * 8) + (size_t)kt0 * 64;  // kt0: first K step of this split-K slice
+    ap[i][0] = (const char*)(a_pc[i].base + chunk * 8) + (size_t)kt0 * 64;  // kt0: first K step of this split-K slice
     ap[i][1] = ap[i][0] + a_delta;
     wp[i][0] = (const char*)(b_row[i] + chunk * 8) + (size_t)kt0 * 64;
     wp[i][1] = wp[i][0] + w_delta;
@@ -1078,32 +991,25 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
     for (int i = 0; i < 2; ++i) {
       const int pc = wave + 8 * i;
       if (AP == 16 || pc < AP) {
-        VDN_GLDS(ap[i][0], s0 + pc * 1024);
-        VDN_GLDS(ap[i][1], s0 + A_TILE + pc * 1024);
+        glds16(ap[i][0], s0 + pc * 1024);
+        glds16(ap[i][1], s0 + A_TILE + pc * 1024);
         ap[i][0] += 64;
         ap[i][1] += 64;
       }
-      VDN_GLDS(wp[i][0], s0 + 2 * A_TILE + pc * 1024);
-      VDN_GLDS(wp[i][1], s0 + 2 * A_TILE + W_TILE + pc * 1024);
+      glds16(wp[i][0], s0 + 2 * A_TILE + pc * 1024);
+      glds16(wp[i][1], s0 + 2 * A_TILE + W_TILE + pc * 1024);
       wp[i][0] += 64;
       wp[i][1] += 64;
     }
   };
-#undef VDN_GLDS
 
   const int wm = wave >> 2, wn = wave & 3;
   const int fr = lane & 15, fq = lane >> 4;
   int a_off[TMW], b_off[TNW];
 #pragma unroll
-  for (int t = 0; t < TMW; ++t) {
-    const int row = wm * (BM / 2) + t * 16 + fr;
-    a_off[t] = row * 64 + ((fq ^ ((0 - (row >> 2)) & 3)) << 4);
-  }
+  for (int t = 0; t < TMW; ++t) a_off[t] = frag_off64(wm * (BM / 2) + t * 16 + fr, fq);
 #pragma unroll
-  for (int t = 0; t < TNW; ++t) {
-    const int row = wn * 64 + t * 16 + fr;
-    b_off[t] = 2 * A_TILE + row * 64 + ((fq ^ ((0 - (row >> 2)) & 3)) << 4);
-  }
+  for (int t = 0; t < TNW; ++t) b_off[t] = frag_off64(wn * 64 + t * 16 + fr, fq, 2 * A_TILE);
 
   f32x4 acc[TMW][TNW];
 #pragma unroll
@@ -1115,95 +1021,60 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
   // path), NOT at the padded weight stride — reading A columns K..ldb would run into the next row and,
   // on the last row, past the buffer (0 x NaN = NaN even though the padded weights are zero).
   const int nk = (nk_total - kt0) < nk_slice ? (nk_total - kt0) : nk_slice;
-  if constexpr (!PIPE) {
-    if constexpr (CONV) stage(0, 0); else stage_plain(0);
-    stage_barrier();
-  }
-
-  // one K step on stage `cur`; STAGED: the next stage's DMA is issued inside the step
-  auto step = [&](int kt, auto staged) {
-    constexpr bool STAGED = decltype(staged)::value;
-    const int cur = kt & 1;
-    if constexpr (STAGED) {
-      if constexpr (CONV) stage(cur ^ 1, kt + 1); else stage_plain(cur ^ 1);
-    }
-    const char* s0 = smem + cur * STAGE;
-    V8 bh[TNW], bl[TNW];
-    V8 ah[2][HALF], al[2][HALF];
+  auto issue = [&](int buf, int kt) {
+    if constexpr (CONV) stage(buf, kt); else stage_plain(buf);
+  };
+  auto read_b = [&](const char* s0, V8 (&h)[TNW], V8 (&l)[TNW]) {
 #pragma unroll
     for (int t = 0; t < TNW; ++t) {
-      bh[t] = *(const V8*)(s0 + b_off[t]);
-      bl[t] = *(const V8*)(s0 + W_TILE + b_off[t]);
+      h[t] = *(const V8*)(s0 + b_off[t]);
+      l[t] = *(const V8*)(s0 + W_TILE + b_off[t]);
     }
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-      for (int t = 0; t < HALF; ++t) {
-        ah[hf][t] = *(const V8*)(s0 + a_off[hf * HALF + t]);
-        al[hf][t] = *(const V8*)(s0 + A_TILE + a_off[hf * HALF + t]);
-        if constexpr (RELU_A) { ah[hf][t] = relu8(ah[hf][t]); al[hf][t] = relu8(al[hf][t]); }
-      }
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-      for (int i = 0; i < HALF; ++i)
-#pragma unroll
-        for (int j = 0; j < TNW; ++j) {
-          f32x4 c = acc[hf * HALF + i][j];
-          c = H::mfma16(bh[j], al[hf][i], c);
-          c = H::mfma16(bl[j], ah[hf][i], c);
-          c = H::mfma16(bh[j], ah[hf][i], c);
-          acc[hf * HALF + i][j] = c;
-        }
-    stage_barrier();
   };
+  auto read_a = [&](const char* s0, int hf, V8 (&h)[HALF], V8 (&l)[HALF]) {
+#pragma unroll
+    for (int t = 0; t < HALF; ++t) {
+      h[t] = *(const V8*)(s0 + a_off[hf * HALF + t]);
+      l[t] = *(const V8*)(s0 + A_TILE + a_off[hf * HALF + t]);
+      if constexpr (RELU_A) { h[t] = relu8(h[t]); l[t] = relu8(l[t]); }
+    }
+  };
+  auto mma = [&](int hf, V8 (&ah)[HALF], V8 (&al)[HALF], V8 (&bh)[TNW], V8 (&bl)[TNW]) {
+#pragma unroll
+    for (int i = 0; i < HALF; ++i)
+#pragma unroll
+      for (int j = 0; j < TNW; ++j) acc[hf * HALF + i][j] = mma3<H>(bh[j], bl[j], ah[i], al[i], acc[hf * HALF + i][j]);
+  };
+
   if constexpr (!PIPE) {
+    // lock-step: one K step on stage `cur`; STAGED: the next stage's DMA is issued inside the step
+    auto step = [&](int kt, auto staged) {
+      const int cur = kt & 1;
+      if constexpr (decltype(staged)::value) issue(cur ^ 1, kt + 1);
+      const char* s0 = smem + cur * STAGE;
+      V8 bh[TNW], bl[TNW], ah[2][HALF], al[2][HALF];
+      read_b(s0, bh, bl);
+      read_a(s0, 0, ah[0], al[0]);
+      read_a(s0, 1, ah[1], al[1]);
+      mma(0, ah[0], al[0], bh, bl);
+      mma(1, ah[1], al[1], bh, bl);
+      stage_barrier();
+    };
+    issue(0, 0);
+    stage_barrier();
     for (int kt = 0; kt + 1 < nk; ++kt) step(kt, std::true_type{});
     step(nk - 1, std::false_type{});
-  }
-
-
-  // ---- phase-shifted pipeline (PIPE): the stage barrier sits in the MIDDLE of a K step.
-  //   phase 1: MFMAs of A-half 0 (operands already in registers) || ds_read A-half 1 of this stage
-  //   [own LDS reads + own DMA complete; barrier]  -> this stage's buffer is free, next stage has landed
-  //   phase 2: issue DMA for stage k+2 || ds_read W and A-half 0 of stage k+1 || MFMAs of A-half 1
-  // so the matrix pipe always has register-resident work while DMA issue, LDS latency and the barrier
-  // pass (the plain loop idles ~1000 cycles per step on them). Costs a second W fragment set.
-  if constexpr (PIPE) {
-    auto issue = [&](int buf, int kt) {
-      if constexpr (CONV) stage(buf, kt); else stage_plain(buf);
-    };
+  } else {
+    // ---- phase-shifted pipeline (PIPE): the stage barrier sits in the MIDDLE of a K step.
+    //   phase 1: MFMAs of A-half 0 (operands already in registers) || ds_read A-half 1 of this stage
+    //   [own LDS reads + own DMA complete; barrier]  -> this stage's buffer is free, next stage has landed
+    //   phase 2: issue DMA for stage k+2 || ds_read W and A-half 0 of stage k+1 || MFMAs of A-half 1
+    // so the matrix pipe always has register-resident work while DMA issue, LDS latency and the barrier
+    // pass (the plain loop idles ~1000 cycles per step on them). Costs a second W fragment set.
     issue(0, 0);
     if (nk > 1) issue(1, 1);
     stage_barrier();
     V8 b0h[TNW], b0l[TNW], b1h[TNW], b1l[TNW], a0h[HALF], a0l[HALF], a1h[HALF], a1l[HALF];
-    auto read_b = [&](const char* s0, V8 (&h)[TNW], V8 (&l)[TNW]) {
-#pragma unroll
-      for (int t = 0; t < TNW; ++t) {
-        h[t] = *(const V8*)(s0 + b_off[t]);
-        l[t] = *(const V8*)(s0 + W_TILE + b_off[t]);
-      }
-    };
-    auto read_a = [&](const char* s0, int hf, V8 (&h)[HALF], V8 (&l)[HALF]) {
-#pragma unroll
-      for (int t = 0; t < HALF; ++t) {
-        h[t] = *(const V8*)(s0 + a_off[hf * HALF + t]);
-        l[t] = *(const V8*)(s0 + A_TILE + a_off[hf * HALF + t]);
-        if constexpr (RELU_A) { h[t] = relu8(h[t]); l[t] = relu8(l[t]); }
-      }
-    };
-    auto mma = [&](int hf, V8 (&ah_)[HALF], V8 (&al_)[HALF], V8 (&bh_)[TNW], V8 (&bl_)[TNW]) {
-#pragma unroll
-      for (int i = 0; i < HALF; ++i)
-#pragma unroll
-        for (int j = 0; j < TNW; ++j) {
-          f32x4 c = acc[hf * HALF + i][j];
-          c = H::mfma16(bh_[j], al_[i], c);
-          c = H::mfma16(bl_[j], ah_[i], c);
-          c = H::mfma16(bh_[j], ah_[i], c);
-          acc[hf * HALF + i][j] = c;
-        }
-    };
     read_b(smem, b0h, b0l);
     read_a(smem, 0, a0h, a0l);
     auto pstep = [&](int kt, V8 (&bch)[TNW], V8 (&bcl)[TNW], V8 (&bnh)[TNW], V8 (&bnl)[TNW]) {
@@ -1229,16 +1100,7 @@ __global__ __launch_bounds__(512) void gemm_x3_big_kernel(const vdn_gemm_desc p)
     stage_barrier();
   }
 
-  if constexpr (STORE == VDN_STX_SPLITK) {
-    vdn_gemm_desc q = p;
-    q.out = (float*)p.splitk_ws + (size_t)slice * p.M * p.N;
-    q.ldc = p.N;
-    epilogue_regs<DT, TMW, TNW, STORE, false>(acc, q, m0 + wm * (BM / 2), n0 + wn * 64, lane);
-  } else if constexpr (SUBPIX) {
-    epilogue_subpix<DT, TMW>(acc, p, m0 + wm * (BM / 2), n0 + wn * 64, lane);
-  } else {
-    epilogue_regs<DT, TMW, TNW, STORE, vdn_pair8<STORE>>(acc, p, m0 + wm * (BM / 2), n0 + wn * 64, lane);
-  }
+  epilogue_x3<DT, TMW, STORE>(acc, p, slice, m0 + wm * (BM / 2), n0 + wn * 64, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1305,14 +1167,7 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
     tile = xcd_remap(blockIdx.x, ntiles);
   }
   int tm_i, tn_i;
-  {
-    constexpr int GM = 4;
-    const int per_group = GM * tiles_n;
-    const int g = tile / per_group, r = tile - g * per_group;
-    const int gm = (tiles_m - g * GM) < GM ? (tiles_m - g * GM) : GM;
-    tn_i = r / gm;
-    tm_i = g * GM + (r - tn_i * gm);
-  }
+  tile_mn(tile, tiles_m, tiles_n, tm_i, tn_i);
   constexpr bool SUBPIX = STORE == VDN_STX_SUBPIX;  // sub-pixel convolution: the K loop walks the tap list of this tile's phase
   unsigned sp_taps = 0;
   int sp_lg = 0;
@@ -1331,39 +1186,9 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
   const int a_plane = a_both ? 0 : (wave & 1);
   const int pa[2] = {(a_li / TQ) * 2 * TQ + a_li % TQ, (a_li / TQ) * 2 * TQ + TQ + a_li % TQ};
   const int pw[2] = {4 * (wave >> 1) + (wave & 1), 4 * (wave >> 1) + (wave & 1) + 2};  // W pieces of sub-half 0 / 1
-  const T* A = (const T*)p.A;
-  const T* a_row[2];
-  int a_iy[2], a_ix[2];
+  APiece<T, CONV> a_pc[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int m = m0 + pa[i] * 16 + lr;
-    m = m < p.M ? m : p.M - 1;
-    if constexpr (CONV) {
-      const int hw = p.cOH * p.cOW;
-      const int b = m / hw, rem = m - b * hw;
-      const int oy = rem / p.cOW, ox = rem - oy * p.cOW;
-      a_row[i] = A + (size_t)b * p.cH * p.cW * p.cC;
-      a_iy[i] = oy * p.cstride - 1;
-      a_ix[i] = ox * p.cstride - 1;
-    } else {
-      a_row[i] = A + (size_t)m * p.lda;
-      a_iy[i] = a_ix[i] = 0;
-    }
-  }
-  // conv fast path: pointer to the centre tap's channel chunk and a 9-bit "tap inside the image" mask per piece
-  const T* center[2] = {nullptr, nullptr};
-  unsigned tap_ok[2] = {0, 0};
-  if constexpr (CONV) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      center[i] = a_row[i] + ((ptrdiff_t)(a_iy[i] + 1) * p.cW + (a_ix[i] + 1)) * p.cC + chunk * 8;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int iy = a_iy[i] + t / 3, ix = a_ix[i] + t % 3;
-        tap_ok[i] |= (unsigned)((iy >= 0) & (iy < p.cH) & (ix >= 0) & (ix < p.cW)) << t;
-      }
-    }
-  }
+  for (int i = 0; i < 2; ++i) a_pc[i].setup(m0 + pa[i] * 16 + lr, chunk * 8, p);
   const char* zeros = (const char*)p.zeros;
   const ptrdiff_t a_delta = (const char*)p.A_lo - (const char*)p.A;
   const ptrdiff_t w_delta = (const char*)p.W_lo - (const char*)p.W;
@@ -1374,11 +1199,8 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
     int n = n0 + (vdn_pair8<STORE> ? (pw[i] >> 2) * 64 + pair8_col(pw[i] & 3, lr) : pw[i] * 16 + lr);
     n = n < p.N ? n : p.N - 1;
     wp[i] = (const char*)((const T*)p.W + (size_t)n * p.ldb + chunk * 8);
-    ap[i] = (const char*)(a_row[i] + chunk * 8);
+    ap[i] = (const char*)(a_pc[i].base + chunk * 8);
   }
-#define VDN_GLDS(src, dst)                                                                \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), \
-                                   (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
   // unit u of K tile kt into stage `buf`: 0 = A sub-half 0, 1 = W sub-half 0, 2 = W sub-half 1, 3 = A sub-half 1
   auto issue = [&](auto uc, int buf, int kt) {
     constexpr int u = decltype(uc)::value;
@@ -1387,74 +1209,39 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
       constexpr int i = u == 0 ? 0 : 1;
       char* dst = s0 + pa[i] * 1024;
       if constexpr (CONV) {
-        bool ok;
-        const char* src;
-        kt += kt0s;  // absolute K step (split-K slices)
-        if (p.conv_korder) {
-          // (ci/64, tap, ci%64) K order: the K tile fixes one tap and one 32-channel slice for every lane, so
-          // the decode is wave-uniform scalar work; per lane only a precomputed validity bit and one 64-bit
-          // add remain (the general path below costs ~25 VALU per piece and made the conv K step 40 %
-          // slower than the plain GEMM's)
-          const int half = kt & 1, t2 = kt >> 1;
-          int c64, tap;  // scalar
-          if constexpr (SUBPIX) {
-            c64 = t2 >> sp_lg;
-            tap = (sp_taps >> (4 * (t2 & ((1 << sp_lg) - 1)))) & 15;
-          } else {
-            c64 = t2 / 9;
-            tap = t2 - c64 * 9;
-          }
-          const int ky = (tap * 11) >> 5, kx = tap - ky * 3;
-          const int off = ((ky - 1) * p.cW + (kx - 1)) * p.cC + c64 * 64 + half * 32;  // scalar, elements
-          ok = (tap_ok[i] >> tap) & 1;
-          src = (const char*)(center[i] + off);
-        } else {
-          const int k = kt * BK3 + chunk * 8;
-          const int tap = (int)(((float)(k >> 3) + 0.5f) * (1.0f / (float)(p.cC >> 3)));
-          const int ci = k - tap * p.cC;
-          const int ky = tap / 3, kx = tap - ky * 3;
-          const int iy = a_iy[i] + ky, ix = a_ix[i] + kx;
-          ok = (tap < 9) & (iy >= 0) & (iy < p.cH) & (ix >= 0) & (ix < p.cW);
-          src = (const char*)(a_row[i] + ((size_t)iy * p.cW + ix) * p.cC + ci);
-        }
+        bool ok;  // kt0s: absolute K step (split-K slices)
+        const char* src = a_pc[i].src(kstep_decode<BK3, SUBPIX>(kt + kt0s, p, sp_taps, sp_lg), chunk * 8, p, ok);
         if (a_both) {
-          VDN_GLDS(ok ? src : zeros, dst);
-          VDN_GLDS(ok ? src + a_delta : zeros, dst + A_TILE);
+          glds16(ok ? src : zeros, dst);
+          glds16(ok ? src + a_delta : zeros, dst + A_TILE);
         } else {
-          VDN_GLDS(ok ? src + (a_plane ? a_delta : 0) : zeros, dst + a_plane * A_TILE);
+          glds16(ok ? src + (a_plane ? a_delta : 0) : zeros, dst + a_plane * A_TILE);
         }
       } else {
         if (a_both) {
-          VDN_GLDS(ap[i], dst);
-          VDN_GLDS(ap[i] + a_delta, dst + A_TILE);
+          glds16(ap[i], dst);
+          glds16(ap[i] + a_delta, dst + A_TILE);
         } else {
-          VDN_GLDS(ap[i] + (a_plane ? a_delta : 0), dst + a_plane * A_TILE);
+          glds16(ap[i] + (a_plane ? a_delta : 0), dst + a_plane * A_TILE);
         }
         ap[i] += 64;
       }
     } else {
       constexpr int i = u == 1 ? 0 : 1;
       char* dst = s0 + 2 * A_TILE + pw[i] * 1024;
-      VDN_GLDS(wp[i], dst);
-      VDN_GLDS(wp[i] + w_delta, dst + W_TILE);
+      glds16(wp[i], dst);
+      glds16(wp[i] + w_delta, dst + W_TILE);
       wp[i] += 64;
     }
   };
-#undef VDN_GLDS
 
   // ---- fragment read offsets (same image and swizzle as the BM x 256 kernel)
   const int fr = lane & 15, fq = lane >> 4;
   int a_off[2 * TQ], b_off[4];
 #pragma unroll
-  for (int t = 0; t < 2 * TQ; ++t) {
-    const int row = wm * (BM / 2) + t * 16 + fr;
-    a_off[t] = row * 64 + ((fq ^ ((0 - (row >> 2)) & 3)) << 4);
-  }
+  for (int t = 0; t < 2 * TQ; ++t) a_off[t] = frag_off64(wm * (BM / 2) + t * 16 + fr, fq);
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int row = wn * 64 + t * 16 + fr;
-    b_off[t] = 2 * A_TILE + row * 64 + ((fq ^ ((0 - (row >> 2)) & 3)) << 4);
-  }
+  for (int t = 0; t < 4; ++t) b_off[t] = frag_off64(wn * 64 + t * 16 + fr, fq, 2 * A_TILE);
 
   f32x4 acc[2 * TQ][4];
 #pragma unroll
@@ -1492,13 +1279,7 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
 #pragma unroll
     for (int i = 0; i < TQ; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        f32x4 c = acc[qa * TQ + i][qb * 2 + j];
-        c = H::mfma16(bh[j], al[i], c);
-        c = H::mfma16(bl[j], ah[i], c);
-        c = H::mfma16(bh[j], ah[i], c);
-        acc[qa * TQ + i][qb * 2 + j] = c;
-      }
+      for (int j = 0; j < 2; ++j) acc[qa * TQ + i][qb * 2 + j] = mma3<H>(bh[j], bl[j], ah[i], al[i], acc[qa * TQ + i][qb * 2 + j]);
     __builtin_amdgcn_s_setprio(0);
   };
   // one phase: [fragment reads, DMA issue, counted wait] barrier [MFMAs] barrier
@@ -1549,31 +1330,53 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
 #undef VDN_PHASE
   if (wm == 0) __builtin_amdgcn_s_barrier();  // balance the barrier count of the two groups
 
-  if constexpr (SPLITK) {
-    vdn_gemm_desc q = p;
-    q.out = (float*)p.splitk_ws + (size_t)slice * p.M * p.N;
-    q.ldc = p.N;
-    epilogue_regs<DT, 2 * TQ, 4, STORE, false>(acc, q, m0 + wm * (BM / 2), n0 + wn * 64, lane);
-  } else if constexpr (SUBPIX) {
-    epilogue_subpix<DT, 2 * TQ>(acc, p, m0 + wm * (BM / 2), n0 + wn * 64, lane);
-  } else {
-    epilogue_regs<DT, 2 * TQ, 4, STORE, vdn_pair8<STORE>>(acc, p, m0 + wm * (BM / 2), n0 + wn * 64, lane);
-  }
+  epilogue_x3<DT, 2 * TQ, STORE>(acc, p, slice, m0 + wm * (BM / 2), n0 + wn * 64, lane);
   }  // tile loop
+}
+
+// ---- run-time launch choices -> compile-time template arguments: f is a generic lambda called with std::integral_constants
+template <int V> using IC = std::integral_constant<int, V>;
+// AMODE of the 4-wave kernels: 0 plain, 1 conv, 2 conv + relu, 3 plain + relu
+template <typename F>
+void with_amode(const vdn_gemm_desc& d, F&& f) {
+  if (d.a_mode == VDN_A_CONV3X3) { if (d.relu_a) f(IC<2>{}); else f(IC<1>{}); }
+  else { if (d.relu_a) f(IC<3>{}); else f(IC<0>{}); }
+}
+// (AMODE, epilogue flavour) pairs the 8-wave kernels are instantiated for: f(IC<AMODE>, IC<STORE>). Convolutions always
+// store plain NHWC rows (PLAIN or the split-plane HALF / RESHALF flavours) or are sub-pixel launches (AMODE 1 only);
+// the straight-line flavours of the encoder / memory linears exist for plain A only.
+template <typename F>
+void with_flavour(const vdn_gemm_desc& d, int fl, F&& f) {
+  if (d.a_mode == VDN_A_CONV3X3) {
+    auto conv = [&](auto st) { if (d.relu_a) f(IC<2>{}, st); else f(IC<1>{}, st); };
+    switch (fl) {
+      case VDN_STX_HALF: conv(IC<VDN_STX_HALF>{}); break;
+      case VDN_STX_RESHALF1: conv(IC<VDN_STX_RESHALF1>{}); break;
+      case VDN_STX_RESHALF2: conv(IC<VDN_STX_RESHALF2>{}); break;
+      case VDN_STX_SUBPIX: f(IC<1>{}, IC<VDN_STX_SUBPIX>{}); break;
+      default: conv(IC<VDN_ST_PLAIN>{}); break;
+    }
+  } else {
+    switch (fl) {
+      case VDN_ST_PLAIN: f(IC<0>{}, IC<VDN_ST_PLAIN>{}); break;
+      case VDN_STX_HALF: f(IC<0>{}, IC<VDN_STX_HALF>{}); break;
+      case VDN_ST_CONVT: f(IC<0>{}, IC<VDN_ST_CONVT>{}); break;
+      case VDN_ST_GEGLU: f(IC<0>{}, IC<VDN_ST_GEGLU>{}); break;
+      case VDN_STX_FC1: f(IC<0>{}, IC<VDN_STX_FC1>{}); break;
+      case VDN_STX_RES: f(IC<0>{}, IC<VDN_STX_RES>{}); break;
+      case VDN_STX_HEADS: f(IC<0>{}, IC<VDN_STX_HEADS>{}); break;
+      default: f(IC<0>{}, IC<VDN_ST_HEADS>{}); break;
+    }
+  }
 }
 
 template <int DT, int BM, int BN, int WM, int WN>
 int launch_tile(const vdn_gemm_desc& d, hipStream_t s) {
   const int tiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
   const size_t lds = 2 * (size_t)(BM + BN) * BK * 2;
-  const bool conv = d.a_mode == VDN_A_CONV3X3;
-  const int amode = conv ? (d.relu_a ? 2 : 1) : (d.relu_a ? 3 : 0);
-  switch (amode) {
-    case 0: hipLaunchKernelGGL((gemm_kernel<DT, BM, BN, WM, WN, 0>), dim3(tiles), dim3(256), lds, s, d); break;
-    case 1: hipLaunchKernelGGL((gemm_kernel<DT, BM, BN, WM, WN, 1>), dim3(tiles), dim3(256), lds, s, d); break;
-    case 2: hipLaunchKernelGGL((gemm_kernel<DT, BM, BN, WM, WN, 2>), dim3(tiles), dim3(256), lds, s, d); break;
-    default: hipLaunchKernelGGL((gemm_kernel<DT, BM, BN, WM, WN, 3>), dim3(tiles), dim3(256), lds, s, d); break;
-  }
+  with_amode(d, [&](auto am) {
+    hipLaunchKernelGGL((gemm_kernel<DT, BM, BN, WM, WN, decltype(am)::value>), dim3(tiles), dim3(256), lds, s, d);
+  });
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }
@@ -1582,14 +1385,7 @@ template <int DT>
 int launch_x3(const vdn_gemm_desc& d, hipStream_t s) {
   const int tiles = ((d.M + 127) / 128) * ((d.N + 127) / 128);
   const size_t lds = 65536;  // 2 stages x 4 planes x 8 KiB
-  const bool conv = d.a_mode == VDN_A_CONV3X3;
-  const int amode = conv ? (d.relu_a ? 2 : 1) : (d.relu_a ? 3 : 0);
-  switch (amode) {
-    case 0: hipLaunchKernelGGL((gemm_x3_kernel<DT, 0>), dim3(tiles), dim3(256), lds, s, d); break;
-    case 1: hipLaunchKernelGGL((gemm_x3_kernel<DT, 1>), dim3(tiles), dim3(256), lds, s, d); break;
-    case 2: hipLaunchKernelGGL((gemm_x3_kernel<DT, 2>), dim3(tiles), dim3(256), lds, s, d); break;
-    default: hipLaunchKernelGGL((gemm_x3_kernel<DT, 3>), dim3(tiles), dim3(256), lds, s, d); break;
-  }
+  with_amode(d, [&](auto am) { hipLaunchKernelGGL((gemm_x3_kernel<DT, decltype(am)::value>), dim3(tiles), dim3(256), lds, s, d); });
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }
@@ -1599,18 +1395,6 @@ int launch_x3_big(const vdn_gemm_desc& d, hipStream_t s) {
   const int tiles = ((d.M + BM - 1) / BM) * ((d.N + 255) / 256);
   const size_t lds = 2 * (size_t)(2 * BM * 64 + 2 * 256 * 64);
   const dim3 g(tiles), b(512);
-  const bool no_pipe = tuning(d).no_pipe != 0;
-  constexpr bool CAN_PIPE = BM <= 192;  // BM = 256 has no registers for the second W fragment set
-  const bool pipe = CAN_PIPE && !no_pipe;
-#define VDN_LAUNCH_BIG(AM, ST)                                                                          \
-  do {                                                                                                  \
-    if constexpr (CAN_PIPE && (AM == 0 || BM == 128)) { /* conv + BM=192 would spill */                \
-      if (pipe) hipLaunchKernelGGL((gemm_x3_big_kernel<DT, AM, BM, ST, true>), g, b, lds, s, d);        \
-      else hipLaunchKernelGGL((gemm_x3_big_kernel<DT, AM, BM, ST, false>), g, b, lds, s, d);            \
-    } else {                                                                                            \
-      hipLaunchKernelGGL((gemm_x3_big_kernel<DT, AM, BM, ST, false>), g, b, lds, s, d);                 \
-    }                                                                                                   \
-  } while (0)
   // straight-line epilogue flavours exist for the plain-A kernels at BM 256 / 192 (the encoder / memory linears)
   int fl = epi_flavour(d);
   // plane-output flavours store 8 columns (16 bytes) per lane: rows and column counts must keep that aligned
@@ -1622,63 +1406,23 @@ int launch_x3_big(const vdn_gemm_desc& d, hipStream_t s) {
   } else if (fl == VDN_STX_RESHALF1 || fl == VDN_STX_RESHALF2) {
     fl = d.store;
   }
+  bool p8 = false;
   if constexpr (BM == 256 || BM == 192) {  // ping-pong 8-phase kernel (VDN_GEMM_P8=0 falls back to the lock-step one)
     // measured (tools/gemm_bench.py): the ping-pong loop runs at 97 % of the clock-limited MFMA rate at BM 256
     // (24 MFMAs cover a load segment) but not at BM 192 (18 do not), where the lock-step PIPE loop is as fast:
     // default = BM 256 only; VDN_GEMM_P8=2 also BM 192, =0 never.
-    if (tuning(d).p8 >= (BM == 256 ? 1 : 2)) {
-      const dim3 g8 = g;
-#define VDN_LAUNCH_P8(AM, ST) hipLaunchKernelGGL((gemm_x3_p8_kernel<DT, AM, ST, BM>), g8, b, lds, s, d)
-      if (d.a_mode == VDN_A_CONV3X3) {
-#define VDN_CONV_P8(ST) do { if (d.relu_a) VDN_LAUNCH_P8(2, ST); else VDN_LAUNCH_P8(1, ST); } while (0)
-        switch (fl) {
-          case VDN_STX_HALF: VDN_CONV_P8(VDN_STX_HALF); break;
-          case VDN_STX_RESHALF1: VDN_CONV_P8(VDN_STX_RESHALF1); break;
-          case VDN_STX_RESHALF2: VDN_CONV_P8(VDN_STX_RESHALF2); break;
-          case VDN_STX_SUBPIX: VDN_LAUNCH_P8(1, VDN_STX_SUBPIX); break;
-          default: VDN_CONV_P8(VDN_ST_PLAIN); break;
-        }
-#undef VDN_CONV_P8
-      } else {
-        switch (fl) {
-          case VDN_ST_PLAIN: VDN_LAUNCH_P8(0, VDN_ST_PLAIN); break;
-          case VDN_STX_HALF: VDN_LAUNCH_P8(0, VDN_STX_HALF); break;
-          case VDN_ST_CONVT: VDN_LAUNCH_P8(0, VDN_ST_CONVT); break;
-          case VDN_ST_GEGLU: VDN_LAUNCH_P8(0, VDN_ST_GEGLU); break;
-          case VDN_STX_FC1: VDN_LAUNCH_P8(0, VDN_STX_FC1); break;
-          case VDN_STX_RES: VDN_LAUNCH_P8(0, VDN_STX_RES); break;
-          case VDN_STX_HEADS: VDN_LAUNCH_P8(0, VDN_STX_HEADS); break;
-          default: VDN_LAUNCH_P8(0, VDN_ST_HEADS); break;
-        }
-      }
-#undef VDN_LAUNCH_P8
-      VDN_CHECK_LAUNCH();
-      return VDN_OK;
-    }
+    p8 = tuning(d).p8 >= (BM == 256 ? 1 : 2);
+    if (p8) with_flavour(d, fl, [&](auto am, auto st) {
+      hipLaunchKernelGGL((gemm_x3_p8_kernel<DT, decltype(am)::value, decltype(st)::value, BM>), g, b, lds, s, d);
+    });
   }
-  if (d.a_mode == VDN_A_CONV3X3) {  // convolutions always store plain NHWC rows
-#define VDN_CONV_BIG(ST) do { if (d.relu_a) VDN_LAUNCH_BIG(2, ST); else VDN_LAUNCH_BIG(1, ST); } while (0)
-    switch (fl) {
-      case VDN_STX_HALF: VDN_CONV_BIG(VDN_STX_HALF); break;
-      case VDN_STX_RESHALF1: VDN_CONV_BIG(VDN_STX_RESHALF1); break;
-      case VDN_STX_RESHALF2: VDN_CONV_BIG(VDN_STX_RESHALF2); break;
-      case VDN_STX_SUBPIX: VDN_LAUNCH_BIG(1, VDN_STX_SUBPIX); break;
-      default: VDN_CONV_BIG(VDN_ST_PLAIN); break;
-    }
-#undef VDN_CONV_BIG
-  } else {
-    switch (fl) {
-      case VDN_ST_PLAIN: VDN_LAUNCH_BIG(0, VDN_ST_PLAIN); break;
-      case VDN_STX_HALF: VDN_LAUNCH_BIG(0, VDN_STX_HALF); break;
-      case VDN_ST_CONVT: VDN_LAUNCH_BIG(0, VDN_ST_CONVT); break;
-      case VDN_ST_GEGLU: VDN_LAUNCH_BIG(0, VDN_ST_GEGLU); break;
-      case VDN_STX_FC1: VDN_LAUNCH_BIG(0, VDN_STX_FC1); break;
-      case VDN_STX_RES: VDN_LAUNCH_BIG(0, VDN_STX_RES); break;
-      case VDN_STX_HEADS: VDN_LAUNCH_BIG(0, VDN_STX_HEADS); break;
-      default: VDN_LAUNCH_BIG(0, VDN_ST_HEADS); break;
-    }
-  }
-#undef VDN_LAUNCH_BIG
+  if (!p8) with_flavour(d, fl, [&](auto am, auto st) {
+    constexpr int AM = decltype(am)::value, ST = decltype(st)::value;
+    // BM = 256 has no registers for the second W fragment set; conv + BM = 192 would spill
+    constexpr bool CAN_PIPE = BM <= 192 && (AM == 0 || BM == 128);
+    if (CAN_PIPE && !tuning(d).no_pipe) hipLaunchKernelGGL((gemm_x3_big_kernel<DT, AM, BM, ST, CAN_PIPE>), g, b, lds, s, d);
+    else hipLaunchKernelGGL((gemm_x3_big_kernel<DT, AM, BM, ST, false>), g, b, lds, s, d);
+  });
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

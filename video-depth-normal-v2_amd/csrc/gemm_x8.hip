@@ -60,9 +60,6 @@ constexpr int x8_inflight(int newest, int k, bool four) {
   for (int t = 0; t < k; ++t) n += x8_pc((newest - t) & 3, four);
   return n;
 }
-#define X8_GLDS(src, dst)                                                                 \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), \
-                                   (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
 
 // PAIR: the W rows of a tile are loaded in the order that gives every lane 8 consecutive output columns per block row
 template <int STORE, bool PAIR, int X8_BM>
@@ -76,16 +73,8 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tiles_n = (p.N + X8_BN - 1) / X8_BN, tiles_m = (p.M + X8_BM - 1) / X8_BM;
-  const int tile = xcd_remap(blockIdx.x, tiles_m * tiles_n);
   int tm_i, tn_i;
-  {  // groups of 4 m-tiles walk n first (an XCD's tiles in flight share A rows and W columns through its L2)
-    constexpr int GM = 4;
-    const int per_group = GM * tiles_n;
-    const int g = tile / per_group, r = tile - g * per_group;
-    const int gm = (tiles_m - g * GM) < GM ? (tiles_m - g * GM) : GM;
-    tn_i = r / gm;
-    tm_i = g * GM + (r - tn_i * gm);
-  }
+  tile_mn(xcd_remap(blockIdx.x, tiles_m * tiles_n), tiles_m, tiles_n, tm_i, tn_i);
   const int m0 = tm_i * X8_BM, n0 = tn_i * X8_BN;
   const int wm = wave >> 2, wn = wave & 3;
   const int r = lane & 31, h = lane >> 5;
@@ -144,8 +133,8 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
       // 64-bit vector adds in the loop; block of four 620 -> 604 us)
       unsigned oa = ph < 2 ? ah_o[i] : a8_o[i], ow = ph < 2 ? wh_o[i] : w8_o[i];
       asm volatile("" : "+v"(oa), "+v"(ow));
-      if (AP == 16 || wave + 8 * i < AP) X8_GLDS(ba + oa, ua + (wave + 8 * i) * 1024);
-      X8_GLDS(bw + ow, uw + (wave + 8 * i) * 1024);
+      if (AP == 16 || wave + 8 * i < AP) glds16(ba + oa, ua + (wave + 8 * i) * 1024);
+      glds16(bw + ow, uw + (wave + 8 * i) * 1024);
     }
   };
   // Counted waits: the K newest units may stay in flight, the newest being the unit of phase NEWPH. A wave's DMA instructions
@@ -583,7 +572,6 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
   }
 }
 #undef X8_WAIT
-#undef X8_GLDS
 
 template <int BM>
 static int x8_launch(const vdn_gemm_desc& d, hipStream_t s) {

@@ -406,6 +406,31 @@ int vdn_dn_prologue(int dt, const float* a, const float* b, int frames, int C, i
 int vdn_dn_tail(const float* x, int F, int IH, int IW, int Cin, const float* w, const float* bias, int OH, int OW,
                 const float* depth_in, int relu, float* raw, float* depth, float* normal, vdn_stream stream);
 
+/* Hiera trunk of the depth + normal model (models/hiera_image_encoder.py:35,60: hiera_{tiny,small,base}_224 of the
+ * published Hiera code, inference, no masking; a 224 x 224 frame gives 56 x 56 tokens, head dim 96 at every stage).
+ * Tokens live in the model's UNROLLED order: with d_k = 2*sy_k + sx_k the three nested stride-2 levels of the grid,
+ * u = ((d1*4 + d2)*4 + d3)*49 + Y*7 + X for position y = 8Y + 4 sy3 + 2 sy2 + sy1 (x alike), so every 2 x 2 max-pool is a
+ * max over the 4 contiguous quarters of a frame's token axis; stage s keeps the last 3 - s digits.
+ * vdn_hiera_embed  — the gather of patch_embed.proj (Conv2d 3 -> 96, 7 x 7, stride 4, pad 3) as GEMM rows, already in
+ *                    unrolled order (the model's `unroll` costs no pass): rows half [frames*3136, ldk],
+ *                    row f*3136 + u, k = (c*7 + ky)*7 + kx = img[f, c, 4y-3+ky, 4x-3+kx] (0 outside), zero tail to ldk
+ *                    (>= 147, a multiple of 64); img f32 [frames, 3, 224, 224]. The projection is a vdn_gemm whose `tab`
+ *                    adds pos_embed permuted to unrolled order.
+ * vdn_hiera_attn   — MaskUnitAttention: qkv half [frames*W*Lkv, 3C] (C = heads*96, columns q | k | v, each [heads][96]);
+ *                    token t of window w of frame f is row f*W*Lkv + t*W + w. q_stride > 1 (the width-changing blocks):
+ *                    t = g*Lq + j, Lq = Lkv / q_stride, and query j is the element-wise max of its q_stride rows
+ *                    (the query max-pool), fused on load. out half [frames*W*Lq, C], row f*W*Lq + j*W + w. fp32 softmax.
+ *                    W = 49 windows for the mask-unit stages, 1 for global attention. qkv_lo / out_lo: both or neither.
+ * vdn_hiera_pool   — y[f, j, :] = max over g < 4 of x[f, g*n + j, :]; x f32 [frames, 4n, C], y f32 [frames, n, C]
+ *                    (the max-pool of a width-changing block's projected residual). C % 4 == 0.
+ * vdn_hiera_reroll — the model's `reroll` + undo_windowing: unrolled tokens f32 [frames, (56 >> stage)^2, C] of stage
+ *                    0..3 -> f32 NHWC map [frames, 56 >> stage, 56 >> stage, C] (what vdn_dn_prologue reads). C % 4 == 0. */
+int vdn_hiera_embed(int dt, const float* img, void* rows, void* rows_lo, int frames, int ldk, vdn_stream stream);
+int vdn_hiera_attn(int dt, const void* qkv, const void* qkv_lo, void* out, void* out_lo, int frames, int heads, int W, int Lkv,
+                   int q_stride, float scale, vdn_stream stream);
+int vdn_hiera_pool(const float* x, float* y, int frames, int n, int C, vdn_stream stream);
+int vdn_hiera_reroll(const float* tokens, float* map, int frames, int stage, int C, vdn_stream stream);
+
 /* One-time weight packing ON THE DEVICE, so that a host in any language can feed the library from the reference's
  * fp32 parameter tensors as torch.nn stores them (vdn/pack.py is a thin caller of these). `w` is the contiguous fp32
  * parameter, (hi, lo) the [rows, ldb] planes vdn_gemm reads (lo may be NULL for the 1-product modes): K contiguous,

@@ -159,6 +159,41 @@ for Ci, k in ((256, 4), (512, 2)):
     bad += diff
     print(f"subpixel conv k={k} Ci={Ci} B=8 37x37: {diff} of {reps // 4} runs differ", flush=True)
     del wsp, pm, o, h0, l0
+# Hiera trunk kernels (csrc/hiera.hip): the LDS-staged key / value tiles of the attention (a pooled-query windowed shape and
+# the 196-key global one, which takes four tiles), then the gather, pool and reroll passes
+for (F, heads, W, Lkv, qs) in ((8, 2, 49, 64, 4), (8, 4, 1, 196, 1), (8, 8, 1, 196, 4)):
+    C = heads * 96
+    qkv = rt.to_half(torch.randn(F * W * Lkv, 3 * C, device="cuda"))
+    o = rt.hbuf(f"rs_hi{heads}_{qs}", (F * W * Lkv // qs, C))
+    rt.hiera_attn(qkv, o, F, heads, W, Lkv, qs, 96 ** -0.5)
+    h0, l0 = o.hi.clone(), o.lo.clone()
+    diff = 0
+    for _ in range(reps):
+        rt.hiera_attn(qkv, o, F, heads, W, Lkv, qs, 96 ** -0.5)
+        diff += int(not (torch.equal(o.hi, h0) and torch.equal(o.lo, l0)))
+    bad += diff
+    print(f"hiera_attn F={F} heads={heads} W={W} Lkv={Lkv} q_stride={qs}: {diff} of {reps} runs differ", flush=True)
+img = torch.randn(8, 3, 224, 224, device="cuda")
+hr = rt.hbuf("rs_hi_rows", (8 * 3136, 192))
+px, py = torch.randn(8 * 3136, 192, device="cuda"), torch.empty(8 * 784, 192, device="cuda")
+pm = torch.empty(8, 28, 28, 192, device="cuda")
+
+
+def run_hiera():
+    rt.hiera_embed(img, hr, 8, 192)
+    rt.hiera_pool(px, py, 8, 784, 192)
+    rt.hiera_reroll(py, pm, 8, 1, 192)
+
+
+run_hiera()
+ref = [t.clone() for t in (hr.hi, hr.lo, py, pm)]
+diff = 0
+for _ in range(reps // 4):
+    run_hiera()
+    diff += int(not all(torch.equal(x, y) for x, y in zip((hr.hi, hr.lo, py, pm), ref)))
+bad += diff
+print(f"hiera embed + pool + reroll F=8: {diff} of {reps // 4} runs differ", flush=True)
+del img, hr, px, py, pm, ref
 t = torch.randn(10960, 1024, device="cuda")
 g, be = torch.randn(1024, device="cuda"), torch.randn(1024, device="cuda")
 oh = rt.hbuf("rs_ln", (10960, 1024))

@@ -21,6 +21,9 @@ def __getattr__(name):
     if name == "VideoDepthAnythingHeadV2":
         from .video_depth_head_v2_sangyu import VideoDepthAnythingHeadV2
         return VideoDepthAnythingHeadV2
+    if name == "HieraImageEncoder":
+        from .hiera_image_encoder import HieraImageEncoder
+        return HieraImageEncoder
     if name == "VideoDepthEstimationModel":
         from .video_depth_model import VideoDepthEstimationModel
         return VideoDepthEstimationModel

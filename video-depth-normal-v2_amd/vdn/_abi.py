@@ -113,6 +113,10 @@ EXPORTS = {
                               C.c_int, C.c_float, vp]),
     "vdn_dn_prologue": (C.c_int, [C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, vp, vp, vp]),
     "vdn_dn_tail": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, fp, C.c_int, fp, fp, fp, vp]),
+    "vdn_hiera_embed": (C.c_int, [C.c_int, fp, vp, vp, C.c_int, C.c_int, vp]),
+    "vdn_hiera_attn": (C.c_int, [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
+    "vdn_hiera_pool": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_hiera_reroll": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_stitch_workspace_bytes": (C.c_size_t, []),
     "vdn_stitch_fit": (C.c_int, [fp, fp, C.c_size_t, vp, fp, vp]),
     "vdn_stitch_apply": (C.c_int, [fp, fp, fp, fp, fp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

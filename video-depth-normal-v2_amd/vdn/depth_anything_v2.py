@@ -61,6 +61,12 @@ class _EngineOwner(nn.Module):
         self._eng = None
         return super().load_state_dict(*a, **k)
 
+    def _load_from_state_dict(self, *a, **k):
+        """An engine owner nested in another module (the native trunks of VideoDepthEstimationModel) is loaded through its
+        parent's load_state_dict, which recurses here and never calls the child's load_state_dict: drop the packed weights."""
+        self._eng = None
+        return super()._load_from_state_dict(*a, **k)
+
     def _runtime(self) -> Runtime:
         dev = next(self.parameters()).device
         _, (dtype, split) = _precision(self.precision)

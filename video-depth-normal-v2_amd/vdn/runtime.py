@@ -398,6 +398,29 @@ class Runtime:
         self._launch(abi.lib.vdn_dn_tail, x.data_ptr(), F, IH, IW, Cn, w.data_ptr(), bias.data_ptr(), OH, OW, self._p(depth_in),
                      int(relu), self._p(raw), self._p(depth), self._p(normal))
 
+    def hiera_embed(self, img: torch.Tensor, rows, frames: int, ldk: int):
+        """f32 [frames, 3, 224, 224] -> the 7 x 7 patch rows [frames*3136, ldk] in unrolled token order (include/vdn.h)."""
+        assert img.dtype == torch.float32 and img.is_contiguous() and tuple(img.shape) == (frames, 3, 224, 224), img.shape
+        rows, rl = _hl(rows)
+        self._launch(abi.lib.vdn_hiera_embed, self.dt, img.data_ptr(), rows.data_ptr(), rl, frames, ldk)
+
+    def hiera_attn(self, qkv, out, frames: int, heads: int, W: int, Lkv: int, q_stride: int, scale: float):
+        """Mask-unit / global attention of the Hiera trunk (include/vdn.h vdn_hiera_attn): qkv [frames*W*Lkv, 3*heads*96]."""
+        (qh, ql), (oh, ol) = _hl(qkv), _hl(out)
+        assert qh.numel() == frames * W * Lkv * 3 * heads * 96 and oh.numel() * q_stride == frames * W * Lkv * heads * 96
+        self._launch(abi.lib.vdn_hiera_attn, self.dt, qh.data_ptr(), ql, oh.data_ptr(), ol, frames, heads, W, Lkv, q_stride, scale,
+                     tag="hiera_attn", flop=4.0 * frames * W * heads * (Lkv // q_stride) * Lkv * 96)
+
+    def hiera_pool(self, x: torch.Tensor, y: torch.Tensor, frames: int, n: int, Cn: int):
+        assert x.dtype == y.dtype == torch.float32 and x.numel() == frames * 4 * n * Cn and y.numel() == frames * n * Cn
+        self._launch(abi.lib.vdn_hiera_pool, x.data_ptr(), y.data_ptr(), frames, n, Cn)
+
+    def hiera_reroll(self, tokens: torch.Tensor, out: torch.Tensor, frames: int, stage: int, Cn: int):
+        side = 56 >> stage
+        assert tokens.dtype == out.dtype == torch.float32 and tokens.numel() == out.numel() == frames * side * side * Cn
+        assert out.is_contiguous()
+        self._launch(abi.lib.vdn_hiera_reroll, tokens.data_ptr(), out.data_ptr(), frames, stage, Cn)
+
     def patchify(self, img, rows, B: int, H: int, W: int, ldk: int):
         rows, rl = _hl(rows)
         self._launch(abi.lib.vdn_patchify, self.dt, img.data_ptr(), rows.data_ptr(), rl, B, H, W, ldk)

@@ -1,7 +1,8 @@
 """Drop-in for models/video_depth_model.py:19-125 (VideoDepthEstimationModel, the depth + normal model).
 
 The reference builds its two Hiera trunks with torch.hub (models/hiera_image_encoder.py:35), which needs the network; here
-the caller injects them (`trunk=` for the depth branch, `img_trunk=` for the RGB branch). They are registered as
+`with_native_trunks` builds them from vdn.HieraImageEncoder (csrc/hiera.hip), or the caller injects any other module
+(`trunk=` for the depth branch, `img_trunk=` for the RGB branch). They are registered as
 `encoder` / `img_encoder`, so state-dict keys equal the reference's. A trunk is any module whose forward(x [N, 3, H, W])
 returns (anything, [4 f32 NHWC maps [N, h_l, w_l, C_l]]) with C = 96 / 192 / 384 / 768 at strides 4 / 8 / 16 / 32
 (hiera_image_encoder.py:53-58). Everything after the trunks runs on libvdn_hip.so: the Sobel normals of the input
@@ -38,6 +39,24 @@ class VideoDepthEstimationModel(_EngineOwner):
         self.encoder = trunk
         self.head = VideoDepthAnythingHeadV2(sequence_length=sequence_length, pe=pe, attention_feature_levels=attention_feature_levels)
         self.set_finetune_modes(encoder_finetune=encoder_finetune)
+
+    @classmethod
+    def with_native_trunks(cls, sequence_length, encoder="hiera_base_224", **kw):
+        """The model with both Hiera trunks built here (vdn.HieraImageEncoder, csrc/hiera.hip) instead of injected: the
+        module tree and state-dict keys of the reference (`encoder.model.*`, `img_encoder.model.*`), nothing fetched."""
+        from .hiera_image_encoder import HieraImageEncoder
+        finetune = kw.get("encoder_finetune", False)
+        trunk = HieraImageEncoder(encoder, finetune=finetune)
+        img_trunk = HieraImageEncoder(encoder, finetune=finetune).share_runtime(trunk)   # one workspace arena for both
+        return cls(sequence_length, encoder=encoder, trunk=trunk, img_trunk=img_trunk, **kw)
+
+    def set_precision(self, name: str):
+        """The native trunks are engine owners of their own: they follow the model's precision."""
+        super().set_precision(name)
+        for t in (self.encoder, self.img_encoder):
+            if isinstance(t, _EngineOwner):
+                t.set_precision(name)
+        return self
 
     def _engines(self):
         if self._eng is None:

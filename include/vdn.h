@@ -389,6 +389,8 @@ int vdn_oc1_combine(const float* z, const float* bias, float* out, int B, int IH
  *                   (g1 < n1, g0 < n0) is the L rows g1*s1 + g0*s0 + j*estride, j < L: spatial = (L = h*w, estride 1,
  *                   n0 1, n1 B*S, s1 h*w), temporal = (L = S, estride h*w, n0 h*w, s0 1, n1 B, s1 S*h*w). Head dim
  *                   C/heads in {12, 24, 48, 96}; online softmax, any L. qkv_lo / out_lo: split planes (both or neither).
+ *                   Shares lane_attn_kernel (csrc/lane_attn.hip) with vdn_hiera_attn: these arguments are its sequence
+ *                   geometry as they stand, with output stride s1 and no query pooling (Lq = L).
  * vdn_dn_prologue — the features the head consumes, in one launch per level (video_depth_model.py:89-103,
  *                   video_depth_head_v2_sangyu.py:272-276): token[(f*hw + p), c] = a[f][c*hw + p] (+ b[f][c*hw + p])
  *                   (+ ape[f % S][c]); a / b f32 per frame [C*hw] (the trunk's NHWC buffers read flat = the `.view`
@@ -421,6 +423,8 @@ int vdn_dn_tail(const float* x, int F, int IH, int IW, int Cin, const float* w, 
  *                    t = g*Lq + j, Lq = Lkv / q_stride, and query j is the element-wise max of its q_stride rows
  *                    (the query max-pool), fused on load. out half [frames*W*Lq, C], row f*W*Lq + j*W + w. fp32 softmax.
  *                    W = 49 windows for the mask-unit stages, 1 for global attention. qkv_lo / out_lo: both or neither.
+ *                    Shares lane_attn_kernel with vdn_dn_attn: in that entry's terms L = Lkv, estride = W, n0 = W, s0 = 1,
+ *                    n1 = frames, s1 = W*Lkv, with output stride W*Lq and q_stride elements pooled into a query.
  * vdn_hiera_pool   — y[f, j, :] = max over g < 4 of x[f, g*n + j, :]; x f32 [frames, 4n, C], y f32 [frames, n, C]
  *                    (the max-pool of a width-changing block's projected residual). C % 4 == 0.
  * vdn_hiera_reroll — the model's `reroll` + undo_windowing: unrolled tokens f32 [frames, (56 >> stage)^2, C] of stage

@@ -1,4 +1,4 @@
-"""Depth + normal model on the MI355X: the three new kernels (csrc/dn_head.hip) against fp64 torch, and the head / wrapper
+"""Depth + normal model on the MI355X: its kernels (csrc/dn_head.hip, csrc/lane_attn.hip) against fp64 torch, and the head / wrapper
 against the fixtures the imported reference wrote (tools/make_golden_dn.py)."""
 import os
 
@@ -56,6 +56,26 @@ def test_dn_attn_vs_fp64(C, hw, S, B, temporal, split):
     tol = 1e-5 if split else 2e-3
     assert rel_l2(got, ref) < tol, rel_l2(got, ref)
     assert worst_px(got, ref) < 10 * tol
+
+
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("frames,heads,W,Lkv", [(2, 2, 49, 16),    # windowed: the stride translation
+                                                (3, 1, 1, 196)])   # global: partial last query tile and last key tile
+def test_dn_and_hiera_entries_agree_bitwise(frames, heads, W, Lkv, split):
+    """vdn_dn_attn and vdn_hiera_attn are one kernel (csrc/lane_attn.hip) behind two argument lists: on a geometry both can
+    express (q_stride 1) the same planes give the same bytes."""
+    rt = _rt(split)
+    C, rows = heads * 96, frames * W * Lkv
+    g = torch.Generator().manual_seed(frames * 1000 + W + Lkv)
+    qkv = rt.to_half((torch.randn(rows, 3 * C, generator=g) * 1.2).to(DEV))
+    a, b = rt.hbuf("a", (rows, C)), rt.hbuf("b", (rows, C))
+    rt.hiera_attn(qkv, a, frames, heads, W, Lkv, 1, 96 ** -0.5)
+    rt.dn_attn(qkv, b, rows, C, heads, L=Lkv, estride=W, n0=W, s0=1 if W > 1 else 0, n1=frames, s1=W * Lkv, scale=96 ** -0.5)
+    assert torch.equal(a.hi, b.hi)
+    assert (a.lo is None) == (b.lo is None) == (not split)
+    if split:
+        assert torch.equal(a.lo, b.lo)
+    assert bool(torch.isfinite(a.hi.float()).all()) and float(a.hi.float().abs().max()) > 0   # both ran on real values
 
 
 def test_dn_prologue_bitwise():

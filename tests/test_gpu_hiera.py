@@ -1,5 +1,5 @@
-"""Native Hiera trunk on the MI355X: the four kernels of csrc/hiera.hip against torch computations made here
-(tests/hiera_ref.py), the trunk against the fixtures tools/make_golden_hiera.py took from the `transformers` port of the
+"""Native Hiera trunk on the MI355X: the kernels of csrc/hiera.hip and the trunk's attention (csrc/lane_attn.hip) against
+torch computations made here (tests/hiera_ref.py), the trunk against the fixtures tools/make_golden_hiera.py took from the `transformers` port of the
 model, and the depth + normal model on native trunks against the imported reference wrapper's fixture."""
 import os
 
@@ -201,7 +201,7 @@ def test_trunk_forward_runs_no_aten_kernel():
     print("device kernels of one trunk forward:", sorted(kernels))
     assert not any(k.startswith(("void at::", "at::", "Cijk", "void rocprim")) for k in kernels), sorted(kernels)
     assert kernels, "the profiler reported no device activity"
-    assert any("hiera_attn_kernel" in k for k in kernels), sorted(kernels)
+    assert any("lane_attn_kernel" in k for k in kernels), sorted(kernels)
 
 
 # ------------------------------------------------------------------------------------------------------ wrapper

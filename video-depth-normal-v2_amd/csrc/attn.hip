@@ -784,9 +784,9 @@ extern "C" int vdn_temporal_attn(int dt, const void* qkv, void* out, const void*
   const int nseq = Bv * D * heads;
   const float sl2 = scale * 1.44269504088896340736f;
   hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_F16) return temporal_launch<VDN_F16>(qkv, out, qkv_lo, out_lo, nseq, T, D, c, heads, sl2, rope_cs, s);
-  if (dt == VDN_BF16) return temporal_launch<VDN_BF16>(qkv, out, qkv_lo, out_lo, nseq, T, D, c, heads, sl2, rope_cs, s);
-  return VDN_EUNSUPPORTED;
+  return with_half(dt, [&](auto t) {
+    return temporal_launch<decltype(t)::value>(qkv, out, qkv_lo, out_lo, nseq, T, D, c, heads, sl2, rope_cs, s);
+  });
 }
 
 extern "C" int vdn_temporal_attn_last(int dt, const float* pool, size_t slot_stride, const int32_t* slots, int T, int HW,
@@ -802,24 +802,24 @@ extern "C" int vdn_temporal_attn_last(int dt, const float* pool, size_t slot_str
   if (c <= 0 || (c & 63) || c > 1024) return VDN_EUNSUPPORTED;  // 8 heads of c/8 = 8 lanes x c/64 channels
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((HW + 3) / 4), block(256);
-#define VDN_TL(DT_, CPL_)                                                                                                  \
-  hipLaunchKernelGGL((temporal_last_kernel<DT_, CPL_>), grid, block, 0, s, pool, slot_stride, tab, T, HW, c, pe_q, pe_k, \
-                     pe_v, scale, (typename Half<DT_>::T*)out, (typename Half<DT_>::T*)out_lo)
-#define VDN_TL_C(DT_)                                  \
-  switch (c) {                                         \
-    case 64: VDN_TL(DT_, 1); break;                    \
-    case 128: VDN_TL(DT_, 2); break;                   \
-    case 192: VDN_TL(DT_, 3); break;                   \
-    case 256: VDN_TL(DT_, 4); break;                   \
-    case 384: VDN_TL(DT_, 6); break;                   \
-    case 512: VDN_TL(DT_, 8); break;                   \
-    case 768: VDN_TL(DT_, 12); break;                  \
-    case 1024: VDN_TL(DT_, 16); break;                 \
-    default: return VDN_EUNSUPPORTED;                  \
-  }
-  if (dt == VDN_F16) { VDN_TL_C(VDN_F16) } else if (dt == VDN_BF16) { VDN_TL_C(VDN_BF16) } else return VDN_EUNSUPPORTED;
-#undef VDN_TL_C
+#define VDN_TL(CPL_)                                                                                                     \
+  hipLaunchKernelGGL((temporal_last_kernel<DT, CPL_>), grid, block, 0, s, pool, slot_stride, tab, T, HW, c, pe_q, pe_k, \
+                     pe_v, scale, (typename Half<DT>::T*)out, (typename Half<DT>::T*)out_lo)
+  return with_half(dt, [&](auto t) -> int {
+    constexpr int DT = decltype(t)::value;
+    switch (c) {
+      case 64: VDN_TL(1); break;
+      case 128: VDN_TL(2); break;
+      case 192: VDN_TL(3); break;
+      case 256: VDN_TL(4); break;
+      case 384: VDN_TL(6); break;
+      case 512: VDN_TL(8); break;
+      case 768: VDN_TL(12); break;
+      case 1024: VDN_TL(16); break;
+      default: return VDN_EUNSUPPORTED;
+    }
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 #undef VDN_TL
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
 }

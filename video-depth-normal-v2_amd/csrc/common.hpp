@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/vdn.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -48,6 +49,17 @@ template <> struct Half<VDN_BF16> {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
   }
 };
+
+// ---- run-time launch choices -> compile-time template arguments: f is a generic lambda called with std::integral_constants
+template <int V> using IC = std::integral_constant<int, V>;
+// the 16-bit operand type of a call: f(IC<VDN_F16 | VDN_BF16>) -> status, with `typename Half<decltype(t)::value>::T` the type
+// behind the call's void pointers
+template <typename F>
+int with_half(int dt, F&& f) {
+  if (dt == VDN_F16) return f(IC<VDN_F16>{});
+  if (dt == VDN_BF16) return f(IC<VDN_BF16>{});
+  return VDN_EUNSUPPORTED;
+}
 
 // ReLU on 8 packed 16-bit floats held as 4 dwords, ONE instruction per dword: as signed 16-bit integers every value
 // with the sign bit set is negative, so v_pk_max_i16(x, 0) clears exactly those (fp16 and bf16 alike; -0 -> +0, +NaN and

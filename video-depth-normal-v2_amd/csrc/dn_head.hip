@@ -1,118 +1,11 @@
 // Depth + normal model (models/video_depth_model.py:64-119, models/video_depth_head_v2_sangyu.py:17-317):
-// the three kernels of its path that the shared GEMM / LayerNorm / resize kernels do not cover.
-//   dn_attn_kernel      grouped 8-head self-attention of the head's TransformerBlocks, head dim 12 / 24 / 48 / 96
+// the two kernels of its path that the shared GEMM / LayerNorm / resize / attention kernels do not cover (the grouped
+// 8-head self-attention of the head's TransformerBlocks, vdn_dn_attn, is lane_attn_kernel: lane_attn.hip).
 //   dn_prologue_kernel  trunk-feature sum + the .view reinterpretation + APE -> frame-major token rows
 //   dn_tail_kernel      conv3x3 48->3 + bias, bilinear resize, residual / ReLU, normal assembly
 #include "common.hpp"
 
 namespace {
-
-template <int DT> __device__ __forceinline__ float ld_h(const typename Half<DT>::T* p, size_t i) { return (float)p[i]; }
-
-template <int DT>
-__device__ __forceinline__ void st_split(typename Half<DT>::T* hi, typename Half<DT>::T* lo, size_t i, float v) {
-  using TT = typename Half<DT>::T;
-  const TT h = (TT)v;   // round to nearest; lo = nearest(v - hi): value = hi + lo to ~2^-21 (HL.from_float)
-  hi[i] = h;
-  if (lo) lo[i] = (TT)(v - (float)h);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// dn_attn_kernel — softmax(scale q k^T) v for every (sequence, head), q | k | v read from the packed in_proj rows.
-// A sequence is L rows of the token matrix: element j of sequence (g1, g0) is row g1 * s1 + g0 * s0 + j * estride.
-// One wave per (64 queries, sequence, head); each lane owns one query row and keeps q, the output accumulator and the
-// running (max, sum) of the online softmax in fp32 registers, so L is unbounded (3136 at level 0). Key / value tiles of
-// 64 rows are staged in LDS as fp32 (hi + lo already summed in split mode) and every lane reads the same key row
-// (an LDS broadcast). The head dim is a template argument, so 12 and 24 need no padding at all.
-constexpr int KT = 64;
-
-template <int DT, int DH>
-__global__ __launch_bounds__(64) void dn_attn_kernel(const typename Half<DT>::T* __restrict__ qkv,
-                                                     const typename Half<DT>::T* __restrict__ qkv_lo,
-                                                     typename Half<DT>::T* __restrict__ out, typename Half<DT>::T* __restrict__ out_lo,
-                                                     int C, int L, int estride, int n0, int s0, int s1, float sl2) {
-  __shared__ float ks[KT][DH];
-  __shared__ float vs[KT][DH];
-  const int lane = threadIdx.x;
-  const int head = blockIdx.y;
-  const int seq = blockIdx.z;
-  const size_t base = (size_t)(seq / n0) * s1 + (size_t)(seq % n0) * s0;
-  const size_t ld = 3 * (size_t)C;
-  const int qi = blockIdx.x * 64 + lane;
-  const bool active = qi < L;
-  float q[DH], o[DH];
-  {
-    const size_t r = (base + (size_t)(active ? qi : 0) * estride) * ld + head * DH;
-#pragma unroll
-    for (int e = 0; e < DH; ++e) {
-      float v = ld_h<DT>(qkv, r + e);
-      if (qkv_lo) v += ld_h<DT>(qkv_lo, r + e);
-      q[e] = v * sl2;   // scale and log2(e) folded into q: exp2 below
-      o[e] = 0.f;
-    }
-  }
-  float m = -INFINITY, l = 0.f;
-  for (int k0 = 0; k0 < L; k0 += KT) {
-    const int nk = min(KT, L - k0);
-    __syncthreads();
-    for (int i = lane; i < nk * DH; i += 64) {
-      const int j = i / DH, e = i - j * DH;
-      const size_t r = (base + (size_t)(k0 + j) * estride) * ld + head * DH + e;
-      float kv = ld_h<DT>(qkv, r + C), vv = ld_h<DT>(qkv, r + 2 * C);
-      if (qkv_lo) {
-        kv += ld_h<DT>(qkv_lo, r + C);
-        vv += ld_h<DT>(qkv_lo, r + 2 * C);
-      }
-      ks[j][e] = kv;
-      vs[j][e] = vv;
-    }
-    __syncthreads();
-    for (int j = 0; j < nk; ++j) {
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < DH; ++e) s = fmaf(q[e], ks[j][e], s);
-      if (s > m) {   // rescale the accumulator only when the running max moves
-        const float c = exp2f(m - s);
-        l *= c;
-#pragma unroll
-        for (int e = 0; e < DH; ++e) o[e] *= c;
-        m = s;
-      }
-      const float p = exp2f(s - m);
-      l += p;
-#pragma unroll
-      for (int e = 0; e < DH; ++e) o[e] = fmaf(p, vs[j][e], o[e]);
-    }
-  }
-  if (!active) return;
-  const float inv = 1.f / l;
-  const size_t r = (base + (size_t)qi * estride) * C + head * DH;
-#pragma unroll
-  for (int e = 0; e < DH; ++e) st_split<DT>(out, out_lo, r + e, o[e] * inv);
-}
-
-template <int DT, int DH>
-int attn_launch(const void* qkv, const void* qkv_lo, void* out, void* out_lo, int C, int heads, int L, int estride, int n0,
-                int s0, int nseq, int s1, float sl2, hipStream_t s) {
-  using TT = typename Half<DT>::T;
-  dim3 grid((L + 63) / 64, heads, nseq);
-  hipLaunchKernelGGL((dn_attn_kernel<DT, DH>), grid, dim3(64), 0, s, (const TT*)qkv, (const TT*)qkv_lo, (TT*)out, (TT*)out_lo,
-                     C, L, estride, n0, s0, s1, sl2);
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
-}
-
-template <int DT>
-int attn_dispatch(int dh, const void* qkv, const void* qkv_lo, void* out, void* out_lo, int C, int heads, int L, int estride,
-                  int n0, int s0, int nseq, int s1, float sl2, hipStream_t s) {
-  switch (dh) {
-    case 12: return attn_launch<DT, 12>(qkv, qkv_lo, out, out_lo, C, heads, L, estride, n0, s0, nseq, s1, sl2, s);
-    case 24: return attn_launch<DT, 24>(qkv, qkv_lo, out, out_lo, C, heads, L, estride, n0, s0, nseq, s1, sl2, s);
-    case 48: return attn_launch<DT, 48>(qkv, qkv_lo, out, out_lo, C, heads, L, estride, n0, s0, nseq, s1, sl2, s);
-    case 96: return attn_launch<DT, 96>(qkv, qkv_lo, out, out_lo, C, heads, L, estride, n0, s0, nseq, s1, sl2, s);
-  }
-  return VDN_EUNSUPPORTED;
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // dn_prologue_kernel — token[(f hw + p), c] = a[f][c hw + p] (+ b[f][c hw + p]) (+ ape[f % S][c]). Each frame's input
@@ -134,7 +27,7 @@ __global__ __launch_bounds__(256) void dn_prologue_kernel(const float* __restric
     if (ape) v += ape[(size_t)(f % S) * C + c];
     const size_t o = (f * hw + p) * C + c;
     if (out_f) out_f[o] = v;
-    if (out_h) st_split<DT>(out_h, out_lo, o, v);
+    if (out_h) store_half_nearest(out_h, out_lo, o, v);
   }
 }
 
@@ -220,25 +113,6 @@ __global__ __launch_bounds__(256) void dn_tail_kernel(const float* __restrict__ 
 
 }  // namespace
 
-extern "C" int vdn_dn_attn(int dt, const void* qkv, const void* qkv_lo, void* out, void* out_lo, int rows, int C, int heads,
-                           int L, int estride, int n0, int s0, int n1, int s1, float scale, vdn_stream stream) {
-  if (!qkv || !out || rows <= 0 || C <= 0 || heads <= 0 || C % heads || L <= 0 || estride <= 0 || n0 <= 0 || s0 < 0 ||
-      n1 <= 0 || s1 < 0)
-    return VDN_EINVAL;
-  if ((qkv_lo == nullptr) != (out_lo == nullptr)) return VDN_EINVAL;
-  const int64_t last = (int64_t)(n1 - 1) * s1 + (int64_t)(n0 - 1) * s0 + (int64_t)(L - 1) * estride;
-  if (last >= rows) return VDN_EINVAL;   // every row a sequence touches lies inside the [rows, 3C] / [rows, C] buffers
-  const int64_t nseq = (int64_t)n0 * n1;
-  if (nseq > 65535 || heads > 65535) return VDN_EUNSUPPORTED;   // grid.z / grid.y
-  const int dh = C / heads;
-  if (dh != 12 && dh != 24 && dh != 48 && dh != 96) return VDN_EUNSUPPORTED;
-  if (dt != VDN_F16 && dt != VDN_BF16) return VDN_EUNSUPPORTED;
-  const float sl2 = scale * 1.44269504088896340736f;
-  hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_F16) return attn_dispatch<VDN_F16>(dh, qkv, qkv_lo, out, out_lo, C, heads, L, estride, n0, s0, (int)nseq, s1, sl2, s);
-  return attn_dispatch<VDN_BF16>(dh, qkv, qkv_lo, out, out_lo, C, heads, L, estride, n0, s0, (int)nseq, s1, sl2, s);
-}
-
 extern "C" int vdn_dn_prologue(int dt, const float* a, const float* b, int frames, int C, int hw, const float* ape, int S,
                                float* out_f, void* out_h, void* out_lo, vdn_stream stream) {
   if (!a || frames <= 0 || C <= 0 || hw <= 0 || (!out_f && !out_h) || (out_lo && !out_h)) return VDN_EINVAL;
@@ -248,14 +122,13 @@ extern "C" int vdn_dn_prologue(int dt, const float* a, const float* b, int frame
   const size_t n = (size_t)frames * C * hw;
   const int blocks = (int)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384);
   hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_BF16)
-    hipLaunchKernelGGL(dn_prologue_kernel<VDN_BF16>, dim3(blocks), dim3(256), 0, s, a, b, ape, S, C, hw, n, out_f,
-                       (__bf16*)out_h, (__bf16*)out_lo);
-  else
-    hipLaunchKernelGGL(dn_prologue_kernel<VDN_F16>, dim3(blocks), dim3(256), 0, s, a, b, ape, S, C, hw, n, out_f,
-                       (_Float16*)out_h, (_Float16*)out_lo);
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
+  return with_half(out_h ? dt : VDN_F16, [&](auto t) -> int {   // without 16-bit planes dt selects nothing
+    using T = typename Half<decltype(t)::value>::T;
+    hipLaunchKernelGGL(dn_prologue_kernel<decltype(t)::value>, dim3(blocks), dim3(256), 0, s, a, b, ape, S, C, hw, n, out_f, (T*)out_h,
+                       (T*)out_lo);
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 }
 
 extern "C" int vdn_dn_tail(const float* x, int F, int IH, int IW, int Cin, const float* w, const float* bias, int OH, int OW,

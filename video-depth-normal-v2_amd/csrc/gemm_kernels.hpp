@@ -1334,8 +1334,7 @@ __global__ __launch_bounds__(512) void gemm_x3_p8_kernel(const vdn_gemm_desc p) 
   }  // tile loop
 }
 
-// ---- run-time launch choices -> compile-time template arguments: f is a generic lambda called with std::integral_constants
-template <int V> using IC = std::integral_constant<int, V>;
+// ---- run-time launch choices -> compile-time template arguments (IC and with_half: common.hpp)
 // AMODE of the 4-wave kernels: 0 plain, 1 conv, 2 conv + relu, 3 plain + relu
 template <typename F>
 void with_amode(const vdn_gemm_desc& d, F&& f) {

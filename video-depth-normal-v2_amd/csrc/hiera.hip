@@ -1,7 +1,7 @@
 // Hiera trunk (hiera_{tiny,small,base}_224 as the depth + normal model builds it, models/hiera_image_encoder.py:35,60):
-// the four kernels of its path that the shared GEMM / LayerNorm kernels do not cover.
+// the three kernels of its path that the shared GEMM / LayerNorm / attention kernels do not cover (its mask-unit / global
+// attention, vdn_hiera_attn, is lane_attn_kernel: lane_attn.hip).
 //   hiera_embed_kernel   7x7 stride-4 pad-3 patch gather -> GEMM rows, written in UNROLLED token order
-//   hiera_attn_kernel    mask-unit / global attention with the query max-pool fused on load, head dim 96
 //   hiera_pool_kernel    max over the 4 token groups of a width-changing block's residual
 //   hiera_reroll_kernel  unrolled tokens of a stage -> f32 NHWC map
 // Token order ("unroll"): the three nested stride-2 levels of the 56 x 56 grid are the leading digits of the token index,
@@ -15,8 +15,6 @@ namespace {
 constexpr int HI_SIDE = 56;    // tokens per side after the patch embedding of a 224 x 224 frame
 constexpr int HI_IMG = 224;
 constexpr int HI_K = 147;      // 3 * 7 * 7
-constexpr int HI_DH = 96;      // head dim at every stage
-constexpr int HI_KT = 64;      // key rows per LDS tile
 
 // token index u of a stage with n unroll levels left and side (7 << n) -> (y, x)
 __device__ __forceinline__ void unrolled_to_yx(int u, int n, int& y, int& x) {
@@ -76,79 +74,6 @@ __global__ __launch_bounds__(256) void hiera_embed_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// hiera_attn_kernel — softmax(scale q k^T) v for every (frame, window, head). Token t of window w of frame f is row
-// f*W*Lkv + t*W + w of qkv [rows, 3C] (columns q | k | v, each [heads][96]). With query stride qs, t = g*Lq + j and query j
-// is the element-wise max over its qs groups, taken while q is loaded; output row f*W*Lq + j*W + w of out [rows/qs, C].
-// One wave per (64 queries, head, frame x window); a lane owns one query row: q, the output accumulator and the running
-// (max, sum) of the softmax stay in fp32 registers. Key / value tiles of 64 rows are staged in LDS as fp32 (hi + lo summed)
-// and every lane reads the same key row (an LDS broadcast).
-template <int DT>
-__global__ __launch_bounds__(64) void hiera_attn_kernel(const typename Half<DT>::T* __restrict__ qkv,
-                                                        const typename Half<DT>::T* __restrict__ qkv_lo,
-                                                        typename Half<DT>::T* __restrict__ out, typename Half<DT>::T* __restrict__ out_lo,
-                                                        int C, int W, int Lkv, int qs, float sl2) {
-  __shared__ float ks[HI_KT][HI_DH];
-  __shared__ float vs[HI_KT][HI_DH];
-  const int lane = threadIdx.x;
-  const int head = blockIdx.y;
-  const int f = blockIdx.x / W, w = blockIdx.x - f * W;
-  const int Lq = Lkv / qs;
-  const size_t ld = 3 * (size_t)C;
-  const size_t in0 = (size_t)f * W * Lkv + w;    // row of token 0 of this window; token t is W rows further per step
-  const int qi = blockIdx.z * 64 + lane;
-  const bool active = qi < Lq;
-  float q[HI_DH], o[HI_DH];
-  {
-    const int j = active ? qi : 0;
-#pragma unroll
-    for (int e = 0; e < HI_DH; ++e) q[e] = -INFINITY;
-    for (int g = 0; g < qs; ++g) {
-      const size_t r = (in0 + (size_t)(g * Lq + j) * W) * ld + head * HI_DH;
-#pragma unroll
-      for (int e = 0; e < HI_DH; ++e) q[e] = fmaxf(q[e], load_half(qkv, qkv_lo, r + e));
-    }
-#pragma unroll
-    for (int e = 0; e < HI_DH; ++e) {
-      q[e] *= sl2;   // scale and log2(e) folded into q: exp2 below
-      o[e] = 0.f;
-    }
-  }
-  float m = -INFINITY, l = 0.f;
-  for (int k0 = 0; k0 < Lkv; k0 += HI_KT) {
-    const int nk = min(HI_KT, Lkv - k0);
-    __syncthreads();
-    for (int i = lane; i < nk * HI_DH; i += 64) {
-      const int j = i / HI_DH, e = i - j * HI_DH;
-      const size_t r = (in0 + (size_t)(k0 + j) * W) * ld + head * HI_DH + e;
-      ks[j][e] = load_half(qkv, qkv_lo, r + C);
-      vs[j][e] = load_half(qkv, qkv_lo, r + 2 * C);
-    }
-    __syncthreads();
-    for (int j = 0; j < nk; ++j) {
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < HI_DH; ++e) s = fmaf(q[e], ks[j][e], s);
-      if (s > m) {   // rescale the accumulator only when the running max moves
-        const float c = exp2f(m - s);
-        l *= c;
-#pragma unroll
-        for (int e = 0; e < HI_DH; ++e) o[e] *= c;
-        m = s;
-      }
-      const float p = exp2f(s - m);
-      l += p;
-#pragma unroll
-      for (int e = 0; e < HI_DH; ++e) o[e] = fmaf(p, vs[j][e], o[e]);
-    }
-  }
-  if (!active) return;
-  const float inv = 1.f / l;
-  const size_t r = ((size_t)f * W * Lq + (size_t)qi * W + w) * C + head * HI_DH;
-#pragma unroll
-  for (int e = 0; e < HI_DH; ++e) store_half_nearest(out, out_lo, r + e, o[e] * inv);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
 // hiera_pool_kernel — y[f, j, :] = max over g < 4 of x[f, g*n + j, :], 4 channels per thread.
 __global__ __launch_bounds__(256) void hiera_pool_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total4, int n,
                                                          int c4) {
@@ -193,38 +118,13 @@ extern "C" int vdn_hiera_embed(int dt, const float* img, void* rows, void* rows_
   if (ldk < HI_K || (ldk & 63) || ((uintptr_t)rows & 15) || ((uintptr_t)rows_lo & 15)) return VDN_EALIGN;
   if ((int64_t)frames * HI_SIDE * HI_SIDE > 0x7fffffff) return VDN_EUNSUPPORTED;   // rows are int32 in vdn_gemm
   const int g = grid_for((size_t)frames * HI_SIDE * HI_SIDE * (ldk >> 3));
-  hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_F16)
-    hipLaunchKernelGGL(hiera_embed_kernel<VDN_F16>, dim3(g), dim3(256), 0, s, img, (_Float16*)rows, (_Float16*)rows_lo, frames, ldk);
-  else if (dt == VDN_BF16)
-    hipLaunchKernelGGL(hiera_embed_kernel<VDN_BF16>, dim3(g), dim3(256), 0, s, img, (__bf16*)rows, (__bf16*)rows_lo, frames, ldk);
-  else
-    return VDN_EUNSUPPORTED;
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
-}
-
-extern "C" int vdn_hiera_attn(int dt, const void* qkv, const void* qkv_lo, void* out, void* out_lo, int frames, int heads, int W,
-                              int Lkv, int q_stride, float scale, vdn_stream stream) {
-  if (!qkv || !out || frames <= 0 || heads <= 0 || W <= 0 || Lkv <= 0 || q_stride <= 0 || Lkv % q_stride) return VDN_EINVAL;
-  if ((qkv_lo == nullptr) != (out_lo == nullptr)) return VDN_EINVAL;
-  if (dt != VDN_F16 && dt != VDN_BF16) return VDN_EUNSUPPORTED;
-  const int64_t rows = (int64_t)frames * W * Lkv;
-  if (rows * 3 * heads * HI_DH > ((int64_t)1 << 40) || (int64_t)frames * W > 0x7fffffff || heads > 65535) return VDN_EUNSUPPORTED;
-  const int Lq = Lkv / q_stride;
-  const dim3 grid((unsigned)(frames * W), heads, (Lq + 63) / 64);
-  if (grid.z > 65535) return VDN_EUNSUPPORTED;
-  const float sl2 = scale * 1.44269504088896340736f;
-  const int C = heads * HI_DH;
-  hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_F16)
-    hipLaunchKernelGGL(hiera_attn_kernel<VDN_F16>, grid, dim3(64), 0, s, (const _Float16*)qkv, (const _Float16*)qkv_lo, (_Float16*)out,
-                       (_Float16*)out_lo, C, W, Lkv, q_stride, sl2);
-  else
-    hipLaunchKernelGGL(hiera_attn_kernel<VDN_BF16>, grid, dim3(64), 0, s, (const __bf16*)qkv, (const __bf16*)qkv_lo, (__bf16*)out,
-                       (__bf16*)out_lo, C, W, Lkv, q_stride, sl2);
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
+  return with_half(dt, [&](auto t) -> int {
+    using T = typename Half<decltype(t)::value>::T;
+    hipLaunchKernelGGL(hiera_embed_kernel<decltype(t)::value>, dim3(g), dim3(256), 0, (hipStream_t)stream, img, (T*)rows, (T*)rows_lo,
+                       frames, ldk);
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 }
 
 extern "C" int vdn_hiera_pool(const float* x, float* y, int frames, int n, int C, vdn_stream stream) {

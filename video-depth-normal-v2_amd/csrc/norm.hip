@@ -368,21 +368,15 @@ extern "C" int vdn_groupnorm(int dt, const void* x, const void* x_lo, void* y, v
   const int pl = 256 / (C >> 3);
   const size_t lds = (size_t)pl * C * 2 * sizeof(float);
   const int chunks = (int)(((size_t)HW * (C >> 3) + 256 * 8 - 1) / (256 * 8));
-  if (dt == VDN_F16) {
-    hipLaunchKernelGGL(groupnorm_stats_kernel<VDN_F16>, dim3(F, nsplit), dim3(256), lds, s, (const _Float16*)x,
-                       (const _Float16*)x_lo, HW, C, groups, partial, nsplit);
-    hipLaunchKernelGGL(groupnorm_apply_kernel<VDN_F16>, dim3(F, chunks), dim3(256), 0, s, (const _Float16*)x,
-                       (const _Float16*)x_lo, (_Float16*)y, (_Float16*)y_lo, HW, C, groups, w, b, eps, partial, nsplit);
-  } else if (dt == VDN_BF16) {
-    hipLaunchKernelGGL(groupnorm_stats_kernel<VDN_BF16>, dim3(F, nsplit), dim3(256), lds, s, (const __bf16*)x,
-                       (const __bf16*)x_lo, HW, C, groups, partial, nsplit);
-    hipLaunchKernelGGL(groupnorm_apply_kernel<VDN_BF16>, dim3(F, chunks), dim3(256), 0, s, (const __bf16*)x,
-                       (const __bf16*)x_lo, (__bf16*)y, (__bf16*)y_lo, HW, C, groups, w, b, eps, partial, nsplit);
-  } else {
-    return VDN_EUNSUPPORTED;
-  }
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
+  return with_half(dt, [&](auto t) -> int {
+    using T = typename Half<decltype(t)::value>::T;
+    hipLaunchKernelGGL(groupnorm_stats_kernel<decltype(t)::value>, dim3(F, nsplit), dim3(256), lds, s, (const T*)x, (const T*)x_lo, HW,
+                       C, groups, partial, nsplit);
+    hipLaunchKernelGGL(groupnorm_apply_kernel<decltype(t)::value>, dim3(F, chunks), dim3(256), 0, s, (const T*)x, (const T*)x_lo, (T*)y,
+                       (T*)y_lo, HW, C, groups, w, b, eps, partial, nsplit);
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 }
 
 extern "C" int vdn_add_vec(const float* x, const float* vec, float alpha, float* y, int rows, int C,
@@ -404,16 +398,13 @@ extern "C" int vdn_addtab_cast(int dt, const float* x, const float* tab, int tab
   const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
   hipStream_t s = (hipStream_t)stream;
   if (!tab) { tab_div = 1; tab_mod = 1; }
-  if (dt == VDN_F16)
-    hipLaunchKernelGGL(addtab_cast_kernel<VDN_F16>, dim3(blocks), dim3(256), 0, s, x, tab, tab_div, tab_mod, (_Float16*)y,
-                       (_Float16*)y_lo, rows, C);
-  else if (dt == VDN_BF16)
-    hipLaunchKernelGGL(addtab_cast_kernel<VDN_BF16>, dim3(blocks), dim3(256), 0, s, x, tab, tab_div, tab_mod, (__bf16*)y,
-                       (__bf16*)y_lo, rows, C);
-  else
-    return VDN_EUNSUPPORTED;
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
+  return with_half(dt, [&](auto t) -> int {
+    using T = typename Half<decltype(t)::value>::T;
+    hipLaunchKernelGGL(addtab_cast_kernel<decltype(t)::value>, dim3(blocks), dim3(256), 0, s, x, tab, tab_div, tab_mod, (T*)y, (T*)y_lo,
+                       rows, C);
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 }
 
 extern "C" int vdn_cast(const void* x, int x_dt, void* y, int y_dt, size_t n, vdn_stream stream) {

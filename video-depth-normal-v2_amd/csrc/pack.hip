@@ -112,14 +112,12 @@ extern "C" int vdn_pack_weight(int dt, int kind, const float* w, int d0, int d1,
   const size_t total = (size_t)a.rows * ldb;
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_F16)
-    hipLaunchKernelGGL(pack_kernel<VDN_F16>, dim3(blocks), dim3(256), 0, s, w, (_Float16*)hi, (_Float16*)lo, a);
-  else if (dt == VDN_BF16)
-    hipLaunchKernelGGL(pack_kernel<VDN_BF16>, dim3(blocks), dim3(256), 0, s, w, (__bf16*)hi, (__bf16*)lo, a);
-  else
-    return VDN_EUNSUPPORTED;
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
+  return with_half(dt, [&](auto t) -> int {
+    using T = typename Half<decltype(t)::value>::T;
+    hipLaunchKernelGGL(pack_kernel<decltype(t)::value>, dim3(blocks), dim3(256), 0, s, w, (T*)hi, (T*)lo, a);
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 }
 
 extern "C" int vdn_pack_bias(int kind, const float* b, int d0, int d1, int d2, float* out, vdn_stream stream) {

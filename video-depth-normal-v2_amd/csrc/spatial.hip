@@ -495,16 +495,13 @@ extern "C" int vdn_upsample_bilinear(int dt, const void* x, const void* x_lo, vo
   if ((C & 7) || (((uintptr_t)x | (uintptr_t)y) & 15)) return VDN_EALIGN;
   const int g = grid_for((size_t)B * OH * OW * (C >> 3), 16384);
   hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_F16)
-    hipLaunchKernelGGL(upsample_kernel<VDN_F16>, dim3(g), dim3(256), 0, s, (const _Float16*)x, (const _Float16*)x_lo,
-                       (_Float16*)y, (_Float16*)y_lo, B, IH, IW, OH, OW, C);
-  else if (dt == VDN_BF16)
-    hipLaunchKernelGGL(upsample_kernel<VDN_BF16>, dim3(g), dim3(256), 0, s, (const __bf16*)x, (const __bf16*)x_lo,
-                       (__bf16*)y, (__bf16*)y_lo, B, IH, IW, OH, OW, C);
-  else
-    return VDN_EUNSUPPORTED;
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
+  return with_half(dt, [&](auto t) -> int {
+    using T = typename Half<decltype(t)::value>::T;
+    hipLaunchKernelGGL(upsample_kernel<decltype(t)::value>, dim3(g), dim3(256), 0, s, (const T*)x, (const T*)x_lo, (T*)y, (T*)y_lo, B,
+                       IH, IW, OH, OW, C);
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 }
 
 extern "C" int vdn_upsample_bilinear_f32(const float* x, float* y, int B, int IH, int IW, int OH, int OW, int relu,
@@ -554,16 +551,12 @@ extern "C" int vdn_patchify(int dt, const float* img, void* rows, void* rows_lo,
   if (ldk < 588 || (ldk & 63) || ((uintptr_t)rows & 15)) return VDN_EALIGN;
   const int g = grid_for((size_t)B * (H / 14) * (W / 14) * (ldk >> 3), 8192);
   hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_F16)
-    hipLaunchKernelGGL(patchify_kernel<VDN_F16>, dim3(g), dim3(256), 0, s, img, (_Float16*)rows, (_Float16*)rows_lo, B, H, W,
-                       ldk);
-  else if (dt == VDN_BF16)
-    hipLaunchKernelGGL(patchify_kernel<VDN_BF16>, dim3(g), dim3(256), 0, s, img, (__bf16*)rows, (__bf16*)rows_lo, B, H, W,
-                       ldk);
-  else
-    return VDN_EUNSUPPORTED;
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
+  return with_half(dt, [&](auto t) -> int {
+    using T = typename Half<decltype(t)::value>::T;
+    hipLaunchKernelGGL(patchify_kernel<decltype(t)::value>, dim3(g), dim3(256), 0, s, img, (T*)rows, (T*)rows_lo, B, H, W, ldk);
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 }
 
 extern "C" int vdn_fill_row(float* x, const float* vec, int B, int rows_per_b, int row, int C, vdn_stream stream) {
@@ -605,16 +598,13 @@ extern "C" int vdn_head_out(int dt, const void* feat, const void* feat_lo, const
   if ((C & 7) || ((uintptr_t)feat & 15)) return VDN_EALIGN;
   const int g = grid_for((size_t)M, 8192);
   hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_F16)
-    hipLaunchKernelGGL(head_out_kernel<VDN_F16>, dim3(g), dim3(256), 0, s, (const _Float16*)feat,
-                       (const _Float16*)feat_lo, w, bias, depth, M, C, relu);
-  else if (dt == VDN_BF16)
-    hipLaunchKernelGGL(head_out_kernel<VDN_BF16>, dim3(g), dim3(256), 0, s, (const __bf16*)feat,
-                       (const __bf16*)feat_lo, w, bias, depth, M, C, relu);
-  else
-    return VDN_EUNSUPPORTED;
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
+  return with_half(dt, [&](auto t) -> int {
+    using T = typename Half<decltype(t)::value>::T;
+    hipLaunchKernelGGL(head_out_kernel<decltype(t)::value>, dim3(g), dim3(256), 0, s, (const T*)feat, (const T*)feat_lo, w, bias, depth,
+                       M, C, relu);
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 }
 
 extern "C" int vdn_mask_down1(const float* depth, float* out, int B, int H, int W, int OH, int OW, const float* w,

@@ -252,14 +252,11 @@ extern "C" int vdn_depth_tail(int dt, const float* x, int B, int IH, int IW, int
   if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)w_lo | (uintptr_t)bias2 | (uintptr_t)w1) & 15) return VDN_EALIGN;
   const int tiles = B * ((OH + TH - 1) / TH) * ((OW + TW - 1) / TW);
   hipStream_t s = (hipStream_t)stream;
-  if (dt == VDN_F16)
-    hipLaunchKernelGGL(depth_tail_kernel<VDN_F16>, dim3(tiles), dim3(256), 2 * PLANE + 2 * SPLANE, s, x, B,
-                       IH, IW, C, (const _Float16*)w, (const _Float16*)w_lo, ldb, bias2, w1, b1, depth, OH, OW, relu);
-  else if (dt == VDN_BF16)
-    hipLaunchKernelGGL(depth_tail_kernel<VDN_BF16>, dim3(tiles), dim3(256), 2 * PLANE + 2 * SPLANE, s, x, B, IH,
-                       IW, C, (const __bf16*)w, (const __bf16*)w_lo, ldb, bias2, w1, b1, depth, OH, OW, relu);
-  else
-    return VDN_EUNSUPPORTED;
-  VDN_CHECK_LAUNCH();
-  return VDN_OK;
+  return with_half(dt, [&](auto t) -> int {
+    using T = typename Half<decltype(t)::value>::T;
+    hipLaunchKernelGGL(depth_tail_kernel<decltype(t)::value>, dim3(tiles), dim3(256), 2 * PLANE + 2 * SPLANE, s, x, B, IH, IW, C,
+                       (const T*)w, (const T*)w_lo, ldb, bias2, w1, b1, depth, OH, OW, relu);
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  });
 }

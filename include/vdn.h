@@ -340,7 +340,7 @@ int vdn_stitch_fit(const float* pred, const float* target, size_t n, void* works
 int vdn_stitch_apply(const float* window, const float* coef, float* out_tail, float* out_new, float* ref1, size_t hw,
                      int T, int align_len, int overlap, int ref_frame, vdn_stream stream);
 
-/* Depth-refiner wrappers v4 / v5 (models/video_depth_model_v5.py:63-87,160-192, models/video_depth_model_v4.py:117-148,
+/* Depth-refiner wrappers v2 .. v5 (models/video_depth_model_v5.py:63-87,160-192, models/video_depth_model_v4.py:117-148,
  * utils/normal_utils.py:4-51). f32 throughout, frames are [frames, n = H*W] row-major.
  * vdn_frame_median  — median[f] = torch.quantile(x[f], 0.5) (linear interpolation), exact radix select;
  *                     workspace = vdn_frame_median_workspace_bytes(frames).
@@ -348,7 +348,19 @@ int vdn_stitch_apply(const float* window, const float* coef, float* out_tail, fl
  *                     (GlobalScaleHead: quantile pool -> 1x1 conv -> TanhToExp); scale_out[f] = s_f (may be NULL).
  * vdn_refine_pack   — encoder input [frames,3,H,W] = (d, nx, ny); normals != 0: Sobel/8 on a reflect-padded map,
  *                     n = (-Ix,-Iy,1)/sqrt(Ix^2+Iy^2+1+1e-8); normals == 0: d broadcast to 3 channels.
- * vdn_refine_finish — out = (scaled + (w * depth + b)) * max_depth (residual != 0) or depth * max_depth.           */
+ * vdn_refine_finish — out = (scaled + (w * depth + b)) * max_depth (residual != 0) or depth * max_depth.
+ * The v3 wrapper (models/video_depth_model_v3.py:167-206) is the same four with max_depth = 65535 in front and
+ * max_depth = 1 in vdn_refine_finish (its result stays normalised); v2 (models/video_depth_model_v2.py:75-100) has no
+ * scale head and its own finish:
+ * vdn_refine_normalize — out = x / max_depth over n floats, the correctly rounded fp32 division vdn_refine_scale applies
+ *                     (video_depth_model_v2.py:77). An entry of its own rather than a mode of vdn_refine_scale: that one
+ *                     reads a per-frame median, and v2 has none to compute.
+ * vdn_refine_mix    — out = relu(a2 * relu(a0 * depth + a1 * x + c0) + c1) over n floats: final_res of
+ *                     video_depth_model_v2.py:64-72,96-97 (Conv2d(2,1,1) - BatchNorm2d - ReLU - Conv2d(1,1,1) -
+ *                     BatchNorm2d - ReLU on stack([depth, x])) with the eval-mode BatchNorms folded into five scalars by
+ *                     the caller. relu is torch.relu's: NaN in, NaN out.
+ * Both take any n >= 1 and any 4-byte-aligned pointers (16 bytes per lane where the arrays' alignments agree, one
+ * float per lane at the ends and where they do not); out must not overlap an input.                               */
 size_t vdn_frame_median_workspace_bytes(int frames);
 int vdn_frame_median(const float* x, int frames, size_t n, float* median, void* workspace, vdn_stream stream);
 int vdn_refine_scale(const float* x, const float* median, int frames, size_t n, float w, float b, float max_log_scale,
@@ -356,6 +368,9 @@ int vdn_refine_scale(const float* x, const float* median, int frames, size_t n, 
 int vdn_refine_pack(const float* d, float* out, int frames, int H, int W, int normals, vdn_stream stream);
 int vdn_refine_finish(const float* scaled, const float* depth, float w, float b, float max_depth, int residual, float* out,
                       size_t n, vdn_stream stream);
+int vdn_refine_normalize(const float* x, float max_depth, float* out, size_t n, vdn_stream stream);
+int vdn_refine_mix(const float* depth, const float* x, float a0, float a1, float c0, float a2, float c1, float* out, size_t n,
+                   vdn_stream stream);
 
 /* Fused depth tail (depth_anything_v2/dpt.py:146-151; video_depth_anything/dpt_temporal.py:106-111 runs the same ops
  * in micro-batches): bilinear resize (align_corners=True) of the fp32 NHWC map x [B, IH, IW, C] (output_conv1's result,

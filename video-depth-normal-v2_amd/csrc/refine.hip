@@ -1,11 +1,15 @@
-// Pre/post-processing kernels of the depth-refiner wrappers (models/video_depth_model_v5.py:63-87,160-192,
-// models/video_depth_model_v4.py:117-148, utils/normal_utils.py:4-51):
+// Pre/post-processing kernels of the depth-refiner wrappers v2 .. v5 (models/video_depth_model_v5.py:63-87,160-192,
+// models/video_depth_model_v4.py:117-148, models/video_depth_model_v3.py:167-206, models/video_depth_model_v2.py:75-100,
+// utils/normal_utils.py:4-51):
 //   vdn_frame_median  — torch.quantile(x, 0.5) per frame (linear interpolation between the two middle order
 //                       statistics) as an exact 3-pass radix select on order-preserving keys (integer atomics:
 //                       deterministic), both ranks in the same passes;
 //   vdn_refine_scale  — x / max_depth * exp(tanh(w * median / max_depth + b) * max_log_scale)  (GlobalScaleHead);
 //   vdn_refine_pack   — network input [F,3,H,W] = (d, nx, ny) with n = (-Ix, -Iy, 1)/|.|, Sobel/8 on a reflect pad;
-//   vdn_refine_finish — (scaled + (w * depth + b)) * max_depth  (scalar 1x1 'ZeroConv' shift + residual).
+//   vdn_refine_finish — (scaled + (w * depth + b)) * max_depth  (scalar 1x1 'ZeroConv' shift + residual; v3: max_depth 1);
+//   vdn_refine_normalize — x / max_depth, a true fp32 division (v2 has no scale head, so no median is computed for it);
+//   vdn_refine_mix    — relu(a2 * relu(a0 * depth + a1 * x + c0) + c1): v2's final_res (Conv2d(2,1,1) - BatchNorm - ReLU -
+//                       Conv2d(1,1,1) - BatchNorm - ReLU) with the eval-mode BatchNorms folded on the host, NaN in -> NaN out.
 // All one pass over HBM.
 #include "common.hpp"
 
@@ -143,9 +147,67 @@ __global__ __launch_bounds__(256) void refine_finish_kernel(const float* __restr
   }
 }
 
+// v2's folded final_res on one pixel; the comparison (not fmaxf) keeps torch.relu's NaN: NaN < 0 is false
+struct MixOp {
+  static constexpr int kInputs = 2;
+  float a0, a1, c0, a2, c1;
+  __device__ __forceinline__ float relu(float v) const { return v < 0.f ? 0.f : v; }
+  __device__ __forceinline__ float operator()(float d, float x) const {
+    return relu(fmaf(a2, relu(fmaf(a0, d, fmaf(a1, x, c0))), c1));
+  }
+};
+
+struct NormalizeOp {
+  static constexpr int kInputs = 1;
+  float max_depth;
+  __device__ __forceinline__ float operator()(float x, float) const { return __fdiv_rn(x, max_depth); }
+};
+
+// out[i] = op(a[i], b[i]) over n floats. Elements [head, head + 4 nvec) are 16-byte aligned in every array and go as
+// float4 per lane; the < 4 in front and the < 4 behind go one float per lane. Arrays whose offsets inside a 16-byte line
+// differ get nvec = 0 from the host: everything is the scalar part then.
+template <class Op>
+__global__ __launch_bounds__(256) void elementwise_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                          float* __restrict__ out, size_t n, size_t head, size_t nvec, Op op) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  const float4* a4 = reinterpret_cast<const float4*>(a + head);
+  const float4* b4 = reinterpret_cast<const float4*>(b + head);
+  float4* o4 = reinterpret_cast<float4*>(out + head);
+  for (size_t i = tid; i < nvec; i += stride) {
+    const float4 va = a4[i];
+    float4 vb = va;
+    if constexpr (Op::kInputs == 2) vb = b4[i];
+    o4[i] = make_float4(op(va.x, vb.x), op(va.y, vb.y), op(va.z, vb.z), op(va.w, vb.w));
+  }
+  const size_t rest = n - 4 * nvec;
+  for (size_t i = tid; i < rest; i += stride) {
+    const size_t j = i < head ? i : i + 4 * nvec;
+    float vb = 0.f;
+    if constexpr (Op::kInputs == 2) vb = b[j];
+    out[j] = op(a[j], vb);
+  }
+}
+
 inline unsigned blocks_for(size_t n, unsigned cap) {
   const size_t b = (n + 255) / 256;
   return (unsigned)(b < cap ? (b ? b : 1) : cap);
+}
+
+template <class Op>
+int launch_elementwise(const float* a, const float* b, float* out, size_t n, Op op, vdn_stream stream) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)(b ? b : a), po = (uintptr_t)out;
+  if ((pa | pb | po) & 3) return VDN_EINVAL;
+  size_t head = 0, nvec = 0;
+  if ((pa & 15) == (pb & 15) && (pa & 15) == (po & 15)) {
+    head = ((16 - (pa & 15)) & 15) / 4;
+    if (head > n) head = n;
+    nvec = (n - head) / 4;
+  }
+  const size_t lanes = nvec > n - 4 * nvec ? nvec : n - 4 * nvec;
+  hipLaunchKernelGGL(elementwise_kernel<Op>, dim3(blocks_for(lanes, 16384)), dim3(256), 0, (hipStream_t)stream, a, b ? b : a, out, n,
+                     head, nvec, op);
+  VDN_CHECK_LAUNCH();
+  return VDN_OK;
 }
 
 }  // namespace
@@ -197,4 +259,15 @@ extern "C" int vdn_refine_finish(const float* scaled, const float* depth, float 
                      max_depth, residual, out, n);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
+}
+
+extern "C" int vdn_refine_normalize(const float* x, float max_depth, float* out, size_t n, vdn_stream stream) {
+  if (!x || !out || n == 0 || !(max_depth > 0.f)) return VDN_EINVAL;
+  return launch_elementwise(x, nullptr, out, n, NormalizeOp{max_depth}, stream);
+}
+
+extern "C" int vdn_refine_mix(const float* depth, const float* x, float a0, float a1, float c0, float a2, float c1, float* out,
+                              size_t n, vdn_stream stream) {
+  if (!depth || !x || !out || n == 0) return VDN_EINVAL;
+  return launch_elementwise(depth, x, out, n, MixOp{a0, a1, c0, a2, c1}, stream);
 }

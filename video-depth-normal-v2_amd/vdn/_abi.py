@@ -109,6 +109,8 @@ EXPORTS = {
     "vdn_refine_scale": (C.c_int, [fp, fp, C.c_int, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, fp, fp, vp]),
     "vdn_refine_pack": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_refine_finish": (C.c_int, [fp, fp, C.c_float, C.c_float, C.c_float, C.c_int, fp, C.c_size_t, vp]),
+    "vdn_refine_normalize": (C.c_int, [fp, C.c_float, fp, C.c_size_t, vp]),
+    "vdn_refine_mix": (C.c_int, [fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, fp, C.c_size_t, vp]),
     "vdn_dn_attn": (C.c_int, [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_float, vp]),
     "vdn_dn_prologue": (C.c_int, [C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, vp, vp, vp]),

@@ -375,6 +375,17 @@ class Runtime:
         self._launch(abi.lib.vdn_refine_finish, self._p(scaled), depth.data_ptr(), w, b, max_depth, int(residual), out.data_ptr(),
                      depth.numel())
 
+    def refine_normalize(self, x, max_depth: float, out):
+        """out = x / max_depth (true fp32 division) for contiguous f32 tensors of equal size."""
+        assert x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype == torch.float32 and out.numel() == x.numel()
+        self._launch(abi.lib.vdn_refine_normalize, x.data_ptr(), max_depth, out.data_ptr(), x.numel())
+
+    def refine_mix(self, depth, x, a0: float, a1: float, c0: float, a2: float, c1: float, out):
+        """out = relu(a2 * relu(a0 * depth + a1 * x + c0) + c1): the v2 refiner's final_res, BatchNorms folded (refiner.fold_final_res)."""
+        for t in (depth, x, out):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == depth.numel()
+        self._launch(abi.lib.vdn_refine_mix, depth.data_ptr(), x.data_ptr(), a0, a1, c0, a2, c1, out.data_ptr(), depth.numel())
+
     def dn_attn(self, qkv, out, rows: int, Cn: int, heads: int, L: int, estride: int, n0: int, s0: int, n1: int, s1: int,
                 scale: float):
         """Grouped self-attention of the depth + normal head (include/vdn.h vdn_dn_attn): qkv [rows, 3C], out [rows, C]."""

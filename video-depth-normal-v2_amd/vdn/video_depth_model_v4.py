@@ -4,3 +4,4 @@ from .refiner import _DepthRefiner
 
 class VideoDepthAnything(_DepthRefiner):
     VERSION = 4
+    NET_HW = None

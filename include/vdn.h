@@ -340,6 +340,44 @@ int vdn_stitch_fit(const float* pred, const float* target, size_t n, void* works
 int vdn_stitch_apply(const float* window, const float* coef, float* out_tail, float* out_new, float* ref1, size_t hw,
                      int T, int align_len, int overlap, int ref_frame, vdn_stream stream);
 
+/* Clip evaluation on the device: eval_single_by_data of eval_depthcrafter/eval.py:55-151 with the seven eval_metrics of
+ * eval_depthcrafter/metric.py, for pred f32 [frames, H, W], gt f32 [frames, H, W] and an optional mask u8 [frames, H, W]
+ * (NULL = all ones; non-zero = use). valid = gt > dmin && gt < dmax && mask, compared in float32 as numpy does for a
+ * float32 gt. What the reference computes in float64 is fp64 here; sums have a fixed order and use no atomics, so two runs
+ * give the same bits. Pointers need only their type's alignment (pred / gt 4 bytes, workspace / coef / out 8 bytes):
+ * loads are one element per lane. VDN_EINVAL: a null pointer (mask excepted), a size <= 0, dmin >= dmax (or a NaN bound),
+ * an unknown domain or TGM mode.
+ * vdn_eval_fit     — coef[0..1] = (scale, shift) minimising sum over valid pixels of (scale * p + shift - t)^2,
+ *                    p = max((double)pred, dmin), t = gt (VDN_EVAL_DISP) or 1 / ((double)gt + 1e-8) (VDN_EVAL_DEPTH);
+ *                    closed form on the normal equations (eval.py:81-107 solves the same system by SVD). When every
+ *                    valid p is the same value c the system has rank 1 and the result is lstsq's minimum-norm solution
+ *                    (c, 1) * mean(t) / (c * c + 1); without any valid pixel coef = (NaN, NaN). Also leaves the per-frame
+ *                    valid counts in `workspace` for vdn_eval_metrics.
+ * vdn_eval_metrics — must follow vdn_eval_fit on the same pred / gt / mask / bounds / workspace. a = clip(aligned, dmin,
+ *                    dmax) with aligned = max(scale * p + shift, dmin) (separate multiply and add roundings), inverted
+ *                    first for VDN_EVAL_DEPTH. Per frame with a valid pixel: |a - g|, |a - g| / g, (a - g)^2 and the counts
+ *                    of max(a / g, g / a) < 1.25, 1.25^2, 1.25^3 over its valid pixels; frames without one are dropped.
+ *                    out[0..6] = abs_relative_difference, delta1_acc, temporal_gradient_matching_error, abs_difference,
+ *                    rmse_linear, delta2_acc, delta3_acc: the mean over the kept frames of the per-frame quotient. The
+ *                    three delta values are float32 quotients and a float32 mean (summed in frame order), widened.
+ *                    TGM = mean of sum |da - dg| / count over valid[first] && dg < 0.05f, dg a float32 difference of gt:
+ *                    VDN_EVAL_TGM_ROWS   the pair is (y, y + 1) of one frame, per kept frame over (H - 1) x W — what the
+ *                                        reference computes, since it slices dim 1 of [T, H, W] tensors;
+ *                    VDN_EVAL_TGM_FRAMES the pair is a kept frame and the next kept one, per pair over H x W —
+ *                                        metric.py:3-33 as written for [B, S, H, W].
+ *                    0 / 0 stays NaN (a kept frame with an empty TGM mask, H == 1, no kept frame).
+ * vdn_resize_bilinear_hp — f32 [frames, IH, IW] -> [frames, OH, OW], half-pixel centres (align_corners=False, the
+ *                    geometry of cv2.resize's default INTER_LINEAR, eval.py:42-53), no antialiasing.              */
+enum vdn_eval_domain { VDN_EVAL_DEPTH = 0, VDN_EVAL_DISP = 1 };
+enum vdn_eval_tgm { VDN_EVAL_TGM_ROWS = 0, VDN_EVAL_TGM_FRAMES = 1 };
+size_t vdn_eval_workspace_bytes(int frames);
+int vdn_eval_fit(const float* pred, const float* gt, const uint8_t* mask, int frames, size_t hw, double dmin, double dmax,
+                 int domain, void* workspace, double* coef, vdn_stream stream);
+int vdn_eval_metrics(const float* pred, const float* gt, const uint8_t* mask, int frames, int H, int W, double dmin,
+                     double dmax, int domain, int tgm, const double* coef, void* workspace, double* out,
+                     vdn_stream stream);
+int vdn_resize_bilinear_hp(const float* x, float* y, int frames, int IH, int IW, int OH, int OW, vdn_stream stream);
+
 /* Depth-refiner wrappers v2 .. v5 (models/video_depth_model_v5.py:63-87,160-192, models/video_depth_model_v4.py:117-148,
  * utils/normal_utils.py:4-51). f32 throughout, frames are [frames, n = H*W] row-major.
  * vdn_frame_median  — median[f] = torch.quantile(x[f], 0.5) (linear interpolation), exact radix select;

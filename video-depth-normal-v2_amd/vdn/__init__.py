@@ -27,4 +27,7 @@ def __getattr__(name):
     if name == "VideoDepthEstimationModel":
         from .video_depth_model import VideoDepthEstimationModel
         return VideoDepthEstimationModel
+    if name == "eval":   # clip evaluation metrics on the device (vdn/eval.py)
+        import importlib
+        return importlib.import_module(".eval", __name__)
     raise AttributeError(name)

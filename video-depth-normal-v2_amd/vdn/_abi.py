@@ -12,6 +12,8 @@ F16, BF16, F32, NONE = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SILU = 0, 1, 2, 3
 A_PLAIN, A_CONV3X3 = 0, 1
 ST_PLAIN, ST_HEADS, ST_CONVT, ST_GEGLU = 0, 1, 2, 3
+EVAL_DEPTH, EVAL_DISP = 0, 1
+EVAL_TGM_ROWS, EVAL_TGM_FRAMES = 0, 1
 PACK_LINEAR, PACK_CONV3X3, PACK_CONV3X3_TAPS, PACK_CONVT, PACK_GEGLU, PACK_ROPE = 0, 1, 2, 3, 4, 5
 
 i32, vp, fp = C.c_int32, C.c_void_p, C.c_void_p
@@ -122,6 +124,10 @@ EXPORTS = {
     "vdn_stitch_workspace_bytes": (C.c_size_t, []),
     "vdn_stitch_fit": (C.c_int, [fp, fp, C.c_size_t, vp, fp, vp]),
     "vdn_stitch_apply": (C.c_int, [fp, fp, fp, fp, fp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_eval_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "vdn_eval_fit": (C.c_int, [fp, fp, vp, C.c_int, C.c_size_t, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
+    "vdn_eval_metrics": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "vdn_resize_bilinear_hp": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_sizeof_gemm_desc": (C.c_size_t, []),
     "vdn_offsetof_gemm_zeros": (C.c_size_t, []),
     "vdn_offsetof_gemm_res2_lo": (C.c_size_t, []),

@@ -356,6 +356,37 @@ class Runtime:
         self._launch(abi.lib.vdn_stitch_apply, window.data_ptr(), coef.data_ptr(), out_tail.data_ptr(), out_new.data_ptr(),
                      ref1.data_ptr(), hw, T, align_len, overlap, ref_frame)
 
+    def _eval_args(self, pred, gt, mask):
+        T = pred.shape[0]
+        for t in (pred, gt):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.dim() == 3 and t.shape == pred.shape
+        if mask is not None:
+            assert mask.is_contiguous() and mask.dtype in (torch.uint8, torch.bool) and mask.shape == pred.shape
+        ws = self.buf("eval_ws", (abi.lib.vdn_eval_workspace_bytes(T) // 8,), torch.float64)
+        return T, ws
+
+    def eval_fit(self, pred, gt, mask, dmin: float, dmax: float, domain: int, coef: torch.Tensor):
+        """coef[0:2] (float64) <- masked least-squares (scale, shift) of the clip evaluation (include/vdn.h vdn_eval_fit)."""
+        T, ws = self._eval_args(pred, gt, mask)
+        assert coef.dtype == torch.float64 and coef.numel() >= 2
+        self._launch(abi.lib.vdn_eval_fit, pred.data_ptr(), gt.data_ptr(), self._p(mask), T, pred[0].numel(), dmin, dmax,
+                     domain, ws.data_ptr(), coef.data_ptr())
+
+    def eval_metrics(self, pred, gt, mask, dmin: float, dmax: float, domain: int, tgm: int, coef: torch.Tensor,
+                     out: torch.Tensor):
+        """out[0:7] (float64) <- the seven clip metrics; follows eval_fit on the same arguments (vdn_eval_metrics)."""
+        T, ws = self._eval_args(pred, gt, mask)
+        assert coef.dtype == torch.float64 and out.dtype == torch.float64 and out.numel() >= 7
+        self._launch(abi.lib.vdn_eval_metrics, pred.data_ptr(), gt.data_ptr(), self._p(mask), T, pred.shape[1], pred.shape[2],
+                     dmin, dmax, domain, tgm, coef.data_ptr(), ws.data_ptr(), out.data_ptr())
+
+    def resize_bilinear_hp(self, x: torch.Tensor, out: torch.Tensor):
+        """out [T, OH, OW] <- half-pixel (align_corners=False) bilinear resize of f32 x [T, IH, IW]."""
+        assert x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype == torch.float32
+        assert x.dim() == 3 and out.dim() == 3 and x.shape[0] == out.shape[0]
+        self._launch(abi.lib.vdn_resize_bilinear_hp, x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], x.shape[2],
+                     out.shape[1], out.shape[2])
+
     def frame_median(self, x: torch.Tensor, median: torch.Tensor):
         """median[f] = torch.quantile(x[f], 0.5) for f32 x [F, ...] (exact radix select on the device)."""
         F = x.shape[0]

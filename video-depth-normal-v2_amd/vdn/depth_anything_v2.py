@@ -80,7 +80,10 @@ class _EngineOwner(nn.Module):
         """u8 [n,h,w,3] on the device (RGB, or BGR with swap_rb) -> f32 [n,3,H,W]: /255, Resize(lower_bound, multiple of 14,
         cubic) + NormalizeImage + PrepareForNet (util/transform.py:109-148) in ONE launch (vdn_preprocess). The cubic kernel
         is the A=-0.75 half-pixel one cv2.INTER_CUBIC uses; cv2 itself is absent offline so this step is parity-unpinned
-        (SURVEY.md §8c)."""
+        against cv2. What is compared: the device output against oracle.ref_cpu.resize_cubic (cv2's published
+        algorithm in float64) + float64 normalisation, on non-square, down-scaled, wide and 1080p frames with a bar of fp32
+        arithmetic alone (tests/test_gpu_geometry.py::test_preprocess_against_fp64_oracle; image2tensor is held to the same bar in
+        tests/test_gpu_e2e.py::test_image2tensor_and_infer_image_against_oracle)."""
         n, h, w, _ = frames_u8.shape
         nw, nh = util.get_size(w, h, input_size)
         return rt.preprocess_u8(frames_u8.contiguous(), nh, nw, _MEAN, _STD, swap_rb)

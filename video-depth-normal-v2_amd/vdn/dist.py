@@ -310,7 +310,9 @@ def infer_video_depth_sharded(model, frames: np.ndarray, target_fps, input_size:
     [1,32/g,3,H,W], group) -> [1,32/g,H,W]` are called per job (tests inject stubs).
 
     The encoder runs in chunks of VDN_ENC_CHUNK (8) frames and the taps of chunk c travel while chunk c + 1 is encoded
-    (`TapExchange`). `stats` (a dict, optional): filled with this rank's seconds per phase — preprocess, encode,
+    (`TapExchange`). On ONE rank nothing travels: unless VDN_ENC_CHUNK is set, the product then encodes in the plain driver's
+    batches (INFER_LEN frames, the ragged tail filled up with copies of the last frame: `window_depths` says why), so the two
+    drivers agree bit for bit. `stats` (a dict, optional): filled with this rank's seconds per phase — preprocess, encode,
     tap_exchange_wait, heads, gather, stitch — and bytes it sent (taps, temporal all-to-alls, gather); the device is then
     synchronised at every phase boundary, so pass it for a DIAGNOSTIC run, not for the timed one."""
     import os
@@ -356,14 +358,16 @@ def infer_video_depth_sharded(model, frames: np.ndarray, target_fps, input_size:
     if staged:
         _, _, local, _, send = tap_exchange_plan(table, jobs, P, T)
         mine = local[r]
-        x_mine = net_input(mine) if mine else net_input(table[0][:1])[:0]  # a rank may own no frame (tiny clips)
+        plain_batches = P == 1 and "VDN_ENC_CHUNK" not in os.environ and hasattr(model, "tap_planes") and hasattr(model, "_engines") and bool(mine)
+        chunk = T if plain_batches else max(1, int(os.environ.get("VDN_ENC_CHUNK", "8")))
+        fill = mine[-1:] * ((-len(mine)) % T) if plain_batches else []   # encoded, never read: `mine` alone names the rows that are
+        x_mine = net_input(mine + fill) if mine else net_input(table[0][:1])[:0]  # a rank may own no frame (tiny clips)
         t0 = mark("preprocess", t0)
-        chunk = max(1, int(os.environ.get("VDN_ENC_CHUNK", "8")))
         if hasattr(model, "tap_planes"):       # the product: encode chunk by chunk, each chunk's taps leave while the next is encoded
             planes, rpf, hw = model.tap_planes(x_mine)
             ex = TapExchange(planes, rpf, mine, send, r, chunk)
             for c in range(ex.nchunks):
-                c0, c1 = c * chunk, min(len(mine), (c + 1) * chunk)
+                c0, c1 = c * chunk, min(len(x_mine), (c + 1) * chunk)
                 if c1 > c0:
                     model.encode_into(x_mine[c0:c1], planes, c0)
                 ex.send_chunk(c)

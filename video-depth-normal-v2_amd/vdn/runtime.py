@@ -473,11 +473,15 @@ class Runtime:
     def bicubic(self, src, dst, ih: int, iw: int, oh: int, ow: int, Cn: int, scale_rows: float, scale_cols: float):
         self._launch(abi.lib.vdn_bicubic, src.data_ptr(), dst.data_ptr(), ih, iw, oh, ow, Cn, scale_rows, scale_cols)
 
-    def preprocess_u8(self, frames_u8: torch.Tensor, H: int, W: int, mean, std, swap_rb: bool = False) -> torch.Tensor:
-        """u8 [n,h,w,3] on the device -> normalised f32 [n,3,H,W] (cubic resize + /255 + mean / std), one launch."""
+    def preprocess_u8(self, frames_u8: torch.Tensor, H: int, W: int, mean, std, swap_rb: bool = False,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """u8 [n,h,w,3] on the device -> normalised f32 [n,3,H,W] (cubic resize + /255 + mean / std), one launch.
+        `out`: a contiguous f32 [n,3,H,W] to write instead of a fresh tensor."""
         n, h, w, _ = frames_u8.shape
         assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
-        out = torch.empty((n, 3, H, W), dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty((n, 3, H, W), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3, H, W)
         m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
         self._launch(abi.lib.vdn_preprocess, frames_u8.data_ptr(), n, h, w, int(swap_rb), out.data_ptr(), H, W, m3, s3)
         return out

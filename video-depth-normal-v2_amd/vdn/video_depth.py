@@ -227,7 +227,11 @@ class VideoDepthAnything(_EngineOwner):
         keyframe, slots 2..9 = the previous window's last 8), and the encoder is per-frame: here every DISTINCT frame
         goes through the encoder once (its 4 final-normed taps stay in HBM, 22 MB per 518x518 ViT-L frame), and a
         window's head reads its 32 slots from that cache — 256 instead of 384 encoder passes for a 256-frame clip,
-        same numbers. Falls back to per-window encoding when the cache would not fit (VDN_TAP_CACHE_GB, default 96)."""
+        same numbers. Every encoder batch holds INFER_LEN frames, the clip's ragged tail filled up with copies of its last
+        frame (never more encoder passes than the reference's 32 per window): vdn_gemm picks its kernel by the row count, so a
+        frame encoded in a batch of 2 is 1e-5 away from the same frame in `forward`'s batch of 32, and a clip's depth would
+        depend on how its length splits. Falls back to per-window encoding when the cache would not fit (VDN_TAP_CACHE_GB,
+        default 96)."""
         import os
         e = self._engines()
         rt, enc, head = e["rt"], e["enc"], e["head"]
@@ -235,19 +239,21 @@ class VideoDepthAnything(_EngineOwner):
         windows = list(range(len(table))) if windows is None else list(windows)
         need = sorted({f for w in windows for f in table[w]})
         budget = float(os.environ.get("VDN_TAP_CACHE_GB", "96")) * 2 ** 30
-        if len(need) * self._tap_bytes_per_frame(H, W) > budget:
+        T = util.INFER_LEN
+        batches = -(-len(need) // T)
+        if batches * T * self._tap_bytes_per_frame(H, W) > budget:
             for w in windows:
                 yield self.forward(net_in[torch.tensor(table[w], device=rt.device)][None])[0]
             return
         ph, pw = H // 14, W // 14
         P, C = ph * pw, self.pretrained.embed_dim
         slot = {f: i for i, f in enumerate(need)}        # cache row block of frame f
-        cache = [rt.hbuf(f"clip_tap{j}", (len(need) * P, C)) for j in range(4)]
-        for c0 in range(0, len(need), util.INFER_LEN):   # encoder batches of 32 distinct frames
-            fr = need[c0:c0 + util.INFER_LEN]
+        cache = [rt.hbuf(f"clip_tap{j}", (batches * T * P, C)) for j in range(4)]
+        for c0 in range(0, len(need), T):   # encoder batches of 32 distinct frames
+            fr = need[c0:c0 + T]
+            fr = fr + fr[-1:] * (T - len(fr))
             x = net_in[torch.tensor(fr, device=rt.device)] if fr != list(range(fr[0], fr[0] + len(fr))) else net_in[fr[0]:fr[0] + len(fr)]
-            enc.run(x.contiguous(), tap_out=[t.narrow0(c0 * P, len(fr) * P) for t in cache])
-        T = util.INFER_LEN
+            enc.run(x.contiguous(), tap_out=[t.narrow0(c0 * P, T * P) for t in cache])
         for w in windows:
             rows = [slot[f] for f in table[w]]
             if rows == list(range(rows[0], rows[0] + T)):          # one contiguous run: read the cache in place

@@ -378,6 +378,33 @@ int vdn_eval_metrics(const float* pred, const float* gt, const uint8_t* mask, in
                      vdn_stream stream);
 int vdn_resize_bilinear_hp(const float* x, float* y, int frames, int IH, int IW, int OH, int OW, vdn_stream stream);
 
+/* The colourised depth the reference's front ends write to disk, made on the device. Replaces, per frame, run.py:59-71,
+ * run_video.py:75-89 and metric_depth/run.py:67-78 (min/max of the frame, matplotlib palette or a grey triple, BGR,
+ * optionally cv2.hconcat([raw, 50 white columns, depth])) and, per clip, save_video of utils/dc_utils.py:72-86 (one min/max
+ * for the clip, the inferno palette or one grey channel, RGB). Stateless, caller's stream, caller-owned buffers.
+ * VDN_EINVAL: a null required pointer, a size <= 0, ch other than 1 or 3, raw with ch != 3 or margin < 0. VDN_EALIGN: a
+ * float or workspace pointer that is not 4-byte aligned. Limits: vdn_minmax_f32 takes groups <= INT32_MAX / 256 (VDN_EINVAL
+ * beyond); vdn_colorize returns VDN_EUNSUPPORTED when N * H or the output width 2W + margin exceeds UINT32_MAX. All of these
+ * are returned before anything is launched.
+ * vdn_minmax_f32 — x f32 [groups, n] contiguous -> out f32 [groups][2] = {min, max} of each group (a frame, or groups = 1
+ *                  for a clip). numpy semantics: a NaN anywhere in a group makes both of its results NaN; +-inf are
+ *                  ordinary values; when +0.0 and -0.0 tie for an extreme the sign of the zero returned is not defined
+ *                  (numpy's depends on element order). x needs 4-byte alignment only (interior by 16-byte loads, ragged ends per element).
+ *                  Two stages through `workspace` (vdn_minmax_workspace_bytes(groups)), no atomics: the same bits every run.
+ * vdn_colorize   — depth f32 [N, H, W]; minmax f32 [N][2] (per_frame != 0) or [1][2]; lut u8 [256][ch], ch = 1 or 3: the
+ *                  channel order is the table's, so BGR and RGB need no mode. raw == NULL: out u8 [N, H, W, ch]. Else raw u8
+ *                  [N, H, W, 3], ch = 3, margin >= 0 and out u8 [N, H, 2W + margin, 3]: the raw pixels verbatim, `margin`
+ *                  pixels of 255, the palette pixels. out needs no alignment.
+ *                  index = (uint8)(((d - mn) / (mx - mn)) * 255.0f): subtract, divide and multiply each rounded to fp32
+ *                  (no reciprocal, no contraction), the conversion truncates — what numpy does on a float32 array, bit
+ *                  for bit. Departures from the reference, which leaves these to an undefined NaN / out-of-range -> uint8
+ *                  cast: (1) mx == mn gives index 0 for every pixel; (2) d outside [mn, mx] (a range the caller
+ *                  supplied) clamps to 0 / 255; (3) a NaN d (or NaN bounds) gives index 0.                          */
+size_t vdn_minmax_workspace_bytes(int groups);
+int vdn_minmax_f32(const float* x, int groups, size_t n, void* workspace, float* out, vdn_stream stream);
+int vdn_colorize(const float* depth, const float* minmax, int per_frame, const uint8_t* lut, int ch, const uint8_t* raw,
+                 int margin, uint8_t* out, int N, int H, int W, vdn_stream stream);
+
 /* Depth-refiner wrappers v2 .. v5 (models/video_depth_model_v5.py:63-87,160-192, models/video_depth_model_v4.py:117-148,
  * utils/normal_utils.py:4-51). f32 throughout, frames are [frames, n = H*W] row-major.
  * vdn_frame_median  — median[f] = torch.quantile(x[f], 0.5) (linear interpolation), exact radix select;

@@ -30,4 +30,7 @@ def __getattr__(name):
     if name == "eval":   # clip evaluation metrics on the device (vdn/eval.py)
         import importlib
         return importlib.import_module(".eval", __name__)
+    if name == "vis":    # the front ends' colourised depth output on the device (vdn/vis.py)
+        import importlib
+        return importlib.import_module(".vis", __name__)
     raise AttributeError(name)

@@ -128,6 +128,9 @@ EXPORTS = {
     "vdn_eval_fit": (C.c_int, [fp, fp, vp, C.c_int, C.c_size_t, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
     "vdn_eval_metrics": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp]),
     "vdn_resize_bilinear_hp": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_minmax_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "vdn_minmax_f32": (C.c_int, [fp, C.c_int, C.c_size_t, vp, fp, vp]),
+    "vdn_colorize": (C.c_int, [fp, fp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_sizeof_gemm_desc": (C.c_size_t, []),
     "vdn_offsetof_gemm_zeros": (C.c_size_t, []),
     "vdn_offsetof_gemm_res2_lo": (C.c_size_t, []),

@@ -188,7 +188,12 @@ class DepthAnythingV2(_EngineOwner):
     @torch.no_grad()
     def infer_image(self, raw_image: np.ndarray, input_size: int = 518) -> np.ndarray:
         """BGR u8 [h,w,3] -> f32 [h,w] (depth_anything_v2.py:57-65)."""
-        image, (h, w) = self.image2tensor(raw_image, input_size)
+        return self._infer_image_device(raw_image, input_size, "infer_image")[0][0].cpu().numpy()
+
+    def _infer_image_device(self, raw_image: np.ndarray, input_size: int, what: str):
+        """infer_image up to its device-to-host copy: (depth f32 [1,h,w], the uploaded BGR frame u8 [1,h,w,3]), both on the
+        device. The one statement of the forward, the resize and the range check that infer_image and infer_image_vis share."""
+        image, (h, w), img = self._upload(raw_image, input_size)
         depth = self.forward(image)
         rt = self._engines()["rt"]
         if tuple(depth.shape[-2:]) != (h, w):
@@ -196,12 +201,31 @@ class DepthAnythingV2(_EngineOwner):
             rt.upsample_f32(depth.contiguous(), out, 1, depth.shape[-2], depth.shape[-1], h, w)
             depth = out
         from .util import check_finite
-        check_finite(depth, "infer_image")
-        return depth[0].cpu().numpy()
+        check_finite(depth, what)
+        return depth, img
+
+    @torch.no_grad()
+    def infer_image_vis(self, raw_image: np.ndarray, input_size: int = 518, pred_only: bool = False, grayscale: bool = False,
+                        palette: str = "Spectral_r") -> np.ndarray:
+        """BGR u8 [h,w,3] -> BGR u8 [h,w,3] (pred_only) or [h, 2w+50, 3] (raw | 50 white columns | depth): the array
+        run.py:59-73 / run_video.py:75-89 build on the host from infer_image's result and hand to cv2.imwrite /
+        VideoWriter.write, byte for byte, made on the device (vdn.vis) from the same forward and the same resize; only the
+        uint8 picture is copied back. palette 'Spectral' gives metric_depth/run.py's. Mutates the memory bank like infer_image."""
+        from . import vis
+        vis._check(palette, "bgr", "frame", grayscale, 3)
+        depth, img = self._infer_image_device(raw_image, input_size, "infer_image_vis")
+        with torch.cuda.device(depth.device):
+            out = vis._colorize(self._engines()["rt"], depth.contiguous(), palette, "bgr", "frame", grayscale, 3,
+                                None if pred_only else img, 50, None)
+        return out[0].cpu().numpy()
+
+    def _upload(self, raw_image: np.ndarray, input_size: int):
+        rt = self._engines()["rt"]
+        h, w = raw_image.shape[:2]
+        img = torch.from_numpy(np.ascontiguousarray(raw_image)).to(rt.device)[None]   # BGR u8: the kernel swaps the channels
+        return self.preprocess(rt, img, input_size, swap_rb=True), (h, w), img
 
     def image2tensor(self, raw_image: np.ndarray, input_size: int = 518):
         """depth_anything_v2.py:67-92."""
-        rt = self._engines()["rt"]
-        h, w = raw_image.shape[:2]
-        img = torch.from_numpy(np.ascontiguousarray(raw_image)).to(rt.device)   # BGR u8: the kernel swaps the channels
-        return self.preprocess(rt, img[None], input_size, swap_rb=True), (h, w)
+        image, hw, _ = self._upload(raw_image, input_size)
+        return image, hw

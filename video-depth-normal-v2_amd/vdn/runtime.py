@@ -387,6 +387,31 @@ class Runtime:
         self._launch(abi.lib.vdn_resize_bilinear_hp, x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], x.shape[2],
                      out.shape[1], out.shape[2])
 
+    def minmax(self, x: torch.Tensor, groups: int, out: torch.Tensor):
+        """out f32 [groups, 2] <- {min, max} of each of the `groups` equal runs of contiguous f32 x (vdn_minmax_f32)."""
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.numel() % groups == 0
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == 2 * groups
+        ws = self.buf("minmax_ws", (abi.lib.vdn_minmax_workspace_bytes(groups) // 4,), torch.float32)
+        self._launch(abi.lib.vdn_minmax_f32, x.data_ptr(), groups, x.numel() // groups, ws.data_ptr(), out.data_ptr())
+
+    def colorize(self, depth: torch.Tensor, minmax: torch.Tensor, lut: torch.Tensor, out: torch.Tensor,
+                 raw: Optional[torch.Tensor] = None, margin: int = 0):
+        """out u8 <- palette pixels of f32 depth [N, H, W] (vdn_colorize): [N, H, W, ch], or with raw u8 [N, H, W, 3]
+        [N, H, 2W + margin, 3]. minmax f32 [N, 2] (per frame) or [1, 2]; lut u8 [256, ch]."""
+        N, H, W = depth.shape
+        ch = lut.shape[1]
+        assert depth.is_contiguous() and depth.dtype == torch.float32
+        assert minmax.is_contiguous() and minmax.dtype == torch.float32 and minmax.numel() in (2, 2 * N)
+        assert lut.is_contiguous() and lut.dtype == torch.uint8 and tuple(lut.shape) == (256, ch)
+        assert out.is_contiguous() and out.dtype == torch.uint8
+        if raw is None:
+            assert out.numel() == N * H * W * ch
+        else:
+            assert raw.is_contiguous() and raw.dtype == torch.uint8 and tuple(raw.shape) == (N, H, W, 3)
+            assert out.numel() == N * H * (2 * W + margin) * 3
+        self._launch(abi.lib.vdn_colorize, depth.data_ptr(), minmax.data_ptr(), int(minmax.numel() == 2 * N and N > 1),
+                     lut.data_ptr(), ch, self._p(raw), margin, out.data_ptr(), N, H, W)
+
     def frame_median(self, x: torch.Tensor, median: torch.Tensor):
         """median[f] = torch.quantile(x[f], 0.5) for f32 x [F, ...] (exact radix select on the device)."""
         F = x.shape[0]

@@ -198,6 +198,11 @@ class VideoDepthAnything(_EngineOwner):
                           fp32: bool = False):
         """frames u8 RGB [N,h,w,3] -> (f32 [N,h,w], target_fps) (video_depth.py:67-156). `fp32` is accepted for
         signature compatibility; operands are always 16-bit with fp32 accumulation."""
+        res = self._infer_video_depth_device(frames, input_size, "infer_video_depth")
+        return util.to_host(res), target_fps  # the clip's only device-to-host copy (pinned buffer)
+
+    def _infer_video_depth_device(self, frames: np.ndarray, input_size: int, what: str) -> torch.Tensor:
+        """infer_video_depth up to its device-to-host copy: the stitched, range-checked clip f32 [N,h,w] on the device."""
         e = self._engines()
         rt = e["rt"]
         fh, fw = frames[0].shape[:2]
@@ -212,8 +217,22 @@ class VideoDepthAnything(_EngineOwner):
         for d in self.window_depths(net_in, table):
             st.push(self.resize_depth(d, fh, fw))  # [32,fh,fw], stays on the device
         res = st.result(n)
-        util.check_finite(res, "infer_video_depth")
-        return util.to_host(res), target_fps  # the clip's only device-to-host copy (pinned buffer)
+        util.check_finite(res, what)
+        return res
+
+    @torch.no_grad()
+    def infer_video_depth_vis(self, frames: np.ndarray, target_fps, input_size: int = 518, grayscale: bool = False,
+                              palette: str = "inferno"):
+        """frames u8 RGB [N,h,w,3] -> (u8 [N,h,w,3] RGB, target_fps), or [N,h,w] with `grayscale`: the frames save_video(depths,
+        is_depths=True) of utils/dc_utils.py:72-81 appends to its writer, byte for byte, made on the device (vdn.vis) from
+        infer_video_depth's stitched result: one min/max for the clip, and the clip's only device-to-host copy is the uint8
+        frames (a quarter to three quarters of the fp32 clip), through the same pinned path."""
+        from . import vis
+        vis._check(palette, "rgb", "clip", grayscale, 1)
+        res = self._infer_video_depth_device(frames, input_size, "infer_video_depth_vis")
+        with torch.cuda.device(res.device):
+            out = vis._colorize(self._engines()["rt"], res.contiguous(), palette, "rgb", "clip", grayscale, 1, None, 0, None)
+        return util.to_host(out[..., 0] if grayscale else out), target_fps
 
     # bytes of encoder taps one frame keeps in the clip-level cache: 4 taps x P tokens x C channels x 16-bit planes
     def _tap_bytes_per_frame(self, H: int, W: int) -> int:

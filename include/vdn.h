@@ -378,6 +378,45 @@ int vdn_eval_metrics(const float* pred, const float* gt, const uint8_t* mask, in
                      vdn_stream stream);
 int vdn_resize_bilinear_hp(const float* x, float* y, int frames, int IH, int IW, int OH, int OW, vdn_stream stream);
 
+/* Normal evaluation on the device: normal_vector / sobel_ix_iy of utils/normal_utils.py:4-52 and VideoNormalLoss of
+ * loss/loss.py:370-409 (the one measure of normal quality the reference has; scripts/train*.py validate). f32 inputs,
+ * frames are [H, W] row-major. Stateless, caller's stream, caller-owned buffers. The stencil, the normalisation and the
+ * cosine are fp64 computed from the f32 samples (separate multiply and add roundings: contraction is off); sums have a
+ * fixed order (a lane's stride through its block's share, the lanes of a wave by xor-shuffle, the four waves, a frame's
+ * blocks in index order, the frames in index order) and use no atomics, so two runs give the same bits. Float pointers
+ * need 4-byte alignment only (VDN_EALIGN otherwise; workspace, frame_sums, frame_counts and out 8 bytes); where pred and
+ * target are 16-byte aligned and H * W is a multiple of 4, vdn_normal_eval reads them four floats per lane.
+ * VDN_EINVAL: a null required pointer, frames <= 0, H < 2 or W < 2 (the reference's reflect pad raises there).
+ * VDN_EUNSUPPORTED: H * W > INT32_MAX. All of these are returned before anything is launched.
+ * The stencil: Ix, Iy = cross-correlation of the reflect-padded map (no edge repeat) with kx = [[1,0,-1],[2,0,-2],[1,0,-1]]
+ * and ky = [[1,2,1],[0,0,0],[-1,-2,-1]], both divided by 8 when normalize_kernel != 0.
+ * vdn_sobel_ix_iy     — ix, iy f32 [frames, H, W] = Ix, Iy, each rounded to f32 once.
+ * vdn_normal_vector   — out f32 [frames, 3, H, W] = (-scale_xy Ix, -scale_xy Iy, scale_z) / sqrt(nx^2 + ny^2 + nz^2 + eps),
+ *                       each component rounded to f32 once. scale_xy, scale_z and eps are the float32 values given (the
+ *                       reference multiplies float32 tensors by them), widened.
+ * vdn_erode_mask3     — out u8 [frames, H, W] = 1 where mask and all of its 3 x 3 neighbours inside the image are
+ *                       non-zero, else 0: eroded_mask of loss.py:380-387, whose convolution zero-pads the inverted mask,
+ *                       so positions outside the image never erode a border pixel.
+ * vdn_normal_eval     — pred f32 [frames, 3, H, W]; target f32 [frames, 3, H, W] of any length (target_is_depth == 0) or a
+ *                       depth map f32 [frames, H, W] (target_is_depth != 0), whose normal is computed per pixel as
+ *                       vdn_normal_vector does with its defaults (kernel / 8, scales 1, eps 1e-8f), held in fp64 and never
+ *                       written; mask u8 [frames, H, W], non-zero = use, NULL = all ones. Over the pixels the erosion
+ *                       of vdn_erode_mask3 keeps: cos = sum_c (a_c / max(|a|, 1e-8)) * (b_c / max(|b|, 1e-8)), which is
+ *                       F.cosine_similarity of torch 2.x; a NaN there is a NaN in the sums. A dropped pixel is selected
+ *                       away, never multiplied by zero: NaN or inf under it reaches nothing.
+ *                       frame_sums[f] = sum of cos, frame_counts[f] = kept pixels (both may be NULL);
+ *                       out[0] = 1 - (sum over frames) / count, or 1.0 when count == 0 (reduction_batch_based returns
+ *                       sum * 0 there); out[1] = count. One pass over the inputs, a frame's blocks leave partials in
+ *                       `workspace` (vdn_normal_eval_workspace_bytes(frames)), a one-block finalise reduces them.       */
+size_t vdn_normal_eval_workspace_bytes(int frames);
+int vdn_sobel_ix_iy(const float* depth, float* ix, float* iy, int frames, int H, int W, int normalize_kernel,
+                    vdn_stream stream);
+int vdn_normal_vector(const float* depth, float* out, int frames, int H, int W, int normalize_kernel, float scale_xy,
+                      float scale_z, float eps, vdn_stream stream);
+int vdn_erode_mask3(const uint8_t* mask, uint8_t* out, int frames, int H, int W, vdn_stream stream);
+int vdn_normal_eval(const float* pred, const float* target, int target_is_depth, const uint8_t* mask, int frames, int H,
+                    int W, void* workspace, double* frame_sums, int64_t* frame_counts, double* out, vdn_stream stream);
+
 /* The colourised depth the reference's front ends write to disk, made on the device. Replaces, per frame, run.py:59-71,
  * run_video.py:75-89 and metric_depth/run.py:67-78 (min/max of the frame, matplotlib palette or a grey triple, BGR,
  * optionally cv2.hconcat([raw, 50 white columns, depth])) and, per clip, save_video of utils/dc_utils.py:72-86 (one min/max

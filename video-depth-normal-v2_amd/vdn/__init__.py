@@ -33,4 +33,7 @@ def __getattr__(name):
     if name == "vis":    # the front ends' colourised depth output on the device (vdn/vis.py)
         import importlib
         return importlib.import_module(".vis", __name__)
+    if name == "normals":  # normal_vector and VideoNormalLoss on the device (vdn/normals.py)
+        import importlib
+        return importlib.import_module(".normals", __name__)
     raise AttributeError(name)

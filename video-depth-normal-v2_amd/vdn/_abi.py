@@ -128,6 +128,11 @@ EXPORTS = {
     "vdn_eval_fit": (C.c_int, [fp, fp, vp, C.c_int, C.c_size_t, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
     "vdn_eval_metrics": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp]),
     "vdn_resize_bilinear_hp": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_normal_eval_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "vdn_sobel_ix_iy": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_normal_vector": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp]),
+    "vdn_erode_mask3": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_normal_eval": (C.c_int, [fp, fp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "vdn_minmax_workspace_bytes": (C.c_size_t, [C.c_int]),
     "vdn_minmax_f32": (C.c_int, [fp, C.c_int, C.c_size_t, vp, fp, vp]),
     "vdn_colorize": (C.c_int, [fp, fp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),

@@ -387,6 +387,48 @@ class Runtime:
         self._launch(abi.lib.vdn_resize_bilinear_hp, x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], x.shape[2],
                      out.shape[1], out.shape[2])
 
+    @staticmethod
+    def _frames3(t: torch.Tensor, dtype=torch.float32):
+        assert t.is_contiguous() and t.dtype == dtype and t.dim() == 3, (t.shape, t.dtype)
+        return t.shape
+
+    def sobel_ix_iy(self, depth: torch.Tensor, ix: torch.Tensor, iy: torch.Tensor, normalize_kernel: bool = True):
+        """ix, iy f32 [F, H, W] <- Sobel (/ 8) of the reflect-padded f32 depth [F, H, W] (include/vdn.h vdn_sobel_ix_iy)."""
+        F, H, W = self._frames3(depth)
+        assert self._frames3(ix) == depth.shape and self._frames3(iy) == depth.shape
+        self._launch(abi.lib.vdn_sobel_ix_iy, depth.data_ptr(), ix.data_ptr(), iy.data_ptr(), F, H, W, int(normalize_kernel))
+
+    def normal_vector(self, depth: torch.Tensor, out: torch.Tensor, normalize_kernel: bool = True, scale_xy: float = 1.0,
+                      scale_z: float = 1.0, eps: float = 1e-8):
+        """out f32 [F, 3, H, W] <- unit normals of f32 depth [F, H, W] (vdn_normal_vector)."""
+        F, H, W = self._frames3(depth)
+        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (F, 3, H, W)
+        self._launch(abi.lib.vdn_normal_vector, depth.data_ptr(), out.data_ptr(), F, H, W, int(normalize_kernel), scale_xy,
+                     scale_z, eps)
+
+    def erode_mask3(self, mask: torch.Tensor, out: torch.Tensor):
+        """out u8 [F, H, W] <- 1 where u8 mask and its 3 x 3 neighbours inside the image are non-zero (vdn_erode_mask3)."""
+        F, H, W = self._frames3(mask, torch.uint8)
+        assert self._frames3(out, torch.uint8) == mask.shape
+        self._launch(abi.lib.vdn_erode_mask3, mask.data_ptr(), out.data_ptr(), F, H, W)
+
+    def normal_eval(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Tensor,
+                    frame_sums: Optional[torch.Tensor] = None, frame_counts: Optional[torch.Tensor] = None):
+        """out[0:2] (float64) <- (1 - masked mean cosine, kept pixels) of pred f32 [F, 3, H, W] against target: normals
+        [F, 3, H, W] or a depth map [F, H, W], whose normals are made on the fly (vdn_normal_eval)."""
+        F, _, H, W = pred.shape
+        assert pred.is_contiguous() and pred.dtype == torch.float32 and pred.shape[1] == 3
+        assert target.is_contiguous() and target.dtype == torch.float32
+        assert tuple(target.shape) in ((F, 3, H, W), (F, H, W)), (pred.shape, target.shape)
+        if mask is not None:
+            assert self._frames3(mask, torch.uint8) == (F, H, W)
+        assert out.dtype == torch.float64 and out.numel() >= 2
+        assert frame_sums is None or (frame_sums.dtype == torch.float64 and frame_sums.numel() == F)
+        assert frame_counts is None or (frame_counts.dtype == torch.int64 and frame_counts.numel() == F)
+        ws = self.buf("normal_eval_ws", (abi.lib.vdn_normal_eval_workspace_bytes(F) // 8,), torch.float64)
+        self._launch(abi.lib.vdn_normal_eval, pred.data_ptr(), target.data_ptr(), int(target.dim() == 3), self._p(mask), F, H, W,
+                     ws.data_ptr(), self._p(frame_sums), self._p(frame_counts), out.data_ptr())
+
     def minmax(self, x: torch.Tensor, groups: int, out: torch.Tensor):
         """out f32 [groups, 2] <- {min, max} of each of the `groups` equal runs of contiguous f32 x (vdn_minmax_f32)."""
         assert x.is_contiguous() and x.dtype == torch.float32 and x.numel() % groups == 0

@@ -1,5 +1,5 @@
-// Shared device helpers for the gfx950 kernels (wave = 64 lanes, MFMA fragments per
-// /opt/skills/guides/cdna_hip_programming.md §3).
+// Shared device and launch helpers for the gfx950 kernels (wave = 64 lanes; MFMA fragment layouts as in AMD's CDNA4
+// instruction set reference). The fixed-order wave and block reductions are in reduce.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -141,11 +141,15 @@ __device__ __forceinline__ void store_from_float(void* p, int dt, size_t i, floa
   else ((__bf16*)p)[i] = (__bf16)v;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+// Blocks of 256 lanes for a grid-stride kernel over n items: ceil(n / 256), at most cap, never 0. Every call site states its cap.
+inline unsigned grid_for(size_t n, unsigned cap) {
+  const size_t b = (n + 255) / 256;
+  return (unsigned)(b < cap ? (b ? b : 1) : cap);
 }
+
+// reflect-padded neighbour indices of a 3 x 3 stencil (no edge repeat); n >= 2
+__device__ __forceinline__ int refl_lo(int i) { return i == 0 ? 1 : i - 1; }
+__device__ __forceinline__ int refl_hi(int i, int n) { return i == n - 1 ? n - 2 : i + 1; }
 
 // Barrier closing a pipeline stage that (a) other waves will overwrite by LDS-DMA and (b) whose DMA for
 // the next stage this wave has issued: the wave's own LDS reads AND its LDS-DMA must have completed

@@ -5,10 +5,11 @@
 //   vdn_resize_bilinear_hp  half-pixel bilinear resize of the prediction to the ground truth's size
 // Everything the reference computes in float64 is fp64 here, with its roundings (separate multiply and add: contraction
 // is off for this file); what it computes in float32 (the valid test, the TGM gradient of gt and its threshold, the three
-// delta accuracies) is float32 here. Sums have a fixed order: a lane's stride through its block's share, the lanes of a
-// wave by xor-shuffle, the four waves, a frame's EVAL_BPF blocks in index order, the frames in index order. No atomics:
+// delta accuracies) is float32 here. Sums have a fixed order: a lane's stride through its block's share, the wave and the
+// block as reduce.hpp states them, a frame's EVAL_BPF blocks in index order, the frames in index order. No atomics:
 // two runs give the same bits. Loads are one float per lane (coalesced), so any 4-byte-aligned pointer is accepted.
 #include "common.hpp"
+#include "reduce.hpp"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -48,6 +49,20 @@ __device__ __forceinline__ bool is_valid(float g, const uint8_t* mask, size_t i,
 __device__ __forceinline__ double clip_low(double v, double lo) { return v < lo ? lo : v; }  // np.maximum: NaN stays NaN
 __device__ __forceinline__ double max_nan(double x, double y) { return (x > y || x != x) ? x : y; }  // torch.max: NaN wins
 
+// what the fit reduces in fp64: sum p*p, sum p, sum p*t, sum t, min p, max p
+struct FitSums {
+  double s[4], pmin, pmax;
+};
+struct FitOp {
+  __device__ __forceinline__ FitSums operator()(FitSums a, const FitSums& b) const {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a.s[k] = a.s[k] + b.s[k];
+    a.pmin = fmin(a.pmin, b.pmin);
+    a.pmax = fmax(a.pmax, b.pmax);
+    return a;
+  }
+};
+
 // the aligned, clipped prediction the metrics compare with gt (eval.py:110-128)
 __device__ __forceinline__ double aligned(float pred, double scale, double shift, int depth_domain, const Range& r) {
   double a = clip_low(scale * clip_low((double)pred, r.lo) + shift, r.lo);
@@ -56,83 +71,39 @@ __device__ __forceinline__ double aligned(float pred, double scale, double shift
   return a > r.hi ? r.hi : a;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// block-wide fixed-order sums of ND doubles and NI ints; lane 0 gets the totals
-template <int ND, int NI>
-__device__ __forceinline__ void block_sums(double (&d)[ND], int (&c)[NI]) {
-  __shared__ double rd[4][ND];
-  __shared__ int rc[4][NI];
-  const int w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < ND; ++k) {
-    const double v = wave_sum_f64(d[k]);
-    if ((threadIdx.x & 63) == 0) rd[w][k] = v;
-  }
-#pragma unroll
-  for (int k = 0; k < NI; ++k) {
-    const int v = wave_sum_i32(c[k]);
-    if ((threadIdx.x & 63) == 0) rc[w][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < ND; ++k) d[k] = (rd[0][k] + rd[1][k]) + (rd[2][k] + rd[3][k]);
-#pragma unroll
-    for (int k = 0; k < NI; ++k) c[k] = (rc[0][k] + rc[1][k]) + (rc[2][k] + rc[3][k]);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------- masked fit
 __global__ __launch_bounds__(256) void eval_fit_partial_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                                const uint8_t* __restrict__ mask, size_t hw, Range r,
                                                                int depth_domain, double* __restrict__ partial) {
   const size_t f = blockIdx.x / EVAL_BPF, b = blockIdx.x % EVAL_BPF, base = f * hw;
-  double s[4] = {0, 0, 0, 0};
-  int cnt[1] = {0};
-  double pmin = INFINITY, pmax = -INFINITY;
+  FitSums a = {{0, 0, 0, 0}, INFINITY, -INFINITY};
+  int cnt = 0;
   for (size_t i = b * 256 + threadIdx.x; i < hw; i += (size_t)EVAL_BPF * 256) {
     const float g = gt[base + i];
     if (!is_valid(g, mask, base + i, r)) continue;
     const double p = clip_low((double)pred[base + i], r.lo);
     const double t = depth_domain ? 1.0 / ((double)g + 1e-8) : (double)g;
-    s[0] += p * p;
-    s[1] += p;
-    s[2] += p * t;
-    s[3] += t;
-    cnt[0] += 1;
-    pmin = fmin(pmin, p);
-    pmax = fmax(pmax, p);
+    a.s[0] += p * p;
+    a.s[1] += p;
+    a.s[2] += p * t;
+    a.s[3] += t;
+    cnt += 1;
+    a.pmin = fmin(a.pmin, p);
+    a.pmax = fmax(a.pmax, p);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    pmin = fmin(pmin, __shfl_xor(pmin, o));
-    pmax = fmax(pmax, __shfl_xor(pmax, o));
-  }
-  __shared__ double mm[4][2];
-  if ((threadIdx.x & 63) == 0) {
-    mm[threadIdx.x >> 6][0] = pmin;
-    mm[threadIdx.x >> 6][1] = pmax;
-  }
-  block_sums(s, cnt);  // has the barrier that also publishes mm
+  __shared__ WaveSlots<FitSums> rd;
+  __shared__ WaveSlots<int> rc;
+  rd.put(a, FitOp{});
+  rc.put(cnt, SumOp{});
+  __syncthreads();
   if (threadIdx.x == 0) {
+    a = rd.get(FitOp{});
     double* o = partial + (size_t)blockIdx.x * FIT_SLOTS;
-    o[0] = s[0];
-    o[1] = s[1];
-    o[2] = s[2];
-    o[3] = s[3];
-    ((int64_t*)o)[4] = cnt[0];
-    o[5] = fmin(fmin(mm[0][0], mm[1][0]), fmin(mm[2][0], mm[3][0]));
-    o[6] = fmax(fmax(mm[0][1], mm[1][1]), fmax(mm[2][1], mm[3][1]));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = a.s[k];
+    ((int64_t*)o)[4] = rc.get(SumOp{});
+    o[5] = a.pmin;
+    o[6] = a.pmax;
   }
 }
 
@@ -144,26 +115,16 @@ __global__ __launch_bounds__(256) void eval_fit_solve_kernel(void* __restrict__ 
     for (int b = 0; b < EVAL_BPF; ++b) n += ((const int64_t*)(ws.fit + ((size_t)f * EVAL_BPF + b) * FIT_SLOTS))[4];
     ws.nvalid[f] = n;
   }
-  double s[4] = {0, 0, 0, 0};
-  int none[1] = {0};
-  double pmin = INFINITY, pmax = -INFINITY;
+  FitSums a = {{0, 0, 0, 0}, INFINITY, -INFINITY};
   for (size_t j = threadIdx.x; j < (size_t)T * EVAL_BPF; j += 256) {
     const double* q = ws.fit + j * FIT_SLOTS;
-    for (int k = 0; k < 4; ++k) s[k] += q[k];
-    pmin = fmin(pmin, q[5]);
-    pmax = fmax(pmax, q[6]);
+    for (int k = 0; k < 4; ++k) a.s[k] += q[k];
+    a.pmin = fmin(a.pmin, q[5]);
+    a.pmax = fmax(a.pmax, q[6]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    pmin = fmin(pmin, __shfl_xor(pmin, o));
-    pmax = fmax(pmax, __shfl_xor(pmax, o));
-  }
-  __shared__ double mm[4][2];
-  if ((threadIdx.x & 63) == 0) {
-    mm[threadIdx.x >> 6][0] = pmin;
-    mm[threadIdx.x >> 6][1] = pmax;
-  }
-  block_sums(s, none);  // barrier: nvalid[] and mm are visible to lane 0 below
+  __shared__ WaveSlots<FitSums> rd;
+  rd.put(a, FitOp{});
+  __syncthreads();  // nvalid[] and the slots are visible to lane 0 below
   if (threadIdx.x != 0) return;
   int64_t total = 0, next = -1;
   for (int f = T - 1; f >= 0; --f) {
@@ -171,9 +132,9 @@ __global__ __launch_bounds__(256) void eval_fit_solve_kernel(void* __restrict__ 
     if (ws.nvalid[f] > 0) next = f;
     total += ws.nvalid[f];
   }
-  pmin = fmin(fmin(mm[0][0], mm[1][0]), fmin(mm[2][0], mm[3][0]));
-  pmax = fmax(fmax(mm[0][1], mm[1][1]), fmax(mm[2][1], mm[3][1]));
-  const double n = (double)total, spp = s[0], sp = s[1], spt = s[2], st = s[3];
+  a = rd.get(FitOp{});
+  const double pmin = a.pmin, pmax = a.pmax;
+  const double n = (double)total, spp = a.s[0], sp = a.s[1], spt = a.s[2], st = a.s[3];
   if (total == 0) {  // no valid pixel: nothing to align to, and every metric is NaN
     coef[0] = coef[1] = NAN;
   } else if (pmin == pmax) {  // all p equal: A = [c 1] has rank 1, lstsq returns the minimum-norm solution
@@ -203,44 +164,50 @@ __global__ __launch_bounds__(256) void eval_metrics_partial_kernel(const float* 
   const bool over_time = row_stride == 0;
   const size_t nb_off = over_time ? (nf >= 0 ? (size_t)nf * hw - base : 0) : row_stride;
   const size_t nb_end = over_time ? (nf >= 0 ? hw : 0) : (hw > row_stride ? hw - row_stride : 0);
-  double s[4] = {0, 0, 0, 0};  // |d|, |d|/g, d*d, TGM
-  int c[5] = {0, 0, 0, 0, 0};  // n, delta1..3, TGM count
+  Tuple<double, 4> s = {{0, 0, 0, 0}};  // |d|, |d|/g, d*d, TGM
+  Tuple<int, 5> c = {{0, 0, 0, 0, 0}};  // n, delta1..3, TGM count
   for (size_t i = b * 256 + threadIdx.x; i < hw; i += (size_t)EVAL_BPF * 256) {
     const float g32 = gt[base + i];
     if (!is_valid(g32, mask, base + i, r)) continue;  // the TGM mask also needs the first pixel of the pair valid
     const double g = (double)g32;
     const double a = aligned(pred[base + i], scale, shift, depth_domain, r);
     const double d = a - g, ad = fabs(d);
-    s[0] += ad;
-    s[1] += ad / g;
-    s[2] += d * d;
+    s.v[0] += ad;
+    s.v[1] += ad / g;
+    s.v[2] += d * d;
     const double q = max_nan(a / g, g / a);
-    c[0] += 1;
-    c[1] += q < 1.25;
-    c[2] += q < 1.5625;
-    c[3] += q < 1.953125;
+    c.v[0] += 1;
+    c.v[1] += q < 1.25;
+    c.v[2] += q < 1.5625;
+    c.v[3] += q < 1.953125;
     if (i < nb_end) {
       const float dg = gt[base + i + nb_off] - g32;  // float32, as the reference's gt tensor
       if (dg < 0.05f) {
         const double da = aligned(pred[base + i + nb_off], scale, shift, depth_domain, r) - a;
-        s[3] += fabs(da - (double)dg);
-        c[4] += 1;
+        s.v[3] += fabs(da - (double)dg);
+        c.v[4] += 1;
       }
     }
   }
-  block_sums(s, c);
+  __shared__ WaveSlots<Tuple<double, 4>> rd;
+  __shared__ WaveSlots<Tuple<int, 5>> rc;
+  rd.put(s, SumOp{});
+  rc.put(c, SumOp{});
+  __syncthreads();
   if (threadIdx.x == 0) {
+    s = rd.get(SumOp{});
+    c = rc.get(SumOp{});
     double* o = ws.met + (size_t)blockIdx.x * MET_SLOTS;
     int64_t* oi = (int64_t*)o;
-    oi[0] = c[0];
-    o[1] = s[0];
-    o[2] = s[1];
-    o[3] = s[2];
-    oi[4] = c[1];
-    oi[5] = c[2];
-    oi[6] = c[3];
-    o[7] = s[3];
-    oi[8] = c[4];
+    oi[0] = c.v[0];
+    o[1] = s.v[0];
+    o[2] = s.v[1];
+    o[3] = s.v[2];
+    oi[4] = c.v[1];
+    oi[5] = c.v[2];
+    oi[6] = c.v[3];
+    o[7] = s.v[3];
+    oi[8] = c.v[4];
   }
 }
 
@@ -378,8 +345,8 @@ extern "C" int vdn_resize_bilinear_hp(const float* x, float* y, int frames, int 
   if (!x || !y || frames <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return VDN_EINVAL;
   if (((uintptr_t)x & 3) || ((uintptr_t)y & 3)) return VDN_EALIGN;
   const size_t total = (size_t)frames * OH * OW;
-  const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  hipLaunchKernelGGL(resize_bilinear_hp_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, y, total, IH, IW, OH, OW);
+  hipLaunchKernelGGL(resize_bilinear_hp_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, (hipStream_t)stream, x, y, total,
+                     IH, IW, OH, OW);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

@@ -106,18 +106,13 @@ __global__ __launch_bounds__(256) void hiera_reroll_kernel(const float* __restri
   }
 }
 
-inline int grid_for(size_t n, size_t cap = 16384) {
-  const size_t b = (n + 255) / 256;
-  return (int)(b < cap ? (b ? b : 1) : cap);
-}
-
 }  // namespace
 
 extern "C" int vdn_hiera_embed(int dt, const float* img, void* rows, void* rows_lo, int frames, int ldk, vdn_stream stream) {
   if (!img || !rows || frames <= 0) return VDN_EINVAL;
   if (ldk < HI_K || (ldk & 63) || ((uintptr_t)rows & 15) || ((uintptr_t)rows_lo & 15)) return VDN_EALIGN;
   if ((int64_t)frames * HI_SIDE * HI_SIDE > 0x7fffffff) return VDN_EUNSUPPORTED;   // rows are int32 in vdn_gemm
-  const int g = grid_for((size_t)frames * HI_SIDE * HI_SIDE * (ldk >> 3));
+  const unsigned g = grid_for((size_t)frames * HI_SIDE * HI_SIDE * (ldk >> 3), 16384);
   return with_half(dt, [&](auto t) -> int {
     using T = typename Half<decltype(t)::value>::T;
     hipLaunchKernelGGL(hiera_embed_kernel<decltype(t)::value>, dim3(g), dim3(256), 0, (hipStream_t)stream, img, (T*)rows, (T*)rows_lo,
@@ -131,7 +126,8 @@ extern "C" int vdn_hiera_pool(const float* x, float* y, int frames, int n, int C
   if (!x || !y || frames <= 0 || n <= 0 || C <= 0) return VDN_EINVAL;
   if ((C & 3) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return VDN_EALIGN;
   const size_t total4 = (size_t)frames * n * (C >> 2);
-  hipLaunchKernelGGL(hiera_pool_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, x, y, total4, n, C >> 2);
+  hipLaunchKernelGGL(hiera_pool_kernel, dim3(grid_for(total4, 16384)), dim3(256), 0, (hipStream_t)stream, x, y, total4, n,
+                     C >> 2);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }
@@ -141,7 +137,8 @@ extern "C" int vdn_hiera_reroll(const float* tokens, float* map, int frames, int
   if ((C & 3) || ((uintptr_t)tokens & 15) || ((uintptr_t)map & 15)) return VDN_EALIGN;
   const int n = 3 - stage, side = 7 << n;
   const size_t total4 = (size_t)frames * side * side * (C >> 2);
-  hipLaunchKernelGGL(hiera_reroll_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, tokens, map, total4, n, C >> 2);
+  hipLaunchKernelGGL(hiera_reroll_kernel, dim3(grid_for(total4, 16384)), dim3(256), 0, (hipStream_t)stream, tokens, map,
+                     total4, n, C >> 2);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

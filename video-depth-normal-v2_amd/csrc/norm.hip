@@ -1,5 +1,6 @@
 // Normalisation / elementwise kernels (HBM-bound; one pass over the data, 8-16 B per lane).
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace {
 

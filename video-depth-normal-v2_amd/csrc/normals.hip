@@ -6,11 +6,12 @@
 //                                       sums; then a one-block finalise
 // The stencil, the normalisation and the cosine are fp64 computed from the f32 samples, with separate multiply and add
 // roundings (contraction is off for this file). Sums have a fixed order: a lane's stride through its block's share, the
-// lanes of a wave by xor-shuffle, the four waves, a frame's NE_BPF blocks in index order, the frames in index order. No
+// wave and the block as reduce.hpp states them, a frame's NE_BPF blocks in index order, the frames in index order. No
 // atomics: two runs give the same bits. Any 4-byte-aligned pointer is accepted; vdn_normal_eval reads pred (and a stored
 // target) four floats per lane where the planes are 16-byte aligned, one per lane otherwise. Stencil and erosion neighbours
 // that belong to other lanes or blocks are read through the cache, as refine_pack_kernel does; the four pixels of a lane share theirs.
 #include "common.hpp"
+#include "reduce.hpp"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -32,10 +33,6 @@ struct Ws {
     bcnt = (int64_t*)(bsum + (size_t)T * NE_BPF);
   }
 };
-
-// reflect-padded neighbour indices (no edge repeat); n >= 2
-__device__ __forceinline__ int refl_lo(int i) { return i == 0 ? 1 : i - 1; }
-__device__ __forceinline__ int refl_hi(int i, int n) { return i == n - 1 ? n - 2 : i + 1; }
 
 // cross-correlation with kx = [[1,0,-1],[2,0,-2],[1,0,-1]], ky = [[1,2,1],[0,0,0],[-1,-2,-1]] (times 1/8 = k), in fp64.
 // a[r][c] is the 3 x 3 window; its centre is not used.
@@ -222,21 +219,14 @@ __global__ __launch_bounds__(256) void normal_eval_partial_kernel(const float* _
       if (++x == W) x = 0, ++y;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o);
-    cnt += __shfl_xor(cnt, o);
-  }
-  __shared__ double rs[4];
-  __shared__ int rc[4];
-  if ((threadIdx.x & 63) == 0) {
-    rs[threadIdx.x >> 6] = sum;
-    rc[threadIdx.x >> 6] = cnt;
-  }
+  __shared__ WaveSlots<double> rs;
+  __shared__ WaveSlots<int> rc;
+  rs.put(sum, SumOp{});
+  rc.put(cnt, SumOp{});
   __syncthreads();
   if (threadIdx.x == 0) {
-    ws.bsum[blockIdx.x] = (rs[0] + rs[1]) + (rs[2] + rs[3]);
-    ws.bcnt[blockIdx.x] = (int64_t)((rc[0] + rc[1]) + (rc[2] + rc[3]));
+    ws.bsum[blockIdx.x] = rs.get(SumOp{});
+    ws.bcnt[blockIdx.x] = (int64_t)rc.get(SumOp{});
   }
 }
 
@@ -268,11 +258,6 @@ __global__ __launch_bounds__(256) void normal_eval_finalise_kernel(void* __restr
   out[1] = (double)n;
 }
 
-inline unsigned blocks_for(size_t n, unsigned cap) {
-  const size_t b = (n + 255) / 256;
-  return (unsigned)(b < cap ? b : cap);
-}
-
 // the shared argument checks of the stencil entries; VDN_OK when the call may launch
 inline int check_frames(int frames, int H, int W) {
   if (frames <= 0 || H < 2 || W < 2) return VDN_EINVAL;
@@ -292,7 +277,7 @@ extern "C" int vdn_sobel_ix_iy(const float* depth, float* ix, float* iy, int fra
   if (!depth || !ix || !iy) return VDN_EINVAL;
   if (const int rc = check_frames(frames, H, W)) return rc;
   if (((uintptr_t)depth & 3) || ((uintptr_t)ix & 3) || ((uintptr_t)iy & 3)) return VDN_EALIGN;
-  hipLaunchKernelGGL(normal_vector_kernel<0>, dim3(blocks_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(normal_vector_kernel<0>, dim3(grid_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream,
                      depth, ix, iy, frames, H, W, normalize_kernel ? 0.125 : 1.0, 1.0, 1.0, 0.0);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
@@ -303,7 +288,7 @@ extern "C" int vdn_normal_vector(const float* depth, float* out, int frames, int
   if (!depth || !out) return VDN_EINVAL;
   if (const int rc = check_frames(frames, H, W)) return rc;
   if (((uintptr_t)depth & 3) || ((uintptr_t)out & 3)) return VDN_EALIGN;
-  hipLaunchKernelGGL(normal_vector_kernel<1>, dim3(blocks_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(normal_vector_kernel<1>, dim3(grid_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream,
                      depth, out, (float*)nullptr, frames, H, W, normalize_kernel ? 0.125 : 1.0, (double)scale_xy, (double)scale_z,
                      (double)eps);
   VDN_CHECK_LAUNCH();
@@ -313,7 +298,7 @@ extern "C" int vdn_normal_vector(const float* depth, float* out, int frames, int
 extern "C" int vdn_erode_mask3(const uint8_t* mask, uint8_t* out, int frames, int H, int W, vdn_stream stream) {
   if (!mask || !out) return VDN_EINVAL;
   if (const int rc = check_frames(frames, H, W)) return rc;
-  hipLaunchKernelGGL(erode_mask3_kernel, dim3(blocks_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream, mask,
+  hipLaunchKernelGGL(erode_mask3_kernel, dim3(grid_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream, mask,
                      out, frames, H, W);
   VDN_CHECK_LAUNCH();
   return VDN_OK;

@@ -124,8 +124,7 @@ __global__ __launch_bounds__(256) void refine_pack_kernel(const float* __restric
       of[2 * hw + p] = c;
       continue;
     }
-    const int ym = y == 0 ? 1 : y - 1, yp = y == H - 1 ? H - 2 : y + 1;  // reflect (no edge repeat)
-    const int xm = x == 0 ? 1 : x - 1, xp = x == W - 1 ? W - 2 : x + 1;
+    const int ym = refl_lo(y), yp = refl_hi(y, H), xm = refl_lo(x), xp = refl_hi(x, W);
     const float a00 = df[ym * W + xm], a01 = df[ym * W + x], a02 = df[ym * W + xp];
     const float a10 = df[y * W + xm], a12 = df[y * W + xp];
     const float a20 = df[yp * W + xm], a21 = df[yp * W + x], a22 = df[yp * W + xp];
@@ -188,11 +187,6 @@ __global__ __launch_bounds__(256) void elementwise_kernel(const float* __restric
   }
 }
 
-inline unsigned blocks_for(size_t n, unsigned cap) {
-  const size_t b = (n + 255) / 256;
-  return (unsigned)(b < cap ? (b ? b : 1) : cap);
-}
-
 template <class Op>
 int launch_elementwise(const float* a, const float* b, float* out, size_t n, Op op, vdn_stream stream) {
   const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)(b ? b : a), po = (uintptr_t)out;
@@ -204,7 +198,7 @@ int launch_elementwise(const float* a, const float* b, float* out, size_t n, Op 
     nvec = (n - head) / 4;
   }
   const size_t lanes = nvec > n - 4 * nvec ? nvec : n - 4 * nvec;
-  hipLaunchKernelGGL(elementwise_kernel<Op>, dim3(blocks_for(lanes, 16384)), dim3(256), 0, (hipStream_t)stream, a, b ? b : a, out, n,
+  hipLaunchKernelGGL(elementwise_kernel<Op>, dim3(grid_for(lanes, 16384)), dim3(256), 0, (hipStream_t)stream, a, b ? b : a, out, n,
                      head, nvec, op);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
@@ -222,8 +216,8 @@ extern "C" int vdn_frame_median(const float* x, int frames, size_t n, float* med
   hipStream_t s = (hipStream_t)stream;
   uint32_t* hist = (uint32_t*)workspace;
   SelState* st = (SelState*)(hist + (size_t)frames * 2 * NBIN);
-  const unsigned per_frame = blocks_for(n, 64);
-  hipLaunchKernelGGL(median_init_kernel, dim3(blocks_for((size_t)frames * 2 * NBIN, 1024)), dim3(256), 0, s, st, hist, frames, n);
+  const unsigned per_frame = grid_for(n, 64);
+  hipLaunchKernelGGL(median_init_kernel, dim3(grid_for((size_t)frames * 2 * NBIN, 1024)), dim3(256), 0, s, st, hist, frames, n);
   hipLaunchKernelGGL(median_hist_kernel<0>, dim3(per_frame, frames), dim3(256), 0, s, x, n, st, hist);
   hipLaunchKernelGGL(median_scan_kernel<0>, dim3(frames * 2), dim3(256), 0, s, st, hist);
   hipLaunchKernelGGL(median_hist_kernel<1>, dim3(per_frame, frames), dim3(256), 0, s, x, n, st, hist);
@@ -238,7 +232,7 @@ extern "C" int vdn_frame_median(const float* x, int frames, size_t n, float* med
 extern "C" int vdn_refine_scale(const float* x, const float* median, int frames, size_t n, float w, float b, float max_log_scale,
                                 float max_depth, float* out, float* scale_out, vdn_stream stream) {
   if (!x || !median || !out || frames <= 0 || n == 0 || !(max_depth > 0.f)) return VDN_EINVAL;
-  hipLaunchKernelGGL(refine_scale_kernel, dim3(blocks_for(n, 256), frames), dim3(256), 0, (hipStream_t)stream, x, median, w, b,
+  hipLaunchKernelGGL(refine_scale_kernel, dim3(grid_for(n, 256), frames), dim3(256), 0, (hipStream_t)stream, x, median, w, b,
                      max_log_scale, max_depth, out, scale_out, n);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
@@ -246,7 +240,7 @@ extern "C" int vdn_refine_scale(const float* x, const float* median, int frames,
 
 extern "C" int vdn_refine_pack(const float* d, float* out, int frames, int H, int W, int normals, vdn_stream stream) {
   if (!d || !out || frames <= 0 || H < 2 || W < 2) return VDN_EINVAL;
-  hipLaunchKernelGGL(refine_pack_kernel, dim3(blocks_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream, d, out,
+  hipLaunchKernelGGL(refine_pack_kernel, dim3(grid_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream, d, out,
                      frames, H, W, normals);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
@@ -255,7 +249,7 @@ extern "C" int vdn_refine_pack(const float* d, float* out, int frames, int H, in
 extern "C" int vdn_refine_finish(const float* scaled, const float* depth, float w, float b, float max_depth, int residual,
                                  float* out, size_t n, vdn_stream stream) {
   if (!depth || !out || n == 0 || (residual && !scaled)) return VDN_EINVAL;
-  hipLaunchKernelGGL(refine_finish_kernel, dim3(blocks_for(n, 16384)), dim3(256), 0, (hipStream_t)stream, scaled, depth, w, b,
+  hipLaunchKernelGGL(refine_finish_kernel, dim3(grid_for(n, 16384)), dim3(256), 0, (hipStream_t)stream, scaled, depth, w, b,
                      max_depth, residual, out, n);
   VDN_CHECK_LAUNCH();
   return VDN_OK;

@@ -498,18 +498,13 @@ __global__ __launch_bounds__(OC_NT) void oc1_combine_kernel(const float* __restr
   }
 }
 
-inline int grid_for(size_t work, int cap = 4096) {
-  const size_t b = (work + 255) / 256;
-  return (int)(b < (size_t)cap ? (b ? b : 1) : cap);
-}
-
 }  // namespace
 
 extern "C" int vdn_upsample_bilinear(int dt, const void* x, const void* x_lo, void* y, void* y_lo, int B, int IH,
                                      int IW, int OH, int OW, int C, vdn_stream stream) {
   if (!x || !y || B <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || C <= 0) return VDN_EINVAL;
   if ((C & 7) || (((uintptr_t)x | (uintptr_t)y) & 15)) return VDN_EALIGN;
-  const int g = grid_for((size_t)B * OH * OW * (C >> 3), 16384);
+  const unsigned g = grid_for((size_t)B * OH * OW * (C >> 3), 16384);
   hipStream_t s = (hipStream_t)stream;
   return with_half(dt, [&](auto t) -> int {
     using T = typename Half<decltype(t)::value>::T;
@@ -523,7 +518,7 @@ extern "C" int vdn_upsample_bilinear(int dt, const void* x, const void* x_lo, vo
 extern "C" int vdn_upsample_bilinear_f32(const float* x, float* y, int B, int IH, int IW, int OH, int OW, int relu,
                                          vdn_stream stream) {
   if (!x || !y || B <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return VDN_EINVAL;
-  hipLaunchKernelGGL(upsample_f32_kernel, dim3(grid_for((size_t)B * OH * OW)), dim3(256), 0, (hipStream_t)stream, x, y,
+  hipLaunchKernelGGL(upsample_f32_kernel, dim3(grid_for((size_t)B * OH * OW, 4096)), dim3(256), 0, (hipStream_t)stream, x, y,
                      B, IH, IW, OH, OW, relu);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
@@ -565,7 +560,7 @@ extern "C" int vdn_patchify(int dt, const float* img, void* rows, void* rows_lo,
                             vdn_stream stream) {
   if (!img || !rows || B <= 0 || H <= 0 || W <= 0 || H % 14 || W % 14) return VDN_EINVAL;
   if (ldk < 588 || (ldk & 63) || ((uintptr_t)rows & 15)) return VDN_EALIGN;
-  const int g = grid_for((size_t)B * (H / 14) * (W / 14) * (ldk >> 3), 8192);
+  const unsigned g = grid_for((size_t)B * (H / 14) * (W / 14) * (ldk >> 3), 8192);
   hipStream_t s = (hipStream_t)stream;
   return with_half(dt, [&](auto t) -> int {
     using T = typename Half<decltype(t)::value>::T;
@@ -587,7 +582,7 @@ extern "C" int vdn_bicubic(const float* src, float* dst, int ih, int iw, int oh,
                            float scale_cols, vdn_stream stream) {
   if (!src || !dst || ih <= 0 || iw <= 0 || oh <= 0 || ow <= 0 || C <= 0 || scale_rows <= 0.f || scale_cols <= 0.f)
     return VDN_EINVAL;
-  hipLaunchKernelGGL(bicubic_kernel, dim3(grid_for((size_t)oh * ow * C)), dim3(256), 0, (hipStream_t)stream, src, dst,
+  hipLaunchKernelGGL(bicubic_kernel, dim3(grid_for((size_t)oh * ow * C, 4096)), dim3(256), 0, (hipStream_t)stream, src, dst,
                      ih, iw, oh, ow, C, 1.0f / scale_rows, 1.0f / scale_cols);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
@@ -602,8 +597,8 @@ extern "C" int vdn_preprocess(const uint8_t* frames, int n, int h, int w, int sw
     nm.mean[c] = mean3[c];
     nm.inv_std[c] = 1.0f / std3[c];
   }
-  hipLaunchKernelGGL(preprocess_kernel, dim3(grid_for((size_t)n * H * W)), dim3(256), 0, (hipStream_t)stream, frames, out, n, h, w, H, W,
-                     swap_rb, nm);
+  hipLaunchKernelGGL(preprocess_kernel, dim3(grid_for((size_t)n * H * W, 4096)), dim3(256), 0, (hipStream_t)stream, frames, out,
+                     n, h, w, H, W, swap_rb, nm);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }
@@ -612,7 +607,7 @@ extern "C" int vdn_head_out(int dt, const void* feat, const void* feat_lo, const
                             int M, int C, int relu, vdn_stream stream) {
   if (!feat || !w || !depth || M <= 0 || C <= 0 || C > 64) return VDN_EINVAL;
   if ((C & 7) || ((uintptr_t)feat & 15)) return VDN_EALIGN;
-  const int g = grid_for((size_t)M, 8192);
+  const unsigned g = grid_for((size_t)M, 8192);
   hipStream_t s = (hipStream_t)stream;
   return with_half(dt, [&](auto t) -> int {
     using T = typename Half<decltype(t)::value>::T;
@@ -626,7 +621,7 @@ extern "C" int vdn_head_out(int dt, const void* feat, const void* feat_lo, const
 extern "C" int vdn_mask_down1(const float* depth, float* out, int B, int H, int W, int OH, int OW, const float* w,
                               vdn_stream stream) {
   if (!depth || !out || !w || B <= 0 || OH != (H + 2 - 3) / 2 + 1 || OW != (W + 2 - 3) / 2 + 1) return VDN_EINVAL;
-  hipLaunchKernelGGL(mask_down1_kernel, dim3(grid_for((size_t)B * OH * OW)), dim3(256), 0, (hipStream_t)stream, depth,
+  hipLaunchKernelGGL(mask_down1_kernel, dim3(grid_for((size_t)B * OH * OW, 4096)), dim3(256), 0, (hipStream_t)stream, depth,
                      out, B, H, W, OH, OW, w);
   VDN_CHECK_LAUNCH();
   return VDN_OK;

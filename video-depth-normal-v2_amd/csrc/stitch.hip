@@ -4,6 +4,7 @@
 // so that a clip needs ONE device-to-host copy instead of 32 per window.
 // All HBM-bound, one pass each; the sums are deterministic (fixed partial order, fp64).
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace {
 
@@ -12,37 +13,35 @@ constexpr int SUM_BLOCKS = 256;
 // partial[b] = {sum p*p, sum p, count, sum p*t, sum t} over this block's grid-stride share
 __global__ __launch_bounds__(256) void align_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                             size_t n, double* __restrict__ partial) {
-  double s[5] = {0, 0, 0, 0, 0};
+  Tuple<double, 5> s = {{0, 0, 0, 0, 0}};
   const size_t n4 = n >> 2;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     const f32x4 p = *(const f32x4*)(pred + 4 * i), t = *(const f32x4*)(target + 4 * i);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      s[0] += (double)p[e] * p[e];
-      s[1] += p[e];
-      s[3] += (double)p[e] * t[e];
-      s[4] += t[e];
+      s.v[0] += (double)p[e] * p[e];
+      s.v[1] += p[e];
+      s.v[3] += (double)p[e] * t[e];
+      s.v[4] += t[e];
     }
-    s[2] += 4.0;
+    s.v[2] += 4.0;
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // tail elements
     const size_t i = (n4 << 2) + threadIdx.x;
-    s[0] += (double)pred[i] * pred[i];
-    s[1] += pred[i];
-    s[2] += 1.0;
-    s[3] += (double)pred[i] * target[i];
-    s[4] += target[i];
+    s.v[0] += (double)pred[i] * pred[i];
+    s.v[1] += pred[i];
+    s.v[2] += 1.0;
+    s.v[3] += (double)pred[i] * target[i];
+    s.v[4] += target[i];
   }
-  __shared__ double red[4][5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    double v = s[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-  }
+  __shared__ WaveSlots<Tuple<double, 5>> red;
+  red.put(s, SumOp{});
   __syncthreads();
-  if (threadIdx.x < 5) partial[blockIdx.x * 5 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  if (threadIdx.x == 0) {
+    s = red.get(SumOp{});
+#pragma unroll
+    for (int k = 0; k < 5; ++k) partial[blockIdx.x * 5 + k] = s.v[k];
+  }
 }
 
 // coef = {scale, shift}: x = A^-1 b of compute_scale_and_shift_full (utils/util.py:49-60), (1, 0) when det == 0
@@ -110,9 +109,8 @@ extern "C" int vdn_stitch_apply(const float* window, const float* coef, float* o
   if (!window || !coef || !out_tail || !out_new || !ref1 || hw == 0) return VDN_EINVAL;
   if (T <= overlap || align_len < 0 || overlap - align_len < 2 || ref_frame < align_len || ref_frame >= T) return VDN_EINVAL;
   const size_t total = (size_t)(T - align_len) * hw;
-  const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  hipLaunchKernelGGL(align_apply_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, window, coef, out_tail, out_new,
-                     ref1, hw, T, align_len, overlap, ref_frame);
+  hipLaunchKernelGGL(align_apply_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, (hipStream_t)stream, window, coef,
+                     out_tail, out_new, ref1, hw, T, align_len, overlap, ref_frame);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

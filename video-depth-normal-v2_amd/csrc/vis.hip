@@ -7,6 +7,7 @@
 //                    does on a float32 array; table lookup; optional hconcat with the raw frame
 // Both are memory traffic: 4 B in per pixel, 1 to 6 B out.
 #include "common.hpp"
+#include "reduce.hpp"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -30,24 +31,11 @@ struct MinMax {
     nan |= (v != v);
   }
 };
-
-__device__ __forceinline__ MinMax block_minmax(MinMax m) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    m.lo = fminf(m.lo, __shfl_xor(m.lo, o));
-    m.hi = fmaxf(m.hi, __shfl_xor(m.hi, o));
-    m.nan |= __shfl_xor(m.nan, o);
+struct MinMaxOp {
+  __device__ __forceinline__ MinMax operator()(MinMax a, const MinMax& b) const {
+    return MinMax{fminf(a.lo, b.lo), fmaxf(a.hi, b.hi), a.nan | b.nan};
   }
-  __shared__ float rl[4], rh[4];
-  __shared__ int rn[4];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) rl[w] = m.lo, rh[w] = m.hi, rn[w] = m.nan;
-  __syncthreads();
-  const int nw = blockDim.x >> 6;
-  m.lo = rl[0], m.hi = rh[0], m.nan = rn[0];
-  for (int k = 1; k < nw; ++k) m.lo = fminf(m.lo, rl[k]), m.hi = fmaxf(m.hi, rh[k]), m.nan |= rn[k];
-  return m;
-}
+};
 
 // Stage 1: block b of group g takes every bpg-th run of 256 aligned float4 of the group's interior; block 0 also takes the
 // (at most 3 + 3) elements before the first and after the last 16-byte boundary. partial[g][b] = {min, max}, both NaN if
@@ -69,8 +57,11 @@ __global__ __launch_bounds__(256) void minmax_partial_kernel(const float* __rest
     if (threadIdx.x < head) m.take(p[threadIdx.x]);
     if (tail0 + threadIdx.x < n) m.take(p[tail0 + threadIdx.x]);
   }
-  m = block_minmax(m);
+  __shared__ WaveSlots<MinMax> red;
+  red.put(m, MinMaxOp{});
+  __syncthreads();
   if (threadIdx.x == 0) {
+    m = red.get(MinMaxOp{});
     float* o = partial + ((size_t)g * MM_MAX_BPG + b) * 2;
     o[0] = m.nan ? NAN : m.lo;
     o[1] = m.nan ? NAN : m.hi;
@@ -87,12 +78,7 @@ __global__ __launch_bounds__(64) void minmax_final_kernel(const float* __restric
     m.hi = fmaxf(m.hi, q[1]);
     m.nan |= (q[0] != q[0]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    m.lo = fminf(m.lo, __shfl_xor(m.lo, o));
-    m.hi = fmaxf(m.hi, __shfl_xor(m.hi, o));
-    m.nan |= __shfl_xor(m.nan, o);
-  }
+  m = wave_reduce(m, MinMaxOp{});
   if (threadIdx.x == 0) {
     out[2 * g] = m.nan ? NAN : m.lo;
     out[2 * g + 1] = m.nan ? NAN : m.hi;
@@ -261,8 +247,7 @@ extern "C" int vdn_colorize(const float* depth, const float* minmax, int per_fra
   size_t first = ch == 3 ? ((uintptr_t)out & 3) : ((4 - ((uintptr_t)out & 3)) & 3);
   first = first < a.pixels ? first : a.pixels;
   const size_t groups = (a.pixels - first) / 4;
-  const size_t want = (groups + 255) / 256;
-  const unsigned grid = (unsigned)(want < 1 ? 1 : want > 4096 ? 4096 : want);
+  const unsigned grid = grid_for(groups, 4096);  // groups may be 0: block 0 still writes the loose pixels
   hipStream_t s = (hipStream_t)stream;
   if (ch == 1) hipLaunchKernelGGL((colorize_kernel<1, false>), dim3(grid), dim3(256), 0, s, a, (unsigned)first, groups);
   else if (!raw) hipLaunchKernelGGL((colorize_kernel<3, false>), dim3(grid), dim3(256), 0, s, a, (unsigned)first, groups);

@@ -417,6 +417,54 @@ int vdn_erode_mask3(const uint8_t* mask, uint8_t* out, int frames, int H, int W,
 int vdn_normal_eval(const float* pred, const float* target, int target_is_depth, const uint8_t* mask, int frames, int H,
                     int W, void* workspace, double* frame_sums, int64_t* frame_counts, double* out, vdn_stream stream);
 
+/* The depth criterion on the device: VideoDepthLoss of loss/loss.py:326-367 as the reference's scripts construct it
+ * (trim = 0, batch-based reduction, no SSIM term), forward only; scripts/train*.py validate:
+ *     loss_dict = criterion(prediction=pred, target=gt, mask=valid)      (all [B, T, H, W])
+ * prediction, target f32 [B, T, H, W] row-major, mask u8 [B, T, H, W] (non-zero = keep, required). Stateless, caller's
+ * stream, caller-owned buffers.
+ * Arithmetic. Tests and sums are fp64 computed from the f32 samples (separate multiply and add roundings: contraction is
+ * off), except the operations the reference's float32 tensors decide something with, which are the same float32
+ * operations here:
+ *   fit      per item b over its T * H * W pixels, masked fp64 sums a00 = sum p^2, a01 = sum p, a11 = count, b0 = sum p t,
+ *            b1 = sum t; det = a00 a11 - a01^2; if det != 0 scale = (a11 b0 - a01 b1) / (det + 1e-6), shift = (-a01 b0 +
+ *            a00 b1) / (det + 1e-6), else both 0; each rounded to f32 once (compute_scale_and_shift).
+ *   align    a = fadd_rn(fmul_rn(scale, p), shift): two f32 roundings. Never stored; every pass recomputes it bit for bit.
+ *   robust   per frame f, for x = a and x = target: n_f = kept pixels; m = the lower median (rank (H W - 1) / 2 of the
+ *            sorted values) of keep ? x : 0, which is torch.median of mask * x and an input sample or 0, so exact (-0.0 is
+ *            returned as +0.0); s = max(sum_keep |x - m| / n_f, 1e-6); m = 0, s = 1 when n_f == 0. xn = (x - m) / s.
+ *   spatial  data = sum_keep |an - tn| / sum n_f (0 when nothing is kept); with d = an - tn, on each grid [::2^k, ::2^k],
+ *            k < scales: g_k = (sum |d(y, x + 2^k) - d(y, x)| + sum |d(y + 2^k, x) - d(y, x)|) / M_k over the pairs of grid
+ *            points that are both kept, inside one frame; M_k = kept grid points of all frames, g_k = 0 when M_k == 0.
+ *            spatial_loss = data + alpha * sum_k g_k; alpha <= 0 skips the regulariser (g_k = M_k = 0).
+ *   stable   per frame, th = fmul_rn(fsub_rn(max, min), 0.05f) of the kept target (-inf for an empty frame). For t = 1 ..
+ *            T - 1 inside one item: pg = fsub_rn(a_t, a_{t-1}), tg = fsub_rn(t_t, t_{t-1}); a pixel counts when kept in
+ *            both frames and |tg| < th[b, t]; stable_loss = sum |pg - tg| / count (0 when count == 0). Computed when
+ *            stable_scale > 0, which needs T >= 2 (the reference divides by zero strides at T == 1).
+ *   absRel   over keep && target > 1e-3f && target < 70f: sum |(a - t) / t| / count (0 when count == 0).
+ *   d1       over the mask: the share of pixels with fdiv_rn(a, t) < 1.25f and fdiv_rn(t, a) < 1.25f (a NaN or inf quotient
+ *            is no hit); 0 when nothing is kept.
+ *   total    spatial_loss + stable_scale * stable_loss (the second term when stable_scale > 0).
+ * A dropped pixel is skipped by a branch, never multiplied by zero: NaN or inf under it reaches nothing. (The reference
+ * multiplies by the mask, so there a NaN under a dropped pixel poisons the sums.)
+ * out f64 [20]: 0 spatial_loss | 1 stable_loss | 2 absRel_loss | 3 d1 | 4 total_loss | 5 data | 6 sum_k g_k | 7 kept pixels |
+ *               8..11 g_0..g_3 | 12..15 M_0..M_3 | 16 pixels of stable_loss | 17 pixels of absRel_loss | 18 hits of d1 |
+ *               19 zero. out == NULL: only the fit runs (scale_shift is then required and T may
+ *               be 1): compute_scale_and_shift on [B, T * H * W].
+ * scale_shift f32 [B][2] = {scale, shift}; frame_stats f64 [B * T][4] = {m of a, s of a, m of target, s of target};
+ * frame_counts i64 [B * T] = n_f. Each may be NULL.
+ * Determinism: sums have a fixed order (a lane's stride through its block's share, the lanes of a wave by xor-shuffle, the
+ * four waves, a frame's blocks in index order, the frames in index order); the medians come from the exact radix select
+ * that vdn_frame_median uses, whose integer atomics count and cannot reorder anything. Two runs give the same bits.
+ * workspace: vdn_depth_loss_workspace_bytes(B, T) bytes (it depends on B and T alone), 8-byte aligned.
+ * Float pointers need 4-byte alignment, workspace, frame_stats, frame_counts and out 8 (VDN_EALIGN otherwise). Where H * W
+ * is a multiple of 4, prediction and target are 16-byte aligned and the mask is 4-byte aligned, a lane reads four pixels
+ * per load; one otherwise. VDN_EINVAL: a null required pointer, a size <= 0, scales < 0, or T < 2 with stable_scale > 0.
+ * VDN_EUNSUPPORTED: H * W > INT32_MAX, B * T > 65535, scales > 4. All of these are returned before anything is launched. */
+size_t vdn_depth_loss_workspace_bytes(int B, int T);
+int vdn_depth_loss(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                   double alpha, int scales, double stable_scale, void* workspace, float* scale_shift,
+                   double* frame_stats, int64_t* frame_counts, double* out, vdn_stream stream);
+
 /* The colourised depth the reference's front ends write to disk, made on the device. Replaces, per frame, run.py:59-71,
  * run_video.py:75-89 and metric_depth/run.py:67-78 (min/max of the frame, matplotlib palette or a grey triple, BGR,
  * optionally cv2.hconcat([raw, 50 white columns, depth])) and, per clip, save_video of utils/dc_utils.py:72-86 (one min/max

@@ -1,0 +1,457 @@
+// The depth criterion of the reference's validate on the device: VideoDepthLoss of loss/loss.py:326-367 (trim = 0,
+// batch-based reduction, no SSIM term), forward only, for [B, T, H, W] tensors that already sit in HBM.
+//   fit        per item, the masked sums of compute_scale_and_shift (fp64), per-frame counts and the masked min / max of
+//              the target; a one-block solve rounds scale and shift to float32 once
+//   select     the lower medians of keep ? aligned : 0 and keep ? target : 0 per frame (select.hpp, two slots)
+//   scale      per frame, sum over kept pixels of |x - m| for both
+//   fused      one pass: data term, the gradient terms of the grids [::2^k, ::2^k], absRel, d1 and the temporal term;
+//              then a one-block finalise
+// The aligned prediction a = fl32(fl32(scale * p) + shift) is never stored: every pass recomputes it bit for bit, so
+// thresholds, medians and differences are taken on the float32 numbers the reference holds. Everything else is fp64
+// computed from the float32 samples with separate multiply and add roundings (contraction is off for this file). A dropped
+// pixel is skipped by a branch: NaN or inf under it reaches nothing. Sums have a fixed order: a lane's stride through its
+// block's share, the wave and the block as reduce.hpp states them, a frame's DL_BPF blocks in index order, the frames in
+// index order. The only atomics are the integer ones of the select's histograms: two runs give the same bits.
+// Any 4-byte-aligned pointer is accepted; where H * W is a multiple of 4, prediction and target are 16-byte aligned and the
+// mask 4-byte aligned, a lane reads four consecutive pixels with one load per plane, one pixel otherwise. Neighbours
+// (x + 2^k, y + 2^k) that belong to other lanes are read through the cache; the right-hand neighbour of the finest grid
+// comes from the lane's own quad, and the next frame's pixels are read like the frame's own.
+#include "common.hpp"
+#include "reduce.hpp"
+#include "select.hpp"
+#include <math.h>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int DL_BPF = 32;        // blocks per frame, fixed so that the workspace depends on B and T alone
+constexpr int DL_MAX_SCALES = 4;  // the reference's default, and all its scripts construct
+constexpr int NACC = 3 + DL_MAX_SCALES;
+// accumulator slots of the fused pass: doubles {data, absRel, temporal, g_0 .. g_3 numerators}, integers {absRel count,
+// d1 hits, temporal count, M_0 .. M_3}
+enum { A_DATA = 0, A_ABSREL = 1, A_TEMP = 2, A_G = 3 };
+
+struct MinOp {
+  __device__ __forceinline__ float operator()(float a, float b) const { return b < a ? b : a; }
+};
+struct MaxOp {
+  __device__ __forceinline__ float operator()(float a, float b) const { return b > a ? b : a; }
+};
+
+// workspace, in 8-byte slots
+struct Ws {
+  double* fit_b;     // [F][DL_BPF][4] block sums p^2, p, p t, t
+  int64_t* cnt_b;    // [F][DL_BPF]
+  float* mm_b;       // [F][DL_BPF][2] block min, max of the kept target
+  double* fit_f;     // [F][4]
+  int64_t* cnt_f;    // [F]
+  float* th;         // [F] (a slot each)
+  float* ss;         // [B][2] scale, shift
+  float* med;        // [F][2] lower median of the aligned prediction, of the target
+  double* dev_b;     // [F][DL_BPF][2] block sums |a - m|, |t - m|
+  double* acc_b;     // [F][DL_BPF][NACC]
+  int64_t* cnt_acc_b;  // [F][DL_BPF][NACC]
+  double* acc_f;     // [F][NACC]
+  int64_t* cnt_acc_f;  // [F][NACC]
+  void* select;
+  __host__ __device__ static size_t slots(size_t B, size_t F) {
+    return F * DL_BPF * (4 + 1 + 1 + 2 + 2 * NACC) + F * (4 + 1 + 1 + 1 + 2 * NACC) + B;
+  }
+  __host__ __device__ Ws(void* p, int B, int T) {
+    const size_t F = (size_t)B * T, FB = F * DL_BPF;
+    double* q = (double*)p;
+    fit_b = q, q += FB * 4;
+    cnt_b = (int64_t*)q, q += FB;
+    mm_b = (float*)q, q += FB;
+    dev_b = q, q += FB * 2;
+    acc_b = q, q += FB * NACC;
+    cnt_acc_b = (int64_t*)q, q += FB * NACC;
+    fit_f = q, q += F * 4;
+    cnt_f = (int64_t*)q, q += F;
+    th = (float*)q, q += F;
+    med = (float*)q, q += F;
+    acc_f = q, q += F * NACC;
+    cnt_acc_f = (int64_t*)q, q += F * NACC;
+    ss = (float*)q, q += B;
+    select = q;
+  }
+};
+
+// Two roundings. Plain operators, which the pragma above keeps apart: the bodies of __fmul_rn and __fadd_rn are compiled under
+// the header's contraction mode, and once inlined the pair becomes one v_fma_f32.
+__device__ __forceinline__ float aligned(float scale, float p, float shift) {
+  const float m = scale * p;
+  return m + shift;
+}
+
+// PPL consecutive pixels of a frame: 4 (one 16-byte load per float plane, one 4-byte load of the mask) or 1
+template <int PPL>
+struct Px {
+  float p[PPL], t[PPL];
+  bool k[PPL];
+  __device__ __forceinline__ Px(const float* __restrict__ pf, const float* __restrict__ tf, const uint8_t* __restrict__ mf, int i) {
+    if (PPL == 4) {
+      const f32x4 v = *(const f32x4*)(pf + i), w = *(const f32x4*)(tf + i);
+      const uint32_t m = *(const uint32_t*)(mf + i);
+#pragma unroll
+      for (int j = 0; j < PPL; ++j) p[j] = v[j], t[j] = w[j], k[j] = ((m >> (8 * j)) & 0xFFu) != 0;
+    } else {
+      p[0] = pf[i], t[0] = tf[i], k[0] = mf[i] != 0;
+    }
+  }
+};
+
+// ------------------------------------------------------------------------------------------------ fit
+template <int PPL>
+__global__ __launch_bounds__(256) void fit_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                          const uint8_t* __restrict__ mask, int B, int T, int hw,
+                                                          void* __restrict__ workspace) {
+  const Ws ws(workspace, B, T);
+  const int f = blockIdx.x / DL_BPF, b = blockIdx.x % DL_BPF;
+  const float* pf = pred + (size_t)f * hw;
+  const float* tf = target + (size_t)f * hw;
+  const uint8_t* mf = mask + (size_t)f * hw;
+  Tuple<double, 4> s = {{0.0, 0.0, 0.0, 0.0}};
+  int cnt = 0;
+  float mn = INFINITY, mx = -INFINITY;
+  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+    const Px<PPL> q(pf, tf, mf, (int)q0);
+#pragma unroll
+    for (int j = 0; j < PPL; ++j)
+      if (q.k[j]) {
+        const double p = (double)q.p[j], t = (double)q.t[j];
+        s.v[0] += p * p;
+        s.v[1] += p;
+        s.v[2] += p * t;
+        s.v[3] += t;
+        cnt += 1;
+        mn = MinOp{}(mn, q.t[j]);
+        mx = MaxOp{}(mx, q.t[j]);
+      }
+  }
+  __shared__ WaveSlots<Tuple<double, 4>> rs;
+  __shared__ WaveSlots<int> rc;
+  __shared__ WaveSlots<float> rmn, rmx;
+  rs.put(s, SumOp{});
+  rc.put(cnt, SumOp{});
+  rmn.put(mn, MinOp{});
+  rmx.put(mx, MaxOp{});
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const Tuple<double, 4> r = rs.get(SumOp{});
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ws.fit_b[(size_t)blockIdx.x * 4 + i] = r.v[i];
+    ws.cnt_b[blockIdx.x] = (int64_t)rc.get(SumOp{});
+    ws.mm_b[(size_t)blockIdx.x * 2] = rmn.get(MinOp{});
+    ws.mm_b[(size_t)blockIdx.x * 2 + 1] = rmx.get(MaxOp{});
+  }
+}
+
+// One block: every frame's blocks in index order, then every item's frames in index order, then the 2 x 2 solve.
+__global__ __launch_bounds__(256) void fit_solve_kernel(void* __restrict__ workspace, int B, int T, int64_t* __restrict__ frame_counts,
+                                                        float* __restrict__ scale_shift) {
+  const Ws ws(workspace, B, T);
+  const int F = B * T;
+  for (int f = threadIdx.x; f < F; f += 256) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    int64_t n = 0;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int b = 0; b < DL_BPF; ++b) {
+      const size_t o = (size_t)f * DL_BPF + b;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s[i] += ws.fit_b[o * 4 + i];
+      n += ws.cnt_b[o];
+      mn = MinOp{}(mn, ws.mm_b[o * 2]);
+      mx = MaxOp{}(mx, ws.mm_b[o * 2 + 1]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ws.fit_f[(size_t)f * 4 + i] = s[i];
+    ws.cnt_f[f] = n;
+    ws.th[f] = (mx - mn) * 0.05f;  // -inf for a frame without a kept pixel: nothing is below it
+    if (frame_counts) frame_counts[f] = n;
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < B; b += 256) {
+    double a00 = 0.0, a01 = 0.0, b0 = 0.0, b1 = 0.0;
+    int64_t n = 0;
+    for (int t = 0; t < T; ++t) {
+      const size_t f = (size_t)b * T + t;
+      a00 += ws.fit_f[f * 4], a01 += ws.fit_f[f * 4 + 1], b0 += ws.fit_f[f * 4 + 2], b1 += ws.fit_f[f * 4 + 3];
+      n += ws.cnt_f[f];
+    }
+    const double a11 = (double)n;
+    const double det = a00 * a11 - a01 * a01;
+    double scale = 0.0, shift = 0.0;
+    if (det != 0.0) {
+      scale = (a11 * b0 - a01 * b1) / (det + 1e-6);
+      shift = (-a01 * b0 + a00 * b1) / (det + 1e-6);
+    }
+    ws.ss[b * 2] = (float)scale;
+    ws.ss[b * 2 + 1] = (float)shift;
+    if (scale_shift) scale_shift[b * 2] = (float)scale, scale_shift[b * 2 + 1] = (float)shift;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ medians
+// slot 0: keep ? aligned prediction : 0; slot 1: keep ? target : 0 (torch.median of mask * x counts dropped pixels as zeros)
+struct LossKey {
+  const float* pred;
+  const float* target;
+  const uint8_t* mask;
+  const float* ss;
+  size_t hw;
+  int T;
+  __device__ __forceinline__ void operator()(int f, size_t i, uint32_t& k0, uint32_t& k1) const {
+    const size_t o = (size_t)f * hw + i;
+    float a = 0.f, t = 0.f;
+    if (mask[o] != 0) {
+      const int b = f / T;
+      a = aligned(ss[b * 2], pred[o], ss[b * 2 + 1]);
+      t = target[o];
+    }
+    k0 = ordered_key(a);
+    k1 = ordered_key(t);
+  }
+};
+
+__global__ void median_store_kernel(const SelState* __restrict__ st, int F, float* __restrict__ med) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < F * 2) med[i] = key_value(st[i].prefix) + 0.f;  // + 0: a median of -0.0 is stored as +0.0
+}
+
+template <int PPL>
+__global__ __launch_bounds__(256) void deviation_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                                const uint8_t* __restrict__ mask, int B, int T, int hw,
+                                                                void* __restrict__ workspace) {
+  const Ws ws(workspace, B, T);
+  const int f = blockIdx.x / DL_BPF, b = blockIdx.x % DL_BPF;
+  const float* pf = pred + (size_t)f * hw;
+  const float* tf = target + (size_t)f * hw;
+  const uint8_t* mf = mask + (size_t)f * hw;
+  const float sc = ws.ss[(f / T) * 2], sh = ws.ss[(f / T) * 2 + 1];
+  const double mp = (double)ws.med[f * 2], mt = (double)ws.med[f * 2 + 1];
+  Tuple<double, 2> s = {{0.0, 0.0}};
+  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+    const Px<PPL> q(pf, tf, mf, (int)q0);
+#pragma unroll
+    for (int j = 0; j < PPL; ++j)
+      if (q.k[j]) {
+        s.v[0] += fabs((double)aligned(sc, q.p[j], sh) - mp);
+        s.v[1] += fabs((double)q.t[j] - mt);
+      }
+  }
+  __shared__ WaveSlots<Tuple<double, 2>> rs;
+  rs.put(s, SumOp{});
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const Tuple<double, 2> r = rs.get(SumOp{});
+    ws.dev_b[(size_t)blockIdx.x * 2] = r.v[0];
+    ws.dev_b[(size_t)blockIdx.x * 2 + 1] = r.v[1];
+  }
+}
+
+// s of normalize_prediction_robust: max(sum |x - m| / n, 1e-6), 1 for a frame without a kept pixel; which = 0 prediction, 1 target
+__device__ double frame_scale(const Ws& ws, int f, int which) {
+  const int64_t n = ws.cnt_f[f];
+  if (n == 0) return 1.0;
+  double s = 0.0;
+  for (int b = 0; b < DL_BPF; ++b) s += ws.dev_b[((size_t)f * DL_BPF + b) * 2 + which];
+  s = s / (double)n;
+  return s < 1e-6 ? 1e-6 : s;
+}
+
+// ------------------------------------------------------------------------------------------------ fused pass
+template <int PPL>
+__global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                           const uint8_t* __restrict__ mask, int B, int T, int H, int W, int scales,
+                                                           int temporal, void* __restrict__ workspace) {
+  const Ws ws(workspace, B, T);
+  const int f = blockIdx.x / DL_BPF, b = blockIdx.x % DL_BPF;
+  const int hw = H * W;
+  const float* pf = pred + (size_t)f * hw;
+  const float* tf = target + (size_t)f * hw;
+  const uint8_t* mf = mask + (size_t)f * hw;
+  __shared__ double fs[2];
+  if (threadIdx.x < 2) fs[threadIdx.x] = frame_scale(ws, f, threadIdx.x);
+  __syncthreads();
+  const float sc = ws.ss[(f / T) * 2], sh = ws.ss[(f / T) * 2 + 1];
+  const double mp = (double)ws.med[f * 2], mt = (double)ws.med[f * 2 + 1], sp = fs[0], st = fs[1];
+  const bool has_next = temporal && (f % T) + 1 < T;  // the next frame of the same item
+  const float th = has_next ? ws.th[f + 1] : 0.f;
+  // the difference of the normalised maps at one pixel
+  auto diff = [&](float a, float t) { return ((double)a - mp) / sp - ((double)t - mt) / st; };
+  Tuple<double, NACC> acc;
+  Tuple<int, NACC> cnt;
+#pragma unroll
+  for (int i = 0; i < NACC; ++i) acc.v[i] = 0.0, cnt.v[i] = 0;
+  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+    const int p0 = (int)q0;
+    const Px<PPL> q(pf, tf, mf, p0);
+    // the same pixels of the next frame: frames are hw apart, so these are the same kind of load as q's
+    const Px<PPL> qn(pf + (has_next ? hw : 0), tf + (has_next ? hw : 0), mf + (has_next ? hw : 0), p0);
+    int y = p0 / W, x = p0 - y * W;
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+      if (q.k[j]) {  // a dropped pixel is skipped: nothing under it is read into the sums
+        const int p = p0 + j;
+        const float a = aligned(sc, q.p[j], sh), t = q.t[j];
+        const double d = diff(a, t);
+        acc.v[A_DATA] += fabs(d);
+        if (t > 1e-3f && t < 70.f) {
+          acc.v[A_ABSREL] += fabs(((double)a - (double)t) / (double)t);
+          cnt.v[A_ABSREL] += 1;
+        }
+        if (__fdiv_rn(a, t) < 1.25f && __fdiv_rn(t, a) < 1.25f) cnt.v[A_DATA] += 1;  // max(a / t, t / a) < 1.25; NaN is false
+        if (has_next && qn.k[j]) {
+          const float tg = qn.t[j] - t;
+          if (fabsf(tg) < th) {
+            const float pg = aligned(sc, qn.p[j], sh) - a;
+            acc.v[A_TEMP] += fabs((double)pg - (double)tg);
+            cnt.v[A_TEMP] += 1;
+          }
+        }
+        bool on = true;
+#pragma unroll
+        for (int k = 0; k < DL_MAX_SCALES; ++k) {
+          const int step = 1 << k;
+          on = on && k < scales && ((x | y) & (step - 1)) == 0;  // a point of the grid [::step, ::step]
+          if (on) {
+            cnt.v[A_G + k] += 1;
+            if (x + step < W) {
+              const int jn = (j + 1) % PPL;
+              if (PPL == 4 && k == 0 && jn > 0) {  // the next pixel of the quad, in the same row
+                if (q.k[jn]) acc.v[A_G + k] += fabs(diff(aligned(sc, q.p[jn], sh), q.t[jn]) - d);
+              } else if (mf[p + step] != 0) {
+                acc.v[A_G + k] += fabs(diff(aligned(sc, pf[p + step], sh), tf[p + step]) - d);
+              }
+            }
+            if (y + step < H) {
+              const size_t o = (size_t)p + (size_t)step * W;
+              if (mf[o] != 0) acc.v[A_G + k] += fabs(diff(aligned(sc, pf[o], sh), tf[o]) - d);
+            }
+          }
+        }
+      }
+      if (++x == W) x = 0, ++y;
+    }
+  }
+  __shared__ WaveSlots<Tuple<double, NACC>> rs;
+  __shared__ WaveSlots<Tuple<int, NACC>> rc;
+  rs.put(acc, SumOp{});
+  rc.put(cnt, SumOp{});
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const Tuple<double, NACC> r = rs.get(SumOp{});
+    const Tuple<int, NACC> c = rc.get(SumOp{});
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) {
+      ws.acc_b[(size_t)blockIdx.x * NACC + i] = r.v[i];
+      ws.cnt_acc_b[(size_t)blockIdx.x * NACC + i] = (int64_t)c.v[i];
+    }
+  }
+}
+
+// One block: every frame's blocks in index order, then the frames in index order. The integer slot of A_DATA holds the d1 hits.
+__global__ __launch_bounds__(256) void loss_finalise_kernel(void* __restrict__ workspace, int B, int T, double alpha, int scales,
+                                                            double stable_scale, double* __restrict__ frame_stats,
+                                                            double* __restrict__ out) {
+  const Ws ws(workspace, B, T);
+  const int F = B * T;
+  for (int f = threadIdx.x; f < F; f += 256) {
+    double s[NACC];
+    int64_t n[NACC];
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) s[i] = 0.0, n[i] = 0;
+    for (int b = 0; b < DL_BPF; ++b)
+#pragma unroll
+      for (int i = 0; i < NACC; ++i) {
+        s[i] += ws.acc_b[((size_t)f * DL_BPF + b) * NACC + i];
+        n[i] += ws.cnt_acc_b[((size_t)f * DL_BPF + b) * NACC + i];
+      }
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) ws.acc_f[(size_t)f * NACC + i] = s[i], ws.cnt_acc_f[(size_t)f * NACC + i] = n[i];
+    if (frame_stats) {
+      frame_stats[(size_t)f * 4] = (double)ws.med[f * 2];
+      frame_stats[(size_t)f * 4 + 1] = frame_scale(ws, f, 0);
+      frame_stats[(size_t)f * 4 + 2] = (double)ws.med[f * 2 + 1];
+      frame_stats[(size_t)f * 4 + 3] = frame_scale(ws, f, 1);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double s[NACC];
+  int64_t n[NACC], kept = 0;
+  for (int i = 0; i < NACC; ++i) s[i] = 0.0, n[i] = 0;
+  for (int f = 0; f < F; ++f) {
+    for (int i = 0; i < NACC; ++i) s[i] += ws.acc_f[(size_t)f * NACC + i], n[i] += ws.cnt_acc_f[(size_t)f * NACC + i];
+    kept += ws.cnt_f[f];
+  }
+  const double data = kept > 0 ? s[A_DATA] / (double)kept : 0.0;
+  double reg = 0.0;
+  for (int k = 0; k < DL_MAX_SCALES; ++k) {
+    const double g = k < scales && n[A_G + k] > 0 ? s[A_G + k] / (double)n[A_G + k] : 0.0;
+    out[8 + k] = g;
+    out[12 + k] = (double)n[A_G + k];
+    reg += g;
+  }
+  const double spatial = alpha > 0.0 ? data + alpha * reg : data;
+  const double stable = n[A_TEMP] > 0 ? s[A_TEMP] / (double)n[A_TEMP] : 0.0;
+  out[0] = spatial;
+  out[1] = stable;
+  out[2] = n[A_ABSREL] > 0 ? s[A_ABSREL] / (double)n[A_ABSREL] : 0.0;
+  out[3] = kept > 0 ? (double)n[A_DATA] / (double)kept : 0.0;
+  out[4] = stable_scale > 0.0 ? spatial + stable_scale * stable : spatial;
+  out[5] = data;
+  out[6] = reg;
+  out[7] = (double)kept;
+  out[16] = (double)n[A_TEMP];
+  out[17] = (double)n[A_ABSREL];
+  out[18] = (double)n[A_DATA];
+  out[19] = 0.0;
+}
+
+}  // namespace
+
+extern "C" size_t vdn_depth_loss_workspace_bytes(int B, int T) {
+  if (B <= 0 || T <= 0) return 0;
+  return sizeof(double) * Ws::slots((size_t)B, (size_t)B * T) + select2_workspace_bytes(B * T);
+}
+
+extern "C" int vdn_depth_loss(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                              double alpha, int scales, double stable_scale, void* workspace, float* scale_shift,
+                              double* frame_stats, int64_t* frame_counts, double* out, vdn_stream stream) {
+  if (!prediction || !target || !mask || !workspace || (!out && !scale_shift)) return VDN_EINVAL;
+  if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || scales < 0) return VDN_EINVAL;
+  if (out && stable_scale > 0.0 && T < 2) return VDN_EINVAL;  // the reference divides by a count of zero strides
+  if ((int64_t)H * W > INT32_MAX || (int64_t)B * T > 65535 || scales > DL_MAX_SCALES) return VDN_EUNSUPPORTED;
+  if (((uintptr_t)prediction & 3) || ((uintptr_t)target & 3) || ((uintptr_t)scale_shift & 3)) return VDN_EALIGN;
+  if (((uintptr_t)workspace & 7) || ((uintptr_t)frame_stats & 7) || ((uintptr_t)frame_counts & 7) || ((uintptr_t)out & 7))
+    return VDN_EALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int F = B * T, hw = H * W;
+  const dim3 grid((unsigned)F * DL_BPF), block(256);
+  // four pixels per lane when every frame of every plane starts on 16 bytes (the mask on 4) and holds whole quads
+  const bool wide = hw % 4 == 0 && !((uintptr_t)prediction & 15) && !((uintptr_t)target & 15) && !((uintptr_t)mask & 3);
+  const Ws ws(workspace, B, T);
+  if (wide) hipLaunchKernelGGL(fit_partial_kernel<4>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
+  else hipLaunchKernelGGL(fit_partial_kernel<1>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
+  hipLaunchKernelGGL(fit_solve_kernel, dim3(1), block, 0, s, workspace, B, T, frame_counts, scale_shift);
+  if (out) {
+    const uint32_t rank = (uint32_t)((hw - 1) / 2);  // torch.median: the lower of the two middle values
+    select2_launch(LossKey{prediction, target, mask, ws.ss, (size_t)hw, T}, F, (size_t)hw, rank, rank, ws.select, s);
+    hipLaunchKernelGGL(median_store_kernel, dim3(grid_for((size_t)F * 2, 1024)), block, 0, s, select2_state(ws.select, F), F, ws.med);
+    const int eff_scales = alpha > 0.0 ? scales : 0;  // the regulariser is skipped, as TrimmedProcrustesLoss skips it
+    const int temporal = stable_scale > 0.0;
+    if (wide) {
+      hipLaunchKernelGGL(deviation_partial_kernel<4>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
+      hipLaunchKernelGGL(loss_partial_kernel<4>, grid, block, 0, s, prediction, target, mask, B, T, H, W, eff_scales, temporal, workspace);
+    } else {
+      hipLaunchKernelGGL(deviation_partial_kernel<1>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
+      hipLaunchKernelGGL(loss_partial_kernel<1>, grid, block, 0, s, prediction, target, mask, B, T, H, W, eff_scales, temporal, workspace);
+    }
+    hipLaunchKernelGGL(loss_finalise_kernel, dim3(1), block, 0, s, workspace, B, T, alpha, eff_scales, stable_scale, frame_stats, out);
+  }
+  VDN_CHECK_LAUNCH();
+  return VDN_OK;
+}

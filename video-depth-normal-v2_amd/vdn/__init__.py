@@ -36,4 +36,7 @@ def __getattr__(name):
     if name == "normals":  # normal_vector and VideoNormalLoss on the device (vdn/normals.py)
         import importlib
         return importlib.import_module(".normals", __name__)
+    if name == "loss":   # VideoDepthLoss on the device (vdn/loss.py)
+        import importlib
+        return importlib.import_module(".loss", __name__)
     raise AttributeError(name)

@@ -429,6 +429,25 @@ class Runtime:
         self._launch(abi.lib.vdn_normal_eval, pred.data_ptr(), target.data_ptr(), int(target.dim() == 3), self._p(mask), F, H, W,
                      ws.data_ptr(), self._p(frame_sums), self._p(frame_counts), out.data_ptr())
 
+    def depth_loss(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor],
+                   alpha: float = 0.5, scales: int = 4, stable_scale: float = 10.0, scale_shift: Optional[torch.Tensor] = None,
+                   frame_stats: Optional[torch.Tensor] = None, frame_counts: Optional[torch.Tensor] = None):
+        """out[0:20] (float64) <- VideoDepthLoss of f32 prediction, target [B, T, H, W] under the u8 mask (vdn_depth_loss;
+        include/vdn.h has the layout). out None: the fit alone, into scale_shift f32 [B, 2]."""
+        B, T, H, W = prediction.shape
+        for t in (prediction, target):
+            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, T, H, W), t.shape
+        assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, T, H, W)
+        assert out is not None or scale_shift is not None
+        assert out is None or (out.dtype == torch.float64 and out.numel() >= 20 and out.is_contiguous())
+        assert scale_shift is None or (scale_shift.dtype == torch.float32 and scale_shift.numel() == 2 * B and scale_shift.is_contiguous())
+        assert frame_stats is None or (frame_stats.dtype == torch.float64 and frame_stats.numel() == 4 * B * T and frame_stats.is_contiguous())
+        assert frame_counts is None or (frame_counts.dtype == torch.int64 and frame_counts.numel() == B * T and frame_counts.is_contiguous())
+        ws = self.buf("depth_loss_ws", (abi.lib.vdn_depth_loss_workspace_bytes(B, T) // 8,), torch.float64)
+        self._launch(abi.lib.vdn_depth_loss, prediction.data_ptr(), target.data_ptr(), mask.data_ptr(), B, T, H, W, float(alpha),
+                     int(scales), float(stable_scale), ws.data_ptr(), self._p(scale_shift), self._p(frame_stats),
+                     self._p(frame_counts), self._p(out))
+
     def minmax(self, x: torch.Tensor, groups: int, out: torch.Tensor):
         """out f32 [groups, 2] <- {min, max} of each of the `groups` equal runs of contiguous f32 x (vdn_minmax_f32)."""
         assert x.is_contiguous() and x.dtype == torch.float32 and x.numel() % groups == 0

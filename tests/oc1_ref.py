@@ -5,21 +5,29 @@ import torch
 import torch.nn.functional as Fn
 
 
-def ac_coords(O, I, dtype, device="cpu"):
+def ac_coords(O, I, dtype, device="cpu", weight="rounded"):
     """align_corners=True source index of every destination index: scale = (I-1)/(O-1), src = scale * dst, evaluated in
-    `dtype` (float32 = the expression of the kernels, float64 = torch's for fp64 tensors)."""
+    `dtype` (float32 = the expression of the kernels, float64 = torch's for fp64 tensors). `weight` is the flavour of
+    csrc/resample.hpp's ac_coord: "rounded" = fl(fl(scale * dst) - i0), "fused" (float32 only) = fl(scale * dst - i0) with one
+    rounding, emulated exactly: the product of two float32 fits a float64, and so does its distance to the integer below."""
     scale = (torch.tensor(I - 1, dtype=dtype) / torch.tensor(O - 1, dtype=dtype)) if O > 1 else torch.tensor(0, dtype=dtype)
     src = scale.to(device) * torch.arange(O, dtype=dtype, device=device)
     i0 = src.to(torch.int64).clamp(max=I - 1)
     i1 = (i0 + 1).clamp(max=I - 1)
+    if weight == "fused":
+        assert dtype == torch.float32
+        exact = scale.double().to(device) * torch.arange(O, dtype=torch.float64, device=device) - i0.double()
+        return i0, i1, exact.float()
+    assert weight == "rounded", weight
     return i0, i1, src - i0.to(dtype)
 
 
-def upsample_nhwc(x, OH, OW, coord=torch.float32):
-    """Bilinear align_corners resize of x [B, h, w, C] with the sample positions computed in `coord`, arithmetic in x.dtype."""
+def upsample_nhwc(x, OH, OW, coord=torch.float32, weight="rounded"):
+    """Bilinear align_corners resize of x [B, h, w, C] with the sample positions computed in `coord` (weights of flavour
+    `weight`), arithmetic in x.dtype."""
     _, h, w, _ = x.shape
-    y0, y1, ly = ac_coords(OH, h, coord, x.device)
-    x0, x1, lx = ac_coords(OW, w, coord, x.device)
+    y0, y1, ly = ac_coords(OH, h, coord, x.device, weight)
+    x0, x1, lx = ac_coords(OW, w, coord, x.device, weight)
     ly, lx = ly.to(x.dtype)[None, :, None, None], lx.to(x.dtype)[None, None, :, None]
     r0, r1 = x[:, y0], x[:, y1]
     top = (1 - lx) * r0[:, :, x0] + lx * r0[:, :, x1]

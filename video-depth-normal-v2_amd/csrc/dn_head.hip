@@ -4,6 +4,7 @@
 //   dn_prologue_kernel  trunk-feature sum + the .view reinterpretation + APE -> frame-major token rows
 //   dn_tail_kernel      conv3x3 48->3 + bias, bilinear resize, residual / ReLU, normal assembly
 #include "common.hpp"
+#include "resample.hpp"
 
 namespace {
 
@@ -80,20 +81,20 @@ __global__ __launch_bounds__(256) void dn_tail_kernel(const float* __restrict__ 
     float acc[3] = {0.f, 0.f, 0.f};
     conv3_at(xf, ws, IH, IW, Cin, oy, ox, acc);
     for (int c = 0; c < 3; ++c) v[c] += acc[c];
-  } else {   // F.interpolate(bilinear, align_corners=True): src = dst * (in - 1) / (out - 1)
-    const float ry = OH > 1 ? (float)(IH - 1) / (float)(OH - 1) : 0.f;
-    const float rx = OW > 1 ? (float)(IW - 1) / (float)(OW - 1) : 0.f;
-    const float sy = ry * oy, sx = rx * ox;
-    const int y0 = min((int)sy, IH - 1), x0 = min((int)sx, IW - 1);
-    const int y1 = min(y0 + 1, IH - 1), x1 = min(x0 + 1, IW - 1);
-    const float wy = sy - y0, wx = sx - x0;
+  } else {   // F.interpolate(bilinear, align_corners=True) of the conv's output, rounded weights (resample.hpp)
+#pragma clang fp contract(off)
+    const auto [y0, y1, wy] = ac_coord<AcWeight::rounded>(oy, ac_scale(IH, OH), IH);
+    const auto [x0, x1, wx] = ac_coord<AcWeight::rounded>(ox, ac_scale(IW, OW), IW);
     float a00[3] = {0.f, 0.f, 0.f}, a01[3] = {0.f, 0.f, 0.f}, a10[3] = {0.f, 0.f, 0.f}, a11[3] = {0.f, 0.f, 0.f};
     conv3_at(xf, ws, IH, IW, Cin, y0, x0, a00);
     conv3_at(xf, ws, IH, IW, Cin, y0, x1, a01);
     conv3_at(xf, ws, IH, IW, Cin, y1, x0, a10);
     conv3_at(xf, ws, IH, IW, Cin, y1, x1, a11);
-    for (int c = 0; c < 3; ++c) {   // the bias is constant over the source pixels and the weights sum to 1
-      const float top = (1.f - wx) * a00[c] + wx * a01[c], bot = (1.f - wx) * a10[c] + wx * a11[c];
+    // The blend, with the roundings this kernel has always had written out (the compiler chose them; a call of bilerp, or
+    // any change to the lines above, made it choose others): (1 - wx) a0 fused into the rounded wx a1, the two rows' products
+    // rounded apart. The bias is constant over the source pixels and the weights sum to 1.
+    for (int c = 0; c < 3; ++c) {
+      const float top = fmaf(1.f - wx, a00[c], wx * a01[c]), bot = fmaf(1.f - wx, a10[c], wx * a11[c]);
       v[c] += (1.f - wy) * top + wy * bot;
     }
   }

@@ -10,6 +10,7 @@
 // two runs give the same bits. Loads are one float per lane (coalesced), so any 4-byte-aligned pointer is accepted.
 #include "common.hpp"
 #include "reduce.hpp"
+#include "resample.hpp"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -262,19 +263,8 @@ __global__ __launch_bounds__(256) void eval_finalise_kernel(void* __restrict__ w
 }
 
 // ---------------------------------------------------------------------------------------------------- resize
-// Half-pixel bilinear: src = fma(in / out, dst + 0.5, -0.5) clamped at 0, the float32 arithmetic of
-// F.interpolate(mode='bilinear', align_corners=False) (its builds contract this expression; a separately rounded product
-// moves a weight by an ulp of the coordinate, 1e-6 of the result); no antialiasing when shrinking (cv2.INTER_LINEAR has none either).
-__device__ __forceinline__ void hp_source(int dst, float scale, int in, int& i0, int& i1, float& w0, float& w1) {
-  float src = fmaf(scale, (float)dst + 0.5f, -0.5f);  // fused, as torch builds it: the weights then match bit for bit
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  i0 = i0 > in - 1 ? in - 1 : i0;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  w1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-  w0 = 1.f - w1;
-}
-
+// Half-pixel bilinear with hp_source's coordinates (resample.hpp); no antialiasing when shrinking (cv2.INTER_LINEAR has none
+// either). The blend below is separately rounded products under this file's contract(off), not resample.hpp's bilerp.
 __global__ __launch_bounds__(256) void resize_bilinear_hp_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total,
                                                                  int IH, int IW, int OH, int OW) {
   const float sh = (float)IH / (float)OH, sw = (float)IW / (float)OW;

@@ -1,21 +1,10 @@
-// Spatial / gather kernels (HBM-bound): bilinear resize, patchify, pos-embed bicubic, depth tail,
-// MaskDownSampler stages, depthwise 7x7.
+// Spatial / gather kernels (HBM-bound): bilinear resize, patchify, pos-embed bicubic, cubic preprocess, head output,
+// MaskDownSampler stages, depthwise 7x7, oc1 combine. (The fused depth tail is tail.hip.)
 #include "common.hpp"
+#include "resample.hpp"
 #include <stddef.h>
 
 namespace {
-
-// PyTorch's align_corners=True source index: scale = (in-1)/(out-1) in float, src = scale * dst, and the weight is taken
-// from that ROUNDED product. Contracted into fma(scale, dst, -i0) the weight is the more exact one, but it is then up to
-// 2^-24 src away from PyTorch's: 4e-4 of a depth of 10 at a 1080-row frame.
-__device__ __forceinline__ void ac_coord(int o, float scale, int in, int& i0, int& i1, float& l1) {
-#pragma clang fp contract(off)
-  const float src = scale * (float)o;
-  i0 = (int)src;
-  i0 = i0 < in - 1 ? i0 : in - 1;
-  i1 = i0 < in - 1 ? i0 + 1 : i0;
-  l1 = src - (float)i0;
-}
 
 template <int DT>
 __global__ __launch_bounds__(256) void upsample_kernel(const typename Half<DT>::T* __restrict__ x,
@@ -27,8 +16,7 @@ __global__ __launch_bounds__(256) void upsample_kernel(const typename Half<DT>::
   using V8 = typename Half<DT>::V8;
   const int cv = C >> 3;
   const size_t total = (size_t)B * OH * OW * cv;
-  const float sy = OH > 1 ? (float)(IH - 1) / (float)(OH - 1) : 0.f;
-  const float sx = OW > 1 ? (float)(IW - 1) / (float)(OW - 1) : 0.f;
+  const float sy = ac_scale(IH, OH), sx = ac_scale(IW, OW);
   for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int c8 = (int)(i % cv);
     size_t pix = i / cv;
@@ -36,10 +24,8 @@ __global__ __launch_bounds__(256) void upsample_kernel(const typename Half<DT>::
     pix /= OW;
     const int oy = (int)(pix % OH);
     const int b = (int)(pix / OH);
-    int y0, y1, x0, x1;
-    float ly, lx;
-    ac_coord(oy, sy, IH, y0, y1, ly);
-    ac_coord(ox, sx, IW, x0, x1, lx);
+    const auto [y0, y1, ly] = ac_coord<AcWeight::rounded>(oy, sy, IH);
+    const auto [x0, x1, lx] = ac_coord<AcWeight::rounded>(ox, sx, IW);
     const size_t xo = (size_t)b * IH * IW * C + c8 * 8;
     const size_t o00 = xo + ((size_t)y0 * IW + x0) * C, o01 = xo + ((size_t)y0 * IW + x1) * C;
     const size_t o10 = xo + ((size_t)y1 * IW + x0) * C, o11 = xo + ((size_t)y1 * IW + x1) * C;
@@ -54,9 +40,7 @@ __global__ __launch_bounds__(256) void upsample_kernel(const typename Half<DT>::
     for (int e = 0; e < 8; ++e) {
       float a00 = (float)v00[e], a01 = (float)v01[e], a10 = (float)v10[e], a11 = (float)v11[e];
       if (xl) { a00 += (float)l00[e]; a01 += (float)l01[e]; a10 += (float)l10[e]; a11 += (float)l11[e]; }
-      const float top = (1.f - lx) * a00 + lx * a01;
-      const float bot = (1.f - lx) * a10 + lx * a11;
-      const float r = (1.f - ly) * top + ly * bot;
+      const float r = bilerp(a00, a01, a10, a11, lx, ly);
       if (yl) { T a, b2; split_rtz(r, a, b2); o[e] = a; ol[e] = b2; }
       else o[e] = (T)r;
     }
@@ -68,21 +52,16 @@ __global__ __launch_bounds__(256) void upsample_kernel(const typename Half<DT>::
 __global__ __launch_bounds__(256) void upsample_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int B,
                                                            int IH, int IW, int OH, int OW, int relu) {
   const size_t total = (size_t)B * OH * OW;
-  const float sy = OH > 1 ? (float)(IH - 1) / (float)(OH - 1) : 0.f;
-  const float sx = OW > 1 ? (float)(IW - 1) / (float)(OW - 1) : 0.f;
+  const float sy = ac_scale(IH, OH), sx = ac_scale(IW, OW);
   for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int ox = (int)(i % OW);
     const size_t t = i / OW;
     const int oy = (int)(t % OH);
     const int b = (int)(t / OH);
-    int y0, y1, x0, x1;
-    float ly, lx;
-    ac_coord(oy, sy, IH, y0, y1, ly);
-    ac_coord(ox, sx, IW, x0, x1, lx);
+    const auto [y0, y1, ly] = ac_coord<AcWeight::rounded>(oy, sy, IH);
+    const auto [x0, x1, lx] = ac_coord<AcWeight::rounded>(ox, sx, IW);
     const float* xb = x + (size_t)b * IH * IW;
-    const float top = (1.f - lx) * xb[y0 * IW + x0] + lx * xb[y0 * IW + x1];
-    const float bot = (1.f - lx) * xb[y1 * IW + x0] + lx * xb[y1 * IW + x1];
-    float v = (1.f - ly) * top + ly * bot;
+    float v = bilerp(xb[y0 * IW + x0], xb[y0 * IW + x1], xb[y1 * IW + x0], xb[y1 * IW + x1], lx, ly);
     if (relu) v = fmaxf(v, 0.f);
     y[i] = v;
   }
@@ -131,17 +110,8 @@ __global__ void fill_row_kernel(float* __restrict__ x, const float* __restrict__
   x[((size_t)b * rows_per_b + row) * C + c] = vec[c];
 }
 
-// torch upsample_bicubic2d (A = -0.75), align_corners=False with an explicit scale factor:
-// src = (dst + 0.5) / scale - 0.5, border-clamped taps.
-__device__ __forceinline__ void cubic_w(float t, float w[4]) {
-  const float A = -0.75f;
-  const float x0 = t + 1.f, x1 = t, x2 = 1.f - t, x3 = 2.f - t;
-  w[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
-  w[1] = ((A + 2.f) * x1 - (A + 3.f)) * x1 * x1 + 1.f;
-  w[2] = ((A + 2.f) * x2 - (A + 3.f)) * x2 * x2 + 1.f;
-  w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
-}
-
+// torch upsample_bicubic2d (A = -0.75), align_corners=False with an explicit scale factor: src = (dst + 0.5) / scale - 0.5
+// (hp_src), border-clamped taps.
 __global__ void bicubic_kernel(const float* __restrict__ src, float* __restrict__ dst, int ih, int iw, int oh, int ow,
                                int C, float inv_sy, float inv_sx) {
   const size_t total = (size_t)oh * ow * C;
@@ -149,40 +119,20 @@ __global__ void bicubic_kernel(const float* __restrict__ src, float* __restrict_
     const int c = (int)(i % C);
     const size_t p = i / C;
     const int ox = (int)(p % ow), oy = (int)(p / ow);
-    const float fy = ((float)oy + 0.5f) * inv_sy - 0.5f;
-    const float fx = ((float)ox + 0.5f) * inv_sx - 0.5f;
+    const float fy = hp_src(oy, inv_sy), fx = hp_src(ox, inv_sx);
     const int iy = (int)floorf(fy), ix = (int)floorf(fx);
     float wy[4], wx[4];
-    cubic_w(fy - (float)iy, wy);
-    cubic_w(fx - (float)ix, wx);
+    const CubicTaps ty = cubic_taps(iy, fy - (float)iy, ih, wy), tx = cubic_taps(ix, fx - (float)ix, iw, wx);
     float acc = 0.f;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      int yy = iy - 1 + a;
-      yy = yy < 0 ? 0 : (yy > ih - 1 ? ih - 1 : yy);
       float rowv = 0.f;
 #pragma unroll
-      for (int bq = 0; bq < 4; ++bq) {
-        int xx = ix - 1 + bq;
-        xx = xx < 0 ? 0 : (xx > iw - 1 ? iw - 1 : xx);
-        rowv += wx[bq] * src[((size_t)yy * iw + xx) * C + c];
-      }
+      for (int bq = 0; bq < 4; ++bq) rowv += wx[bq] * src[((size_t)ty.idx(a) * iw + tx.idx(bq)) * C + c];
       acc += wy[a] * rowv;
     }
     dst[i] = acc;
   }
-}
-
-// Half-pixel source coordinate (o + 0.5) * in / out - 0.5 = num / den with num = (2 o + 1) in - out, den = 2 out, split
-// EXACTLY into its floor and its fraction: an fp32 product with a rounded in / out is off by up to 2^-24 of the coordinate,
-// which at a 1080-row frame moves the fraction (and with it every cubic weight) by 1e-4. 64-bit: num reaches 2 in out.
-// The fraction's numerator is below den, so both conversions are exact while out < 2^23 and the quotient is rounded once.
-__device__ __forceinline__ void halfpixel_coord(int o, int in, int out, int& i, float& t) {
-  const long long den = 2ll * out, num = (2ll * o + 1) * in - out;
-  long long q = num / den, r = num - q * den;
-  if (r < 0) { r += den; --q; }   // floor, not truncation: num < 0 left of / above the first source centre when up-scaling
-  i = (int)q;
-  t = (float)r / (float)den;
 }
 
 // vdn_preprocess: the whole pre-processing of a batch of frames in one launch — u8 [n,h,w,3] (RGB, or BGR with swap_rb) ->
@@ -201,20 +151,15 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     halfpixel_coord(oy, ih, oh, iy, ty);
     halfpixel_coord(ox, iw, ow, ix, tx);
     float wy[4], wx[4];
-    cubic_w(ty, wy);
-    cubic_w(tx, wx);
+    const CubicTaps cy = cubic_taps(iy, ty, ih, wy), cx = cubic_taps(ix, tx, iw, wx);
     const uint8_t* img = src + (size_t)f * ih * iw * 3;
     float acc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      int yy = iy - 1 + a;
-      yy = yy < 0 ? 0 : (yy > ih - 1 ? ih - 1 : yy);
       float rowv[3] = {0.f, 0.f, 0.f};
 #pragma unroll
       for (int bq = 0; bq < 4; ++bq) {
-        int xx = ix - 1 + bq;
-        xx = xx < 0 ? 0 : (xx > iw - 1 ? iw - 1 : xx);
-        const uint8_t* px = img + ((size_t)yy * iw + xx) * 3;
+        const uint8_t* px = img + ((size_t)cy.idx(a) * iw + cx.idx(bq)) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) rowv[c] += wx[bq] * ((float)px[c] / 255.0f);
       }
@@ -406,10 +351,6 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const float* __restrict__ 
 // pixels x CS channels and stages the source patch those read (11 x 11 pixels at scale 1/2) in LDS once: z crosses the
 // memory system about twice (halo) instead of 36 times.
 constexpr int OC_T = 16, OC_NT = 512;  // output tile side, threads per workgroup
-__host__ __device__ inline int oc_src0(int o, float scale, int in) {  // ac_coord's i0
-  const int i0 = (int)(scale * (float)o);
-  return i0 < in - 1 ? i0 : in - 1;
-}
 template <int CS>
 __global__ __launch_bounds__(OC_NT) void oc1_combine_kernel(const float* __restrict__ z, const float* __restrict__ bias,
                                                           float* __restrict__ out, int IH, int IW, int OH, int OW, int Co,
@@ -417,8 +358,7 @@ __global__ __launch_bounds__(OC_NT) void oc1_combine_kernel(const float* __restr
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sz = (float*)smem;  // [patch pixel][tap][CS]
   constexpr int V = CS / 4;
-  const float sy = OH > 1 ? (float)(IH - 1) / (float)(OH - 1) : 0.f;
-  const float sx = OW > 1 ? (float)(IW - 1) / (float)(OW - 1) : 0.f;
+  const float sy = ac_scale(IH, OH), sx = ac_scale(IW, OW);
   const int slices = Co / CS, txn = (OW + OC_T - 1) / OC_T, tyn = (OH + OC_T - 1) / OC_T;
   int bid = blockIdx.x;
   const int cs = (bid % slices) * CS;
@@ -428,10 +368,9 @@ __global__ __launch_bounds__(OC_NT) void oc1_combine_kernel(const float* __restr
   const int oy0 = (bid % tyn) * OC_T, b = bid / tyn;
   // source rows / columns that the tile's sample positions [o0 - 1, o0 + OC_T] (clipped to the map) touch
   const int ylast = oy0 + OC_T < OH - 1 ? oy0 + OC_T : OH - 1, xlast = ox0 + OC_T < OW - 1 ? ox0 + OC_T : OW - 1;
-  const int py0 = oc_src0(oy0 > 0 ? oy0 - 1 : 0, sy, IH), px0 = oc_src0(ox0 > 0 ? ox0 - 1 : 0, sx, IW);
-  int py1 = oc_src0(ylast, sy, IH), px1 = oc_src0(xlast, sx, IW);
-  py1 = py1 < IH - 1 ? py1 + 1 : py1;
-  px1 = px1 < IW - 1 ? px1 + 1 : px1;
+  constexpr AcWeight R = AcWeight::rounded;  // the materialised map's flavour
+  const int py0 = ac_coord<R>(oy0 > 0 ? oy0 - 1 : 0, sy, IH).i0, px0 = ac_coord<R>(ox0 > 0 ? ox0 - 1 : 0, sx, IW).i0;
+  const int py1 = ac_coord<R>(ylast, sy, IH).i1, px1 = ac_coord<R>(xlast, sx, IW).i1;
   const int nph = py1 - py0 + 1, npw = px1 - px0 + 1;
   if (nph * npw > max_pix) return;  // the host sized the LDS for every tile of this shape: never taken
   const float* zb = z + ((size_t)b * IH * IW) * 9 * Co + cs;
@@ -464,21 +403,18 @@ __global__ __launch_bounds__(OC_NT) void oc1_combine_kernel(const float* __restr
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
       const int xx = ox + kx - 1;
-      int x0 = 0, x1 = 0;
-      float l = 0.f;
-      if (xx >= 0 && xx < OW) ac_coord(xx, sx, IW, x0, x1, l);
-      xa[kx] = (x0 - px0) * 9 * CS;
-      xb[kx] = (x1 - px0) * 9 * CS;
-      xl[kx] = l;
+      AcCoord cx = {0, 0, 0.f};
+      if (xx >= 0 && xx < OW) cx = ac_coord<R>(xx, sx, IW);
+      xa[kx] = (cx.i0 - px0) * 9 * CS;
+      xb[kx] = (cx.i1 - px0) * 9 * CS;
+      xl[kx] = cx.l1;
     }
     f32x4 acc = *(const f32x4*)(bias + cs + v * 4);
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
       const int yy = oy + ky - 1;
       if (yy < 0 || yy >= OH) continue;
-      int y0, y1;
-      float ly;
-      ac_coord(yy, sy, IH, y0, y1, ly);
+      const auto [y0, y1, ly] = ac_coord<R>(yy, sy, IH);
       const float* r0 = sz + (size_t)(y0 - py0) * npw * 9 * CS + v * 4;
       const float* r1 = sz + (size_t)(y1 - py0) * npw * 9 * CS + v * 4;
 #pragma unroll
@@ -489,7 +425,7 @@ __global__ __launch_bounds__(OC_NT) void oc1_combine_kernel(const float* __restr
         const float lx = xl[kx];
         const f32x4 a00 = *(const f32x4*)(r0 + xa[kx] + t), a01 = *(const f32x4*)(r0 + xb[kx] + t);
         const f32x4 a10 = *(const f32x4*)(r1 + xa[kx] + t), a11 = *(const f32x4*)(r1 + xb[kx] + t);
-        // the four corner weights once per tap instead of three lerps per channel (the kernel is VALU- and LDS-heavy)
+        // not bilerp, on purpose: the four corner weights once per tap instead of three lerps per channel (VALU- and LDS-heavy)
         const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
         acc += w00 * a00 + w01 * a01 + (w10 * a10 + w11 * a11);
       }
@@ -529,20 +465,17 @@ extern "C" int vdn_oc1_combine(const float* z, const float* bias, float* out, in
   if (!z || !bias || !out || B <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || Co <= 0) return VDN_EINVAL;
   if ((Co & 15) || (((uintptr_t)z | (uintptr_t)bias | (uintptr_t)out) & 15)) return VDN_EALIGN;
   // the largest source patch any tile stages, with the kernel's own expressions
-  const float sy = OH > 1 ? (float)(IH - 1) / (float)(OH - 1) : 0.f;
-  const float sx = OW > 1 ? (float)(IW - 1) / (float)(OW - 1) : 0.f;
-  auto span = [](int O, int I, float s) {
+  auto span = [](int O, int I) {
+    const float s = ac_scale(I, O);
     int worst = 0;
     for (int o0 = 0; o0 < O; o0 += OC_T) {
       const int last = o0 + OC_T < O - 1 ? o0 + OC_T : O - 1;
-      int p1 = oc_src0(last, s, I);
-      p1 = p1 < I - 1 ? p1 + 1 : p1;
-      const int n = p1 - oc_src0(o0 > 0 ? o0 - 1 : 0, s, I) + 1;
+      const int n = ac_coord<AcWeight::rounded>(last, s, I).i1 - ac_coord<AcWeight::rounded>(o0 > 0 ? o0 - 1 : 0, s, I).i0 + 1;
       worst = n > worst ? n : worst;
     }
     return worst;
   };
-  const int max_pix = span(OH, IH, sy) * span(OW, IW, sx);
+  const int max_pix = span(OH, IH) * span(OW, IW);
   constexpr int CS = 16;  // 11 x 11 pixels x 9 taps x 16 channels x 4 B = 68 KiB: two workgroups per CU
   const size_t lds = (size_t)max_pix * 9 * CS * sizeof(float);
   if (lds > 160 * 1024) return VDN_EUNSUPPORTED;  // scale well above 1/2: not a 2x up-sampling

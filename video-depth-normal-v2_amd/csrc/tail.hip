@@ -23,6 +23,7 @@
 //          halves summed through LDS, one coalesced store per tile row.
 // Roofline: MFMA (19.8 GF per 518 x 518 frame at C = 128, x3 executed); HBM traffic = out1 once (+ halo) + depth.
 #include "common.hpp"
+#include "resample.hpp"
 
 namespace {
 
@@ -33,13 +34,9 @@ constexpr int PLANE = PH * PWS * 64;                                        // b
 constexpr int SP = 13, SPLANE = SP * SP * 64;                               // source (out1) patch: 13 x 13 pixels x 32 f32 = 2 SPLANE bytes
 constexpr int SLOADS = (SP * SP * 4 * 2 + 255) / 256;                       // 16-byte source loads per thread and pass
 
-__device__ __forceinline__ void ac_coord(int o, float scale, int in, int& i0, int& i1, float& l1) {
-  const float src = scale * (float)o;  // PyTorch's align_corners=True source index (same as upsample_kernel)
-  i0 = (int)src;
-  i0 = i0 < in - 1 ? i0 : in - 1;
-  i1 = i0 < in - 1 ? i0 + 1 : i0;
-  l1 = src - (float)i0;
-}
+// Every coordinate of this kernel is ac_coord<AcWeight::fused>: the weight is fma(scale, dst, -i0), one rounding, NOT the
+// rounded-product weight of upsample_kernel (resample.hpp; tests/test_gpu_resample.py holds it in place).
+constexpr AcWeight FUSED = AcWeight::fused;
 
 template <int DT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void depth_tail_kernel(const float* __restrict__ x, int B, int IH, int IW,
@@ -60,8 +57,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int b = tile / (tiles_x * tiles_y);
   const int trem = tile - b * tiles_x * tiles_y;
   const int ty0 = (trem / tiles_x) * TH, tx0 = (trem % tiles_x) * TW;
-  const float sy = OH > 1 ? (float)(IH - 1) / (float)(OH - 1) : 0.f;
-  const float sx = OW > 1 ? (float)(IW - 1) / (float)(OW - 1) : 0.f;
+  const float sy = ac_scale(IH, OH), sx = ac_scale(IW, OW);
   const float* xb = x + (size_t)b * IH * IW * C;
 
   // wave (wj, wr): output channels 16 wj .. 16 wj + 15 of tile rows 8 wr .. 8 wr + 7. One 16-channel block per wave
@@ -88,11 +84,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       abase[kx][rm] = smem + (wr * 8 * PWS + fr + kx) * 64 + ((fq ^ ((rm + ((fr + kx) >> 2)) & 3)) << 4);
 
   // ---- source patch: origin = the source pixel under the halo's first row / column
-  int dummy;
-  float dl;
-  int sy0, sx0;
-  ac_coord(ty0 > 0 ? ty0 - 1 : 0, sy, IH, sy0, dummy, dl);
-  ac_coord(tx0 > 0 ? tx0 - 1 : 0, sx, IW, sx0, dummy, dl);
+  const int sy0 = ac_coord<FUSED>(ty0 > 0 ? ty0 - 1 : 0, sy, IH).i0, sx0 = ac_coord<FUSED>(tx0 > 0 ? tx0 - 1 : 0, sx, IW).i0;
   // LDS-DMA of the patch: item = (pixel, 4-float piece) in LDS order, 16 B per lane, 1 KiB per wave-instruction; no
   // registers are held while it is in flight (a register-staged prefetch across the MFMA phase spilled)
   auto dma_src = [&](int cb) {
@@ -135,10 +127,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int e = 0; e < 8; ++e) { oh[e] = (T)0.f; ol[e] = (T)0.f; }
       if (gy >= 0 && gy < OH && gx >= 0 && gx < OW) {
-        int y0, y1, x0, x1;
-        float ly, lx;
-        ac_coord(gy, sy, IH, y0, y1, ly);
-        ac_coord(gx, sx, IW, x0, x1, lx);
+        const auto [y0, y1, ly] = ac_coord<FUSED>(gy, sy, IH);
+        const auto [x0, x1, lx] = ac_coord<FUSED>(gx, sx, IW);
         const float* c00 = (const float*)ssrc + ((y0 - sy0) * SP + (x0 - sx0)) * 32 + ch * 8;
         const float* c01 = (const float*)ssrc + ((y0 - sy0) * SP + (x1 - sx0)) * 32 + ch * 8;
         const float* c10 = (const float*)ssrc + ((y1 - sy0) * SP + (x0 - sx0)) * 32 + ch * 8;
@@ -247,8 +237,7 @@ extern "C" int vdn_depth_tail(int dt, const float* x, int B, int IH, int IW, int
   if (!x || !w || !w_lo || !bias2 || !w1 || !depth || B <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return VDN_EINVAL;
   if (C <= 0 || (C % CB) || ldb < 9 * C || (ldb & 7)) return VDN_EALIGN;
   // the 13 x 13 source patch must cover the 18-pixel halo of a tile: floor(17 s) + 3 <= 13 for both scales
-  const float sy = OH > 1 ? (float)(IH - 1) / (float)(OH - 1) : 0.f, sx = OW > 1 ? (float)(IW - 1) / (float)(OW - 1) : 0.f;
-  if ((int)(17.f * sy) + 3 > SP || (int)(17.f * sx) + 3 > SP) return VDN_EUNSUPPORTED;
+  if ((int)(17.f * ac_scale(IH, OH)) + 3 > SP || (int)(17.f * ac_scale(IW, OW)) + 3 > SP) return VDN_EUNSUPPORTED;
   if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)w_lo | (uintptr_t)bias2 | (uintptr_t)w1) & 15) return VDN_EALIGN;
   const int tiles = B * ((OH + TH - 1) / TH) * ((OW + TW - 1) / TW);
   hipStream_t s = (hipStream_t)stream;

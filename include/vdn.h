@@ -418,7 +418,8 @@ int vdn_normal_eval(const float* pred, const float* target, int target_is_depth,
                     int W, void* workspace, double* frame_sums, int64_t* frame_counts, double* out, vdn_stream stream);
 
 /* The depth criterion on the device: VideoDepthLoss of loss/loss.py:326-367 as the reference's scripts construct it
- * (trim = 0, batch-based reduction, no SSIM term), forward only; scripts/train*.py validate:
+ * (trim = 0, batch-based reduction, no SSIM term), the forward (its gradient: vdn_depth_loss_backward below);
+ * scripts/train*.py validate:
  *     loss_dict = criterion(prediction=pred, target=gt, mask=valid)      (all [B, T, H, W])
  * prediction, target f32 [B, T, H, W] row-major, mask u8 [B, T, H, W] (non-zero = keep, required). Stateless, caller's
  * stream, caller-owned buffers.
@@ -464,6 +465,58 @@ size_t vdn_depth_loss_workspace_bytes(int B, int T);
 int vdn_depth_loss(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
                    double alpha, int scales, double stable_scale, void* workspace, float* scale_shift,
                    double* frame_stats, int64_t* frame_counts, double* out, vdn_stream stream);
+
+/* The gradient of that criterion with respect to `prediction`: what autograd computes in the training step of
+ * scripts/train*.py (total_loss.backward()) for
+ *     L = c_sp * spatial_loss + c_st * stable_loss + c_ar * absRel_loss
+ * where coeff f32 [3] = {c_sp, c_st, c_ar} is read on the device (no host synchronisation): for upstream gradients g of the
+ * dictionary's entries, c_sp = g_total + g_spatial, c_st = stable_scale * g_total + g_stable, c_ar = g_absRel. d1 is piecewise
+ * constant: its gradient is zero. Gradients with respect to target, and second derivatives, are not computed.
+ * prediction, target, mask, B .. stable_scale are the arguments of the vdn_depth_loss call whose outputs are passed here:
+ * scale_shift f32 [B][2], frame_stats f64 [B * T][4], frame_counts i64 [B * T] and out f64 [20], all required. The fit's
+ * solve, the select and the deviation pass are not run again; the four masked sums of the fit, which the forward does not
+ * return, are summed again in the forward's order. grad_prediction f32 [B, T, H, W] is written everywhere.
+ * Arithmetic (fp64 from the f32 samples, contraction off; the two f32 roundings of a have the derivative 1; sign(0) = 0, as
+ * in the backward of torch.abs). With k the keep mask, (sc, sh) the forward's f32 pair, m, s the median and scale of a, cnt
+ * = n_f, x = (a - m) / s and d = x - y the difference of the normalised maps:
+ *   g_x     at a kept pixel: c_sp * (sign(d) / M + alpha * (n_0 / M_0 + n_1 / M_1 + ...)), M = out[7], M_k = out[12 + k],
+ *           n_k = the sum over the pixel's kept neighbours at stride 2^k (left, right, upper, lower, inside its frame) on
+ *           each grid k it belongs to of sign(d_self - d_nb), an integer; grids with M_k == 0 add nothing; k ascending.
+ *           A gather: no lane writes another lane's pixel.
+ *   frame   g_s = -sum g_x x / s when cnt > 0 and sum_keep |a - m| / cnt >= 1e-6 (the clamp passes nothing below its
+ *           bound), else 0; sigma = sum_keep sign(a - m); g_m = -sum g_x / s - g_s * sigma / cnt (0 when cnt == 0).
+ *   g_a     g_x / s + g_s * sign(a - m) / cnt
+ *           + g_m at the median's holder: the kept pixel of lowest index whose a equals m. Nobody holds it when the frame
+ *             keeps nothing, or when m == 0 and the frame has a dropped pixel: the median is then taken to be the 0 of a
+ *             dropped pixel, where the reference's mask * a has the derivative 0.
+ *           + c_st * (e_later - e_earlier) / out[16]: for a pair (t - 1, t) of one item that the forward counts (kept in both
+ *             frames, |tg| < th[b, t], the same f32 decisions), e = sign(pg - tg) at the later frame's pixel and the same at
+ *             the earlier frame's, where it is subtracted. Only when stable_scale > 0.
+ *           + c_ar * sign(a - target) / (target * out[17]) where the forward counts the pixel for absRel.
+ *   fit     per item G0 = sum_keep g_a p, G1 = sum_keep g_a, D = det + 1e-6;
+ *           g_p = sc * g_a + (G0 * (dN0 - sc * dD) + G1 * (dN1 - sh * dD)) / D at a kept pixel, with dN0 = a11 t - b1,
+ *           dN1 = -b0 - a01 t + 2 p b1, dD = 2 (p a11 - a01); rounded to f32 once. An item with det == 0 has gradient 0.
+ * A dropped pixel's gradient is +0.0 and it is skipped by a branch: NaN or inf under it reaches nothing.
+ * Passes: per-frame sums in 32 blocks per frame, a one-block solve (g_s, g_m, holder, threshold, the fit's sums), the sums
+ * G0 and G1 in 32 blocks per frame, a one-block solve, the write. No atomics; sums have the forward's fixed order (the
+ * holder is a minimum over indices): two runs give the same bits.
+ * The first pass leaves g_x in an fp64 plane of the workspace, the second turns it into g_a in place and the third reads it,
+ * so the workspace is vdn_depth_loss_backward_workspace_bytes(B, T, H, W) bytes: a part that depends on B and T alone plus
+ * B * T * H * W * 8, 8-byte aligned. (Recomputing g_x in every pass instead was measured and dropped: DESIGN 5.14.)
+ * Load shapes and bits. Where H * W is a multiple of 4 a lane owns four consecutive pixels, read with one 16-byte load per
+ * plane (and written with one store) when prediction, target and grad_prediction are 16-byte aligned and the mask 4-byte
+ * aligned, and with a load per pixel otherwise; else a lane owns one pixel. The order of every sum therefore depends on the
+ * shape alone, never on where a tensor starts: for the same forward state the gradient has the same bits at any alignment.
+ * (vdn_depth_loss itself sums a misaligned tensor one pixel per lane, so its fp64 per-frame scales may differ in the last
+ * place between two alignments of the same data; the gradient inherits exactly that difference and adds none.)
+ * Errors as vdn_depth_loss, returned before anything is launched: VDN_EINVAL for a null pointer (every pointer is
+ * required), a size <= 0, scales < 0, or T < 2 with stable_scale > 0; VDN_EUNSUPPORTED for H * W > INT32_MAX, B * T > 65535,
+ * scales > 4; VDN_EALIGN for a float pointer off 4 bytes or workspace, frame_stats, frame_counts or out off 8. */
+size_t vdn_depth_loss_backward_workspace_bytes(int B, int T, int H, int W);
+int vdn_depth_loss_backward(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                            double alpha, int scales, double stable_scale, const float* scale_shift,
+                            const double* frame_stats, const int64_t* frame_counts, const double* out, const float* coeff,
+                            void* workspace, float* grad_prediction, vdn_stream stream);
 
 /* The colourised depth the reference's front ends write to disk, made on the device. Replaces, per frame, run.py:59-71,
  * run_video.py:75-89 and metric_depth/run.py:67-78 (min/max of the frame, matplotlib palette or a grey triple, BGR,

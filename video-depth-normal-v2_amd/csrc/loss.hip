@@ -22,22 +22,14 @@
 #include <math.h>
 
 #pragma clang fp contract(off)
+#include "loss_px.hpp"
 
 namespace {
 
-constexpr int DL_BPF = 32;        // blocks per frame, fixed so that the workspace depends on B and T alone
-constexpr int DL_MAX_SCALES = 4;  // the reference's default, and all its scripts construct
 constexpr int NACC = 3 + DL_MAX_SCALES;
 // accumulator slots of the fused pass: doubles {data, absRel, temporal, g_0 .. g_3 numerators}, integers {absRel count,
 // d1 hits, temporal count, M_0 .. M_3}
 enum { A_DATA = 0, A_ABSREL = 1, A_TEMP = 2, A_G = 3 };
-
-struct MinOp {
-  __device__ __forceinline__ float operator()(float a, float b) const { return b < a ? b : a; }
-};
-struct MaxOp {
-  __device__ __forceinline__ float operator()(float a, float b) const { return b > a ? b : a; }
-};
 
 // workspace, in 8-byte slots
 struct Ws {
@@ -75,30 +67,6 @@ struct Ws {
     cnt_acc_f = (int64_t*)q, q += F * NACC;
     ss = (float*)q, q += B;
     select = q;
-  }
-};
-
-// Two roundings. Plain operators, which the pragma above keeps apart: the bodies of __fmul_rn and __fadd_rn are compiled under
-// the header's contraction mode, and once inlined the pair becomes one v_fma_f32.
-__device__ __forceinline__ float aligned(float scale, float p, float shift) {
-  const float m = scale * p;
-  return m + shift;
-}
-
-// PPL consecutive pixels of a frame: 4 (one 16-byte load per float plane, one 4-byte load of the mask) or 1
-template <int PPL>
-struct Px {
-  float p[PPL], t[PPL];
-  bool k[PPL];
-  __device__ __forceinline__ Px(const float* __restrict__ pf, const float* __restrict__ tf, const uint8_t* __restrict__ mf, int i) {
-    if (PPL == 4) {
-      const f32x4 v = *(const f32x4*)(pf + i), w = *(const f32x4*)(tf + i);
-      const uint32_t m = *(const uint32_t*)(mf + i);
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) p[j] = v[j], t[j] = w[j], k[j] = ((m >> (8 * j)) & 0xFFu) != 0;
-    } else {
-      p[0] = pf[i], t[0] = tf[i], k[0] = mf[i] != 0;
-    }
   }
 };
 

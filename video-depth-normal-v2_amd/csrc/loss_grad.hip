@@ -1,0 +1,406 @@
+// The gradient of the depth criterion (loss.hip) with respect to its prediction, on the device: what autograd computes for
+//   L = c_sp * spatial_loss + c_st * stable_loss + c_ar * absRel_loss
+// of the reference's VideoDepthLoss (d1 is piecewise constant), from the state the forward left: the float32 fit, the
+// per-frame medians, scales and counts, and out[20]. include/vdn.h (vdn_depth_loss_backward) states the arithmetic.
+//   stats      per frame in DL_BPF blocks: sum g_x, sum g_x x, sum |a - m| (for the clamp's branch), sigma = sum sign(a - m),
+//              the lowest index of a kept pixel with a == m, the masked min / max of the target, and the four sums of the fit
+//   solve 1    one block: g_s, g_m, the median's holder and the float32 temporal threshold per frame; the fit's sums per item
+//   fit sums   g_a per kept pixel; per frame in DL_BPF blocks sum g_a p and sum g_a
+//   solve 2    one block: an item's frames in index order
+//   write      g_p = sc g_a + keep * (fit correction), rounded to float32 once; +0.0 at a dropped pixel
+// g_x is a gather: a pixel reads its left, right, upper and lower neighbour at stride 2^k on every grid it belongs to, inside
+// its own frame, and no lane writes another lane's pixel. There are no atomics; sums have the forward's fixed order.
+// Pass 1 leaves g_x in an fp64 plane of the workspace, pass 3 turns it into g_a in place and pass 5 reads it, so the stencil is
+// evaluated once. The alternative, every pass recomputing g_x from the inputs with a workspace that depends on B and T alone,
+// was measured and dropped: 679 against 380 us for the launch at [1, 32, 518, 518] (profiles/depth_loss_grad.md).
+// A lane owns four consecutive pixels whenever H * W is a multiple of 4, with 16-byte loads where the bases allow and a load
+// per pixel otherwise, so the sums and the gradient's bits do not depend on the tensors' alignment; one pixel per lane else.
+// Everything is fp64 computed from the float32 samples, contraction off; a dropped pixel is skipped by a branch.
+#include "common.hpp"
+#include "reduce.hpp"
+#include <limits.h>
+#include <math.h>
+
+#pragma clang fp contract(off)
+#include "loss_px.hpp"
+
+namespace {
+
+constexpr int NSUM = 7;  // sum g_x, sum g_x x, sum |a - m|, sum p^2, sum p, sum p t, sum t
+enum { I_A00 = 0, I_A01, I_A11, I_B0, I_B1, I_D, I_OK, I_G0, I_G1, I_SLOTS };
+
+struct IntMinOp {
+  __device__ __forceinline__ int operator()(int a, int b) const { return b < a ? b : a; }
+};
+
+// workspace, in 8-byte slots
+struct Gw {
+  double* sum_b;     // [F][DL_BPF][NSUM]
+  int64_t* sig_b;    // [F][DL_BPF] sigma
+  int64_t* hold_b;   // [F][DL_BPF] lowest index with a == m, INT_MAX for none
+  float* mm_b;       // [F][DL_BPF][2] block min, max of the kept target
+  double* G_b;       // [F][DL_BPF][2] block sums g_a p, g_a
+  double* fit_f;     // [F][4]
+  double* gsm;       // [F][2] g_s, g_m
+  int64_t* hold_f;   // [F] the holder's index in the frame, -1 for nobody
+  float* th;         // [F] (a slot each)
+  double* item;      // [B][I_SLOTS]
+  double* plane;     // [F][H W] g_x, then g_a
+  __host__ __device__ static size_t slots(size_t B, size_t F) { return F * DL_BPF * (NSUM + 1 + 1 + 1 + 2) + F * (4 + 2 + 1 + 1) + B * I_SLOTS; }
+  __host__ __device__ Gw(void* p, int B, int T) {
+    const size_t F = (size_t)B * T, FB = F * DL_BPF;
+    double* q = (double*)p;
+    sum_b = q, q += FB * NSUM;
+    sig_b = (int64_t*)q, q += FB;
+    hold_b = (int64_t*)q, q += FB;
+    mm_b = (float*)q, q += FB;
+    G_b = q, q += FB * 2;
+    fit_f = q, q += F * 4;
+    gsm = q, q += F * 2;
+    hold_f = (int64_t*)q, q += F;
+    th = (float*)q, q += F;
+    item = q, q += (size_t)B * I_SLOTS;
+    plane = q;
+  }
+};
+
+__device__ __forceinline__ int sgn(double v) { return (v > 0.0) - (v < 0.0); }  // 0 for 0 and for NaN
+
+// What every pass knows about its frame. The forward's results are read, never redone: sc, sh (scale_shift), the medians and
+// scales (frame_stats), the counts (frame_counts, out).
+struct FrameCtx {
+  const float* pf;
+  const float* tf;
+  const uint8_t* mf;
+  int H, W, hw, scales;
+  float sc, sh;
+  double mp, sp, mt, st, cnt;
+  double alpha, c_sp, c_st, c_ar, Mtot, Mk[DL_MAX_SCALES], Mt, Mar;
+  bool has_prev, has_next;  // a frame of the same item before / after this one, when the temporal term is on
+  __device__ FrameCtx(const float* pred, const float* target, const uint8_t* mask, int T, int H_, int W_, double alpha_, int scales_,
+                      int temporal, const float* __restrict__ ss, const double* __restrict__ fs, const int64_t* __restrict__ fc,
+                      const double* __restrict__ out, const float* __restrict__ coeff, int f) {
+    H = H_, W = W_, hw = H_ * W_, scales = scales_, alpha = alpha_;
+    pf = pred + (size_t)f * hw, tf = target + (size_t)f * hw, mf = mask + (size_t)f * hw;
+    sc = ss[(f / T) * 2], sh = ss[(f / T) * 2 + 1];
+    mp = fs[(size_t)f * 4], sp = fs[(size_t)f * 4 + 1], mt = fs[(size_t)f * 4 + 2], st = fs[(size_t)f * 4 + 3];
+    cnt = (double)fc[f];
+    c_sp = (double)coeff[0], c_st = temporal ? (double)coeff[1] : 0.0, c_ar = (double)coeff[2];
+    Mtot = out[7], Mt = temporal ? out[16] : 0.0, Mar = out[17];
+#pragma unroll
+    for (int k = 0; k < DL_MAX_SCALES; ++k) Mk[k] = out[12 + k];
+    has_prev = temporal && (f % T) > 0;
+    has_next = temporal && (f % T) + 1 < T;
+  }
+  // the difference of the normalised maps at one pixel, exactly as the forward takes it
+  __device__ __forceinline__ double diff(float a, float t) const { return ((double)a - mp) / sp - ((double)t - mt) / st; }
+  __device__ __forceinline__ double diff_at(size_t o) const { return diff(aligned(sc, pf[o], sh), tf[o]); }
+  // g_x of the kept pixel p = (y, x) whose difference is d: the data term's sign and, per grid, the integer sum of
+  // sign(d_self - d_nb) over the kept neighbours, divided by the grid's kept points; grids in ascending order
+  __device__ __forceinline__ double gx(int p, int y, int x, double d) const {
+    double reg = 0.0;
+    bool on = true;
+#pragma unroll
+    for (int k = 0; k < DL_MAX_SCALES; ++k) {
+      const int step = 1 << k;
+      on = on && k < scales && ((x | y) & (step - 1)) == 0;
+      if (on && Mk[k] > 0.0) {
+        int n = 0;
+        if (x + step < W && mf[p + step] != 0) n += sgn(d - diff_at((size_t)p + step));
+        if (x >= step && mf[p - step] != 0) n += sgn(d - diff_at((size_t)p - step));
+        if (y + step < H) {
+          const size_t o = (size_t)p + (size_t)step * W;
+          if (mf[o] != 0) n += sgn(d - diff_at(o));
+        }
+        if (y >= step) {
+          const size_t o = (size_t)p - (size_t)step * W;
+          if (mf[o] != 0) n += sgn(d - diff_at(o));
+        }
+        reg += (double)n / Mk[k];
+      }
+    }
+    return c_sp * ((double)sgn(d) / Mtot + alpha * reg);
+  }
+  // g_a of the kept pixel p with aligned prediction a and target t, from its g_x; gs, gm, holder, th_self and th_next are
+  // solve 1's results for this frame (th_next: of the next frame)
+  __device__ __forceinline__ double ga(int p, float a, float t, double gxv, double gs, double gm, int64_t holder, float th_self,
+                                       float th_next) const {
+    double g = gxv / sp + gs * (double)sgn((double)a - mp) / cnt;
+    if ((int64_t)p == holder) g += gm;
+    if (Mt > 0.0) {
+      int later = 0, earlier = 0;
+      if (has_prev && mf[(ptrdiff_t)p - hw] != 0) {  // the pair (f - 1, f): this frame is the later one
+        const float tq = tf[(ptrdiff_t)p - hw], tg = t - tq;
+        if (fabsf(tg) < th_self) {
+          const float pg = a - aligned(sc, pf[(ptrdiff_t)p - hw], sh);
+          later = sgn((double)pg - (double)tg);
+        }
+      }
+      if (has_next && mf[(size_t)p + hw] != 0) {     // the pair (f, f + 1): this frame is the earlier one
+        const float tq = tf[(size_t)p + hw], tg = tq - t;
+        if (fabsf(tg) < th_next) {
+          const float pg = aligned(sc, pf[(size_t)p + hw], sh) - a;
+          earlier = sgn((double)pg - (double)tg);
+        }
+      }
+      g += c_st * (double)(later - earlier) / Mt;
+    }
+    if (Mar > 0.0 && t > 1e-3f && t < 70.f) g += c_ar * (double)sgn((double)a - (double)t) / ((double)t * Mar);
+    return g;
+  }
+};
+
+#define GRAD_ARGS                                                                                                              \
+  const float *__restrict__ pred, const float *__restrict__ target, const uint8_t *__restrict__ mask, int B, int T, int H, int W, \
+      double alpha, int scales, int temporal, const float *__restrict__ ss, const double *__restrict__ fs,                      \
+      const int64_t *__restrict__ fc, const double *__restrict__ out, const float *__restrict__ coeff, void *__restrict__ workspace
+#define GRAD_CTX FrameCtx c(pred, target, mask, T, H, W, alpha, scales, temporal, ss, fs, fc, out, coeff, f)
+
+// ------------------------------------------------------------------------------------------------ pass 1
+template <int PPL, bool VEC>
+__global__ __launch_bounds__(256) void grad_stats_kernel(GRAD_ARGS) {
+  const Gw ws(workspace, B, T);
+  const int f = blockIdx.x / DL_BPF, b = blockIdx.x % DL_BPF;
+  const GRAD_CTX;
+  const float mpf = (float)c.mp;  // the median is a float32 sample or 0
+  Tuple<double, NSUM> s;
+#pragma unroll
+  for (int i = 0; i < NSUM; ++i) s.v[i] = 0.0;
+  int sigma = 0, hold = INT_MAX;
+  float mn = INFINITY, mx = -INFINITY;
+  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < c.hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+    const int p0 = (int)q0;
+    const Px<PPL, VEC> q(c.pf, c.tf, c.mf, p0);
+    int y = p0 / W, x = p0 - y * W;
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+      double g = 0.0;
+      if (q.k[j]) {
+        const float a = aligned(c.sc, q.p[j], c.sh), t = q.t[j];
+        g = c.gx(p0 + j, y, x, c.diff(a, t));
+        const double dev = (double)a - c.mp, pd = (double)q.p[j], td = (double)t;
+        s.v[0] += g;
+        s.v[1] += g * (dev / c.sp);
+        s.v[2] += fabs(dev);
+        s.v[3] += pd * pd;
+        s.v[4] += pd;
+        s.v[5] += pd * td;
+        s.v[6] += td;
+        sigma += sgn(dev);
+        if (a == mpf) hold = IntMinOp{}(hold, p0 + j);
+        mn = MinOp{}(mn, t);
+        mx = MaxOp{}(mx, t);
+      }
+      ws.plane[(size_t)f * c.hw + p0 + j] = g;
+      if (++x == W) x = 0, ++y;
+    }
+  }
+  __shared__ WaveSlots<Tuple<double, NSUM>> rs;
+  __shared__ WaveSlots<int> rg, rh;
+  __shared__ WaveSlots<float> rmn, rmx;
+  rs.put(s, SumOp{});
+  rg.put(sigma, SumOp{});
+  rh.put(hold, IntMinOp{});
+  rmn.put(mn, MinOp{});
+  rmx.put(mx, MaxOp{});
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const Tuple<double, NSUM> r = rs.get(SumOp{});
+#pragma unroll
+    for (int i = 0; i < NSUM; ++i) ws.sum_b[(size_t)blockIdx.x * NSUM + i] = r.v[i];
+    ws.sig_b[blockIdx.x] = (int64_t)rg.get(SumOp{});
+    ws.hold_b[blockIdx.x] = (int64_t)rh.get(IntMinOp{});
+    ws.mm_b[(size_t)blockIdx.x * 2] = rmn.get(MinOp{});
+    ws.mm_b[(size_t)blockIdx.x * 2 + 1] = rmx.get(MaxOp{});
+  }
+}
+
+// One block: every frame's blocks in index order, then every item's frames in index order.
+__global__ __launch_bounds__(256) void grad_solve1_kernel(void* __restrict__ workspace, int B, int T, int hw, const double* __restrict__ fs,
+                                                          const int64_t* __restrict__ fc) {
+  const Gw ws(workspace, B, T);
+  const int F = B * T;
+  for (int f = threadIdx.x; f < F; f += 256) {
+    double s[NSUM];
+#pragma unroll
+    for (int i = 0; i < NSUM; ++i) s[i] = 0.0;
+    int64_t sigma = 0, hold = INT_MAX;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int b = 0; b < DL_BPF; ++b) {
+      const size_t o = (size_t)f * DL_BPF + b;
+#pragma unroll
+      for (int i = 0; i < NSUM; ++i) s[i] += ws.sum_b[o * NSUM + i];
+      sigma += ws.sig_b[o];
+      hold = ws.hold_b[o] < hold ? ws.hold_b[o] : hold;
+      mn = MinOp{}(mn, ws.mm_b[o * 2]);
+      mx = MaxOp{}(mx, ws.mm_b[o * 2 + 1]);
+    }
+    const int64_t n = fc[f];
+    const double m = fs[(size_t)f * 4], sp = fs[(size_t)f * 4 + 1];
+    double gs = 0.0, gm = 0.0;
+    if (n > 0) {
+      if (s[2] / (double)n >= 1e-6) gs = -s[1] / sp;  // the clamp passes no gradient below its bound
+      gm = -s[0] / sp - gs * (double)sigma / (double)n;
+    }
+    ws.gsm[(size_t)f * 2] = gs;
+    ws.gsm[(size_t)f * 2 + 1] = gm;
+    // a median of 0 in a frame with a dropped pixel is taken to be a dropped pixel's 0: mask * a has the derivative 0 there
+    ws.hold_f[f] = (n == 0 || hold == INT_MAX || (m == 0.0 && n < (int64_t)hw)) ? -1 : hold;
+    ws.th[f] = (mx - mn) * 0.05f;  // -inf for a frame without a kept pixel: nothing is below it
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ws.fit_f[(size_t)f * 4 + i] = s[3 + i];
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < B; b += 256) {
+    double a00 = 0.0, a01 = 0.0, b0 = 0.0, b1 = 0.0;
+    int64_t n = 0;
+    for (int t = 0; t < T; ++t) {
+      const size_t f = (size_t)b * T + t;
+      a00 += ws.fit_f[f * 4], a01 += ws.fit_f[f * 4 + 1], b0 += ws.fit_f[f * 4 + 2], b1 += ws.fit_f[f * 4 + 3];
+      n += fc[f];
+    }
+    const double a11 = (double)n, det = a00 * a11 - a01 * a01;
+    double* it = ws.item + (size_t)b * I_SLOTS;
+    it[I_A00] = a00, it[I_A01] = a01, it[I_A11] = a11, it[I_B0] = b0, it[I_B1] = b1, it[I_D] = det + 1e-6;
+    it[I_OK] = det != 0.0 ? 1.0 : 0.0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ pass 2
+template <int PPL, bool VEC>
+__global__ __launch_bounds__(256) void grad_fit_partial_kernel(GRAD_ARGS) {
+  const Gw ws(workspace, B, T);
+  const int f = blockIdx.x / DL_BPF, b = blockIdx.x % DL_BPF;
+  const GRAD_CTX;
+  const double gs = ws.gsm[(size_t)f * 2], gm = ws.gsm[(size_t)f * 2 + 1];
+  const int64_t holder = ws.hold_f[f];
+  const float th_self = ws.th[f], th_next = c.has_next ? ws.th[f + 1] : 0.f;
+  Tuple<double, 2> s = {{0.0, 0.0}};
+  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < c.hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+    const int p0 = (int)q0;
+    const Px<PPL, VEC> q(c.pf, c.tf, c.mf, p0);
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+      if (q.k[j]) {
+        const float a = aligned(c.sc, q.p[j], c.sh), t = q.t[j];
+        const size_t o = (size_t)f * c.hw + p0 + j;
+        const double g = c.ga(p0 + j, a, t, ws.plane[o], gs, gm, holder, th_self, th_next);
+        ws.plane[o] = g;  // g_x becomes g_a in place: the lane that wrote the slot reads and rewrites it
+        s.v[0] += g * (double)q.p[j];
+        s.v[1] += g;
+      }
+    }
+  }
+  __shared__ WaveSlots<Tuple<double, 2>> rs;
+  rs.put(s, SumOp{});
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const Tuple<double, 2> r = rs.get(SumOp{});
+    ws.G_b[(size_t)blockIdx.x * 2] = r.v[0];
+    ws.G_b[(size_t)blockIdx.x * 2 + 1] = r.v[1];
+  }
+}
+
+// One block, a lane per item: every frame's blocks in index order, the frames in index order.
+__global__ __launch_bounds__(256) void grad_solve2_kernel(void* __restrict__ workspace, int B, int T) {
+  const Gw ws(workspace, B, T);
+  for (int b = threadIdx.x; b < B; b += 256) {
+    double G0 = 0.0, G1 = 0.0;
+    for (int t = 0; t < T; ++t) {
+      double f0 = 0.0, f1 = 0.0;
+      for (int k = 0; k < DL_BPF; ++k) {
+        const size_t o = ((size_t)b * T + t) * DL_BPF + k;
+        f0 += ws.G_b[o * 2], f1 += ws.G_b[o * 2 + 1];
+      }
+      G0 += f0, G1 += f1;
+    }
+    ws.item[(size_t)b * I_SLOTS + I_G0] = G0;
+    ws.item[(size_t)b * I_SLOTS + I_G1] = G1;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ pass 3
+template <int PPL, bool VEC>
+__global__ __launch_bounds__(256) void grad_write_kernel(GRAD_ARGS, float* __restrict__ grad) {
+  const Gw ws(workspace, B, T);
+  const int f = blockIdx.x / DL_BPF, b = blockIdx.x % DL_BPF;
+  const GRAD_CTX;
+  const double* it = ws.item + (size_t)(f / T) * I_SLOTS;
+  const double a01 = it[I_A01], a11 = it[I_A11], b0 = it[I_B0], b1 = it[I_B1], D = it[I_D], G0 = it[I_G0], G1 = it[I_G1];
+  const bool ok = it[I_OK] != 0.0;
+  const double scd = (double)c.sc, shd = (double)c.sh;
+  float* gf = grad + (size_t)f * c.hw;
+  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < c.hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+    const int p0 = (int)q0;
+    const Px<PPL, VEC> q(c.pf, c.tf, c.mf, p0);
+    float r[PPL];
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+      r[j] = 0.f;
+      if (q.k[j] && ok) {
+        const double g = ws.plane[(size_t)f * c.hw + p0 + j];
+        const double pd = (double)q.p[j], td = (double)q.t[j];
+        const double dN0 = a11 * td - b1, dN1 = -b0 - a01 * td + 2.0 * pd * b1, dD = 2.0 * (pd * a11 - a01);
+        const double fit = (G0 * (dN0 - scd * dD) + G1 * (dN1 - shd * dD)) / D;
+        r[j] = (float)(scd * g + fit);
+      }
+    }
+    if (VEC) {
+      *(f32x4*)(gf + p0) = f32x4{r[0], r[1], r[2], r[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < PPL; ++j) gf[p0 + j] = r[j];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" size_t vdn_depth_loss_backward_workspace_bytes(int B, int T, int H, int W) {
+  if (B <= 0 || T <= 0 || H <= 0 || W <= 0) return 0;
+  const size_t F = (size_t)B * T;
+  return sizeof(double) * (Gw::slots((size_t)B, F) + F * (size_t)H * W);
+}
+
+extern "C" int vdn_depth_loss_backward(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                                       double alpha, int scales, double stable_scale, const float* scale_shift,
+                                       const double* frame_stats, const int64_t* frame_counts, const double* out, const float* coeff,
+                                       void* workspace, float* grad_prediction, vdn_stream stream) {
+  if (!prediction || !target || !mask || !workspace || !scale_shift || !frame_stats || !frame_counts || !out || !coeff || !grad_prediction)
+    return VDN_EINVAL;
+  if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || scales < 0) return VDN_EINVAL;
+  if (stable_scale > 0.0 && T < 2) return VDN_EINVAL;
+  if ((int64_t)H * W > INT32_MAX || (int64_t)B * T > 65535 || scales > DL_MAX_SCALES) return VDN_EUNSUPPORTED;
+  if (((uintptr_t)prediction & 3) || ((uintptr_t)target & 3) || ((uintptr_t)scale_shift & 3) || ((uintptr_t)coeff & 3) ||
+      ((uintptr_t)grad_prediction & 3))
+    return VDN_EALIGN;
+  if (((uintptr_t)workspace & 7) || ((uintptr_t)frame_stats & 7) || ((uintptr_t)frame_counts & 7) || ((uintptr_t)out & 7))
+    return VDN_EALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int F = B * T, hw = H * W;
+  const dim3 grid((unsigned)F * DL_BPF), block(256);
+  // A lane owns four consecutive pixels whenever a frame holds whole quads, so the sums do not depend on where the tensors
+  // start; the 16-byte loads and stores are taken when every frame of every plane starts on 16 bytes (the mask on 4).
+  const bool quads = hw % 4 == 0;
+  const bool vec = quads && !((uintptr_t)prediction & 15) && !((uintptr_t)target & 15) && !((uintptr_t)mask & 3) &&
+                   !((uintptr_t)grad_prediction & 15);
+  const int eff_scales = alpha > 0.0 ? scales : 0;  // as the forward: the regulariser is skipped
+  const int temporal = stable_scale > 0.0;
+  auto launch = [&](auto ppl, auto v) {
+    constexpr int PPL = decltype(ppl)::value;
+    constexpr bool VEC = decltype(v)::value != 0;
+    hipLaunchKernelGGL((grad_stats_kernel<PPL, VEC>), grid, block, 0, s, prediction, target, mask, B, T, H, W, alpha, eff_scales,
+                       temporal, scale_shift, frame_stats, frame_counts, out, coeff, workspace);
+    hipLaunchKernelGGL(grad_solve1_kernel, dim3(1), block, 0, s, workspace, B, T, hw, frame_stats, frame_counts);
+    hipLaunchKernelGGL((grad_fit_partial_kernel<PPL, VEC>), grid, block, 0, s, prediction, target, mask, B, T, H, W, alpha, eff_scales,
+                       temporal, scale_shift, frame_stats, frame_counts, out, coeff, workspace);
+    hipLaunchKernelGGL(grad_solve2_kernel, dim3(1), block, 0, s, workspace, B, T);
+    hipLaunchKernelGGL((grad_write_kernel<PPL, VEC>), grid, block, 0, s, prediction, target, mask, B, T, H, W, alpha, eff_scales,
+                       temporal, scale_shift, frame_stats, frame_counts, out, coeff, workspace, grad_prediction);
+  };
+  if (vec) launch(IC<4>{}, IC<1>{});
+  else if (quads) launch(IC<4>{}, IC<0>{});
+  else launch(IC<1>{}, IC<0>{});
+  VDN_CHECK_LAUNCH();
+  return VDN_OK;
+}

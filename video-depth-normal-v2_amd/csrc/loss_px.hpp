@@ -1,0 +1,46 @@
+// What the passes of the depth criterion share (loss.hip forward, loss_grad.hip backward): the block layout of a frame, the
+// aligned prediction and the load of a lane's pixels. Include it AFTER the unit's `#pragma clang fp contract(off)`: aligned()
+// is a multiply that feeds an add, and both units must round it twice.
+#pragma once
+#include "common.hpp"
+
+namespace {
+
+constexpr int DL_BPF = 32;        // blocks per frame, fixed so that the workspace depends on B and T alone
+constexpr int DL_MAX_SCALES = 4;  // the reference's default, and all its scripts construct
+
+struct MinOp {
+  __device__ __forceinline__ float operator()(float a, float b) const { return b < a ? b : a; }
+};
+struct MaxOp {
+  __device__ __forceinline__ float operator()(float a, float b) const { return b > a ? b : a; }
+};
+
+// Two roundings. Plain operators, which the unit's pragma keeps apart: the bodies of __fmul_rn and __fadd_rn are compiled under
+// the header's contraction mode, and once inlined the pair becomes one v_fma_f32.
+__device__ __forceinline__ float aligned(float scale, float p, float shift) {
+  const float m = scale * p;
+  return m + shift;
+}
+
+// PPL consecutive pixels of a frame: 4 or 1. VEC: the four come by one 16-byte load per float plane and one 4-byte load of the
+// mask (the bases must allow it); otherwise every pixel by a load of its own, the lane owning the same pixels either way.
+template <int PPL, bool VEC = (PPL == 4)>
+struct Px {
+  float p[PPL], t[PPL];
+  bool k[PPL];
+  __device__ __forceinline__ Px(const float* __restrict__ pf, const float* __restrict__ tf, const uint8_t* __restrict__ mf, int i) {
+    if (VEC) {
+      static_assert(!VEC || PPL == 4, "the vector loads take four pixels");
+      const f32x4 v = *(const f32x4*)(pf + i), w = *(const f32x4*)(tf + i);
+      const uint32_t m = *(const uint32_t*)(mf + i);
+#pragma unroll
+      for (int j = 0; j < PPL; ++j) p[j] = v[j], t[j] = w[j], k[j] = ((m >> (8 * j)) & 0xFFu) != 0;
+    } else {
+#pragma unroll
+      for (int j = 0; j < PPL; ++j) p[j] = pf[i + j], t[j] = tf[i + j], k[j] = mf[i + j] != 0;
+    }
+  }
+};
+
+}  // namespace

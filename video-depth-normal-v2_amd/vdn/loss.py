@@ -1,12 +1,20 @@
 """The depth criterion on the device: the reference's loss.loss.VideoDepthLoss as its scripts construct it, computed by the
-kernels of csrc/loss.hip on tensors that can stay in HBM. In the `validate` of scripts/train.py, train_v2.py, train_v3.py and
-train_v4.py, replace
+kernels of csrc/loss.hip on tensors that can stay in HBM, with its gradient with respect to the prediction by the kernels of
+csrc/loss_grad.hip. In scripts/train.py, train_v2.py, train_v3.py and train_v4.py, which build the criterion once and use it
+in `validate` (under no_grad) and in the training step (total_loss.backward()), replace
 
     from loss.loss import VideoDepthLoss
 by
     from vdn.loss import VideoDepthLoss
 
-Forward only: nothing here records a gradient. Tensors are taken as float32 (masks as "non-zero = keep"; bool, uint8 and
+Gradients. A prediction that requires a gradient (with gradients enabled) goes through a torch.autograd.Function: the
+forward is the same launch, the backward is one launch of vdn_depth_loss_backward for whatever combination of the
+dictionary's entries was differentiated (d1 is piecewise constant and contributes zero). It is once differentiable. Without
+a gradient to record, forward is what it was: the same launches and tensors, nothing extra. A target that requires a
+gradient raises NotImplementedError: the reference would differentiate it and none of its scripts does. depth_loss_grad
+returns the same gradient without autograd.
+
+Tensors are taken as float32 (masks as "non-zero = keep"; bool, uint8 and
 float masks all do); a CUDA tensor of the right type is used in place, anything else is copied to `device` once, and results
 stay on the device unless a function says otherwise. include/vdn.h (vdn_depth_loss) states the arithmetic: the fit and all
 sums are fp64 on the device, and exactly the operations the reference's float32 tensors decide something with (the
@@ -29,6 +37,7 @@ from .normals import _on_device, _runtime_for
 
 OUT_SLOTS = 20   # include/vdn.h: the layout of vdn_depth_loss's out
 MAX_SCALES = 4
+_SLOT = {"spatial_loss": 0, "stable_loss": 1, "absRel_loss": 2, "d1": 3, "total_loss": 4}
 
 
 def _check(prediction, target, mask, dims: int) -> tuple:
@@ -57,8 +66,10 @@ def _check_args(alpha, scales, trim, stable_scale, ssim_loss_scale, reduction):
         raise NotImplementedError(f"scales={scales!r}: 0 .. {MAX_SCALES} gradient grids are computed")
 
 
-def _launch(prediction, target, mask, alpha, scales, stable_scale, device, per_frame: bool):
-    """-> (runtime, res): res float64 on the device, out[20] | frame_stats [F][4] | frame_counts [F] (int64) when per_frame."""
+def _launch(prediction, target, mask, alpha, scales, stable_scale, device, per_frame: bool, state: bool = False):
+    """-> (runtime, res): res float64 on the device, out[20] | frame_stats [F][4] | frame_counts [F] (int64) when per_frame.
+    state: -> (runtime, res, the fit f32 [B, 2] in a tensor of its own, and the float32 prediction, target and uint8 mask the
+    kernels read), what the backward needs."""
     B, T, H, W = _check(prediction, target, mask, 4)
     if stable_scale > 0 and T < 2:
         raise ValueError("stable_scale > 0 needs T >= 2: the temporal term of a single frame divides by a count of zero")
@@ -71,13 +82,50 @@ def _launch(prediction, target, mask, alpha, scales, stable_scale, device, per_f
         res = rt.buf("depth_loss_res", (OUT_SLOTS + 5 * F,), torch.float64)
         stats = res[OUT_SLOTS:OUT_SLOTS + 4 * F] if per_frame else None
         counts = res[OUT_SLOTS + 4 * F:].view(torch.int64) if per_frame else None
-        rt.depth_loss(p, t, m, res[:OUT_SLOTS], alpha, int(scales), stable_scale, None, stats, counts)
-    return rt, res
+        ss = torch.empty((B, 2), dtype=torch.float32, device=rt.device) if state else None
+        rt.depth_loss(p, t, m, res[:OUT_SLOTS], alpha, int(scales), stable_scale, ss, stats, counts)
+    return (rt, res, ss, p, t, m) if state else (rt, res)
+
+
+def _backward(rt, p, t, m, alpha, scales, stable_scale, ss, res, coeff) -> torch.Tensor:
+    """One launch of vdn_depth_loss_backward -> float32 [B, T, H, W]. res: out[20] | frame_stats | frame_counts as _launch left
+    them for these inputs (a copy: the runtime's buffer is reused by the next call); coeff float32 [3] on the device."""
+    F = p.shape[0] * p.shape[1]
+    with torch.cuda.device(rt.device):
+        grad = torch.empty_like(p)
+        rt.depth_loss_backward(p, t, m, alpha, int(scales), stable_scale, ss, res[OUT_SLOTS:OUT_SLOTS + 4 * F],
+                               res[OUT_SLOTS + 4 * F:].view(torch.int64), res[:OUT_SLOTS], coeff, grad)
+    return grad
+
+
+class _DepthLossFn(torch.autograd.Function):
+    """The five values of the criterion as one float32 [5] tensor (slots of _SLOT), differentiable in `prediction`."""
+
+    @staticmethod
+    def forward(ctx, prediction, target, mask, alpha, scales, stable_scale, device):
+        rt, res, ss, p, t, m = _launch(prediction, target, mask, alpha, scales, stable_scale, device, True, state=True)
+        with torch.cuda.device(rt.device):
+            res = res.clone()   # the O(B T) state, kept: the runtime's buffer is reused by the next call
+            v = res[:5].to(torch.float32)
+        ctx.save_for_backward(p, t, m, ss, res)
+        ctx.args = (rt, alpha, scales, stable_scale, prediction.dtype, prediction.device)
+        return v
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        p, t, m, ss, res = ctx.saved_tensors
+        rt, alpha, scales, stable_scale, dtype, device = ctx.args
+        with torch.cuda.device(rt.device):
+            g = g.to(device=rt.device, dtype=torch.float32)
+            coeff = torch.stack((g[4] + g[0], g[4] * stable_scale + g[1], g[2]))   # c_sp, c_st, c_ar; d1 contributes zero
+        grad = _backward(rt, p, t, m, alpha, scales, stable_scale, ss, res, coeff)
+        return grad.to(device=device, dtype=dtype), None, None, None, None, None, None
 
 
 class VideoDepthLoss(torch.nn.Module):
-    """loss/loss.py:326-367, forward only, with the reference's constructor signature and attributes. trim != 0,
-    reduction != "batch-based" and ssim_loss_scale > 0 raise NotImplementedError (see the module's text)."""
+    """loss/loss.py:326-367 with the reference's constructor signature and attributes, differentiable in the prediction.
+    trim != 0, reduction != "batch-based" and ssim_loss_scale > 0 raise NotImplementedError (see the module's text)."""
 
     def __init__(self, alpha=0.5, scales=4, trim=0.0, stable_scale=10, ssim_loss_scale=0.0, reduction="batch-based", *,
                  device="cuda"):
@@ -99,15 +147,20 @@ class VideoDepthLoss(torch.nn.Module):
     def forward(self, prediction, target, mask) -> Dict[str, torch.Tensor]:
         """prediction, target, mask [B, T, H, W] -> {'spatial_loss', 'stable_loss' (when stable_scale > 0), 'absRel_loss',
         'd1', 'total_loss'}: 0-dim float32 tensors on the device, no host synchronisation. ValueError when T == 1 and
-        stable_scale > 0, where the reference divides by zero."""
+        stable_scale > 0, where the reference divides by zero. With gradients enabled and a prediction that requires one, the
+        values carry a grad_fn whose backward gives prediction.grad in the prediction's dtype and shape."""
         if self.ssim_loss_scale > 0:      # the attribute is public, as in the reference
             raise NotImplementedError("ssim_loss_scale > 0 is not computed")
+        if torch.is_grad_enabled() and isinstance(target, torch.Tensor) and target.requires_grad:
+            raise NotImplementedError("the gradient with respect to target is not computed; detach the target")
+        if torch.is_grad_enabled() and isinstance(prediction, torch.Tensor) and prediction.requires_grad:
+            v = _DepthLossFn.apply(prediction, target, mask, self._alpha, self.scales, float(self.stable_scale), self.device)
+            return {k: v[_SLOT[k]] for k in self.keys}
         rt, res = _launch(prediction, target, mask, self._alpha, self.scales, float(self.stable_scale),
                           self.device, False)
         with torch.cuda.device(rt.device):
             v = res[:5].to(torch.float32)   # a copy: the buffer is reused by the next call
-        slot = {"spatial_loss": 0, "stable_loss": 1, "absRel_loss": 2, "d1": 3, "total_loss": 4}
-        return {k: v[slot[k]] for k in self.keys}
+        return {k: v[_SLOT[k]] for k in self.keys}
 
 
 def compute_scale_and_shift(prediction, target, mask, *, device="cuda"):
@@ -149,3 +202,17 @@ def depth_loss(prediction, target, mask, alpha=0.5, scales=4, stable_scale=10, *
                m_target=stats[..., 2].clone(), s_target=stats[..., 3].clone(),
                count=host[OUT_SLOTS + 4 * F:].view(torch.int64).view(B, T).clone())
     return out
+
+
+def depth_loss_grad(prediction, target, mask, alpha=0.5, scales=4, stable_scale=10, *, weights=(1, 0, 0, 0), device="cuda"):
+    """The gradient with respect to prediction of weights[0] * total_loss + weights[1] * spatial_loss + weights[2] *
+    stable_loss + weights[3] * absRel_loss, without autograd: float32 [B, T, H, W] on the device (the forward's launch and one
+    of vdn_depth_loss_backward). What VideoDepthLoss's backward computes, for tools and tests."""
+    _check_args(alpha, scales, 0.0, stable_scale, 0.0, "batch-based")
+    if len(weights) != 4:
+        raise ValueError(f"weights are (total, spatial, stable, absRel), got {weights!r}")
+    w = [float(x) for x in weights]
+    rt, res, ss, p, t, m = _launch(prediction, target, mask, float(alpha), scales, float(stable_scale), device, True, state=True)
+    with torch.cuda.device(rt.device):
+        coeff = torch.tensor([w[0] + w[1], float(stable_scale) * w[0] + w[2], w[3]], dtype=torch.float32, device=rt.device)
+    return _backward(rt, p, t, m, float(alpha), scales, float(stable_scale), ss, res, coeff)

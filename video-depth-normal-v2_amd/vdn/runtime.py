@@ -448,6 +448,26 @@ class Runtime:
                      int(scales), float(stable_scale), ws.data_ptr(), self._p(scale_shift), self._p(frame_stats),
                      self._p(frame_counts), self._p(out))
 
+    def depth_loss_backward(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, alpha: float, scales: int,
+                            stable_scale: float, scale_shift: torch.Tensor, frame_stats: torch.Tensor, frame_counts: torch.Tensor,
+                            out: torch.Tensor, coeff: torch.Tensor, grad: torch.Tensor):
+        """grad f32 [B, T, H, W] <- the gradient of c_sp * spatial + c_st * stable + c_ar * absRel with respect to the f32
+        prediction (vdn_depth_loss_backward), coeff f32 [3] = {c_sp, c_st, c_ar} on the device. scale_shift, frame_stats,
+        frame_counts and out are what depth_loss wrote for the same inputs and arguments."""
+        B, T, H, W = prediction.shape
+        for t in (prediction, target, grad):
+            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, T, H, W), t.shape
+        assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, T, H, W)
+        assert scale_shift.dtype == torch.float32 and scale_shift.numel() == 2 * B and scale_shift.is_contiguous()
+        assert frame_stats.dtype == torch.float64 and frame_stats.numel() == 4 * B * T and frame_stats.is_contiguous()
+        assert frame_counts.dtype == torch.int64 and frame_counts.numel() == B * T and frame_counts.is_contiguous()
+        assert out.dtype == torch.float64 and out.numel() >= 20 and out.is_contiguous()
+        assert coeff.dtype == torch.float32 and coeff.numel() == 3 and coeff.is_contiguous()
+        ws = self.buf("depth_loss_backward_ws", (abi.lib.vdn_depth_loss_backward_workspace_bytes(B, T, H, W) // 8,), torch.float64)
+        self._launch(abi.lib.vdn_depth_loss_backward, prediction.data_ptr(), target.data_ptr(), mask.data_ptr(), B, T, H, W,
+                     float(alpha), int(scales), float(stable_scale), scale_shift.data_ptr(), frame_stats.data_ptr(),
+                     frame_counts.data_ptr(), out.data_ptr(), coeff.data_ptr(), ws.data_ptr(), grad.data_ptr())
+
     def minmax(self, x: torch.Tensor, groups: int, out: torch.Tensor):
         """out f32 [groups, 2] <- {min, max} of each of the `groups` equal runs of contiguous f32 x (vdn_minmax_f32)."""
         assert x.is_contiguous() and x.dtype == torch.float32 and x.numel() % groups == 0

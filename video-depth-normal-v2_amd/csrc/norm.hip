@@ -147,7 +147,15 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const XT* __restrict__ x
 }
 
 // ---------------------------------------------------------------- GroupNorm (NHWC), 2 kernels
-// stats: grid (F, nsplit); deterministic: per-channel column sums in fixed order, then per group.
+// stats: grid (F, nsplit); deterministic: per-channel column sums in fixed order, then per group. Two passes over the split's
+// pixels (the second one hits L2): the first gives every group its mean over this split, the second sums d = x - mean and d^2,
+// so the squares are those of values of the size of the spread, not of the offset (q / n - mean^2 from one pass of fp32 sums
+// of x and x^2 lost accuracy as (mean / std)^2: 3.6e-4 of the output at a ratio of 64). partial[f][split][g] = (mean, M2) of
+// the split's n = (p1 - p0) * C / groups values, mean refined by sum(d) / n and M2 = sum(d^2) - sum(d)^2 / n; an empty split
+// (HW < nsplit) writes (0, 0). apply merges the splits in split order with Chan's pairwise update; the counts follow from the
+// split bounds, gn_split_begin in both kernels.
+__device__ __forceinline__ int gn_split_begin(int HW, int sp, int nsplit) { return (int)(((long long)HW * sp) / nsplit); }
+
 template <int DT>
 __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const typename Half<DT>::T* __restrict__ x,
                                                               const typename Half<DT>::T* __restrict__ xl, int HW,
@@ -160,44 +168,55 @@ __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const typename Hal
   const int pl = 256 / cv;            // pixel lanes (>= 1 because C <= 2048)
   const int tid = threadIdx.x;
   const int my_pl = tid / cv, my_cv = tid - my_pl * cv;
-  const int p0 = (int)(((long long)HW * sp) / nsplit), p1 = (int)(((long long)HW * (sp + 1)) / nsplit);
-  float s[8], ss[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s[e] = ss[e] = 0.f;
-  if (my_pl < pl) {
-    const size_t xo = (size_t)f * HW * C + my_cv * 8;
-    for (int p = p0 + my_pl; p < p1; p += pl) {
-      const V8 v = *(const V8*)(x + xo + (size_t)p * C);
-      V8 vl;
-      if (xl) vl = *(const V8*)(xl + xo + (size_t)p * C);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float fv = xl ? (float)v[e] + (float)vl[e] : (float)v[e];
-        s[e] += fv;
-        ss[e] += fv * fv;
-      }
-    }
-  }
+  const int p0 = gn_split_begin(HW, sp, nsplit), p1 = gn_split_begin(HW, sp + 1, nsplit);
+  const int cg = C / groups;
   float* col = (float*)smem;  // [pl][C][2]
-  if (my_pl < pl) {
+  __shared__ float gmean[64];
+  const size_t xo = (size_t)f * HW * C + my_cv * 8;
+  const float n = (float)(p1 - p0) * (float)cg;
+  // pass 0: sums of x -> the split's group means; pass 1: sums of d = x - mean and of d^2
+  for (int pass = 0; pass < 2; ++pass) {
+    float s[8], ss[8], m[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      col[((size_t)my_pl * C + my_cv * 8 + e) * 2] = s[e];
-      col[((size_t)my_pl * C + my_cv * 8 + e) * 2 + 1] = ss[e];
+      s[e] = ss[e] = 0.f;
+      m[e] = (pass && my_pl < pl) ? gmean[(my_cv * 8 + e) / cg] : 0.f;
     }
-  }
-  __syncthreads();
-  const int cg = C / groups;
-  for (int g = tid; g < groups; g += 256) {
-    float a = 0.f, bq = 0.f;
-    for (int k = 0; k < pl; ++k)
-      for (int c = g * cg; c < (g + 1) * cg; ++c) {
-        a += col[((size_t)k * C + c) * 2];
-        bq += col[((size_t)k * C + c) * 2 + 1];
+    if (my_pl < pl) {
+      for (int p = p0 + my_pl; p < p1; p += pl) {
+        const V8 v = *(const V8*)(x + xo + (size_t)p * C);
+        V8 vl;
+        if (xl) vl = *(const V8*)(xl + xo + (size_t)p * C);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = (xl ? (float)v[e] + (float)vl[e] : (float)v[e]) - m[e];
+          s[e] += d;
+          ss[e] += d * d;
+        }
       }
-    float* o = partial + (((size_t)f * nsplit + sp) * groups + g) * 2;
-    o[0] = a;
-    o[1] = bq;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        col[((size_t)my_pl * C + my_cv * 8 + e) * 2] = s[e];
+        col[((size_t)my_pl * C + my_cv * 8 + e) * 2 + 1] = ss[e];
+      }
+    }
+    __syncthreads();
+    for (int g = tid; g < groups; g += 256) {
+      float a = 0.f, bq = 0.f;
+      for (int k = 0; k < pl; ++k)
+        for (int c = g * cg; c < (g + 1) * cg; ++c) {
+          a += col[((size_t)k * C + c) * 2];
+          bq += col[((size_t)k * C + c) * 2 + 1];
+        }
+      if (pass == 0) {
+        gmean[g] = n > 0.f ? a / n : 0.f;
+      } else {
+        float* o = partial + (((size_t)f * nsplit + sp) * groups + g) * 2;
+        o[0] = n > 0.f ? gmean[g] + a / n : 0.f;
+        o[1] = n > 0.f ? fmaxf(bq - a * a / n, 0.f) : 0.f;
+      }
+    }
+    __syncthreads();   // gmean before pass 1 reads it; col before pass 1 overwrites it
   }
 }
 
@@ -215,17 +234,19 @@ __global__ __launch_bounds__(256) void groupnorm_apply_kernel(const typename Hal
   const int f = blockIdx.x;
   const int cg = C / groups;
   for (int g = threadIdx.x; g < groups; g += 256) {
-    float a = 0.f, q = 0.f;
+    // Chan's update, splits in order: (n, mean, M2) + (nk, mk, M2k), d = mk - mean -> mean + d nk / (n + nk), M2 + M2k + d^2 n nk / (n + nk)
+    float n = 0.f, mean = 0.f, m2 = 0.f;
     for (int k = 0; k < nsplit; ++k) {
       const float* pp = partial + (((size_t)f * nsplit + k) * groups + g) * 2;
-      a += pp[0];
-      q += pp[1];
+      const float nk = (float)(gn_split_begin(HW, k + 1, nsplit) - gn_split_begin(HW, k, nsplit)) * (float)cg;
+      if (nk == 0.f) continue;   // HW < nsplit leaves empty splits
+      const float d = pp[0] - mean, tot = n + nk;
+      mean += d * (nk / tot);
+      m2 += pp[1] + d * d * (n * (nk / tot));
+      n = tot;
     }
-    const float n = (float)HW * (float)cg;
-    const float mean = a / n;
-    const float var = fmaxf(q / n - mean * mean, 0.f);
     mr[2 * g] = mean;
-    mr[2 * g + 1] = rsqrtf(var + eps);
+    mr[2 * g + 1] = rsqrtf(m2 / n + eps);
   }
   __syncthreads();
   const size_t nvec = (size_t)HW * (C >> 3);

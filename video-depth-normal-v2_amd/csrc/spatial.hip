@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const float* __restrict__ 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sw = (float*)smem;                 // [49][32]
   float* sx = sw + 49 * DW_CB;              // [DW_TH + 6][WT + 6][DW_PS]  (halo of 3 columns on both sides, zero outside the image)
-  // WT: columns per tile (the whole row when it fits the LDS, else 64-column tiles: maps wider than 73 pixels)
+  // WT: columns per tile (the whole row when it fits the LDS, else 64-column tiles: maps wider than 72 pixels)
   const int cblocks = C / DW_CB, rtiles = (H + DW_TH - 1) / DW_TH, ctiles = (W + WT - 1) / WT;
   int bid = blockIdx.x;
   const int cb = (bid % cblocks) * DW_CB;
@@ -575,7 +575,7 @@ extern "C" int vdn_dwconv7(const float* x, float* y, int B, int H, int W, int C,
                            vdn_stream stream) {
   if (!x || !y || !w || !bias || B <= 0 || H <= 0 || W <= 0 || C <= 0) return VDN_EINVAL;
   if (C % DW_CB) return VDN_EALIGN;
-  // the whole row per tile while it fits the 160 KiB of LDS (W <= 73: the 37 x 37 grid of 518 x 518 inputs), else 64-column tiles
+  // the whole row per tile while it fits the 160 KiB of LDS (W <= 72, which takes 163 520 of its 163 840 bytes: the 37 x 37 grid of 518 x 518 inputs), else 64-column tiles
   const int WT = ((size_t)49 * DW_CB + (size_t)(DW_TH + 6) * (W + 6) * DW_PS) * sizeof(float) <= 160 * 1024 ? W : 64;
   const size_t lds = ((size_t)49 * DW_CB + (size_t)(DW_TH + 6) * (WT + 6) * DW_PS) * sizeof(float);
   static const hipError_t attr = hipFuncSetAttribute((const void*)dwconv7_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -379,7 +379,8 @@ int vdn_eval_metrics(const float* pred, const float* gt, const uint8_t* mask, in
 int vdn_resize_bilinear_hp(const float* x, float* y, int frames, int IH, int IW, int OH, int OW, vdn_stream stream);
 
 /* Normal evaluation on the device: normal_vector / sobel_ix_iy of utils/normal_utils.py:4-52 and VideoNormalLoss of
- * loss/loss.py:370-409 (the one measure of normal quality the reference has; scripts/train*.py validate). f32 inputs,
+ * loss/loss.py:370-409 (the one measure of normal quality the reference has; scripts/train*.py validate, and with
+ * vdn_normal_loss_backward below the training step). f32 inputs,
  * frames are [H, W] row-major. Stateless, caller's stream, caller-owned buffers. The stencil, the normalisation and the
  * cosine are fp64 computed from the f32 samples (separate multiply and add roundings: contraction is off); sums have a
  * fixed order (a lane's stride through its block's share, the lanes of a wave by xor-shuffle, the four waves, a frame's
@@ -416,6 +417,31 @@ int vdn_normal_vector(const float* depth, float* out, int frames, int H, int W, 
 int vdn_erode_mask3(const uint8_t* mask, uint8_t* out, int frames, int H, int W, vdn_stream stream);
 int vdn_normal_eval(const float* pred, const float* target, int target_is_depth, const uint8_t* mask, int frames, int H,
                     int W, void* workspace, double* frame_sums, int64_t* frame_counts, double* out, vdn_stream stream);
+
+/* The gradient of vdn_normal_eval's out[0] with respect to pred, times a coefficient: what autograd computes for
+ * g * normal_loss of the reference's VideoNormalLoss. pred, target, target_is_depth, mask, frames, H and W as for
+ * vdn_normal_eval; a target made from depth is a constant of the differentiation.
+ *   count   device pointer to the forward's kept count N, the out[1] vdn_normal_eval wrote for the same inputs (fp64)
+ *   coeff   device pointer to g, the gradient arriving at the loss (fp64)
+ *   grad_pred f32 [frames, 3, H, W], every element written exactly once
+ * F.cosine_similarity clamps both norms to 1e-8 outside the graph, so autograd differentiates sum_c (p_c / n) (t_c / n_t)
+ * with n = max(|p|, 1e-8), n_t = max(|t|, 1e-8) as if dn/dp = p / |p| on both sides of the clamp, and 0 at |p| = 0. With
+ * that = t / n_t:
+ *   kept pixel     grad_c = -(g / N) * (that_c - ((p . that) / n) * (p_c / |p|)) / n        (p_c / |p| := 0 where |p| = 0)
+ *   dropped pixel  +0.0 in all three channels; it is skipped, never multiplied by zero, so NaN or inf under it reaches nothing
+ *                  (the reference writes NaN there)
+ *   N == 0         +0.0 everywhere
+ * fp64 from the f32 samples, contraction off, 1 / n and 1 / n_t formed once per pixel, one rounding to f32 at the store. One
+ * launch, no workspace, no atomics, no host synchronisation; an element depends on its own pixel alone, so the two load shapes
+ * (four pixels per lane with 16-byte loads and stores where pred, grad_pred and a stored target are 16-byte aligned and H * W
+ * is a multiple of 4; one pixel per lane otherwise) and two runs give the same bits.
+ * VDN_EINVAL: a null pointer other than mask, frames <= 0, H < 2 or W < 2. VDN_EUNSUPPORTED: H * W > INT32_MAX. VDN_EALIGN:
+ * a float pointer off 4 bytes, count or coeff off 8. All returned before anything is launched.
+ * vdn_normal_loss_backward_trip(wide): the pixels of a frame that one trip of the grid covers (64 blocks x 256 lanes x 4 or
+ * 1); a larger frame sends the lanes round their stride loop again.                                                        */
+int vdn_normal_loss_backward_trip(int wide);
+int vdn_normal_loss_backward(const float* pred, const float* target, int target_is_depth, const uint8_t* mask, int frames,
+                             int H, int W, const double* count, const double* coeff, float* grad_pred, vdn_stream stream);
 
 /* The depth criterion on the device: VideoDepthLoss of loss/loss.py:326-367 as the reference's scripts construct it
  * (trim = 0, batch-based reduction, no SSIM term), the forward (its gradient: vdn_depth_loss_backward below);

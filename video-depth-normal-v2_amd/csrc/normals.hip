@@ -12,13 +12,11 @@
 // that belong to other lanes or blocks are read through the cache, as refine_pack_kernel does; the four pixels of a lane share theirs.
 #include "common.hpp"
 #include "reduce.hpp"
-#include <math.h>
 
 #pragma clang fp contract(off)
+#include "normal_px.hpp"
 
 namespace {
-
-constexpr int NE_BPF = 64;  // blocks per frame, fixed so that the workspace depends on the frame count alone
 
 // workspace, in 8-byte slots: [T] frame sums | [T] frame counts (i64) | [T][NE_BPF] block sums | [T][NE_BPF] block counts
 struct Ws {
@@ -34,54 +32,12 @@ struct Ws {
   }
 };
 
-// cross-correlation with kx = [[1,0,-1],[2,0,-2],[1,0,-1]], ky = [[1,2,1],[0,0,0],[-1,-2,-1]] (times 1/8 = k), in fp64.
-// a[r][c] is the 3 x 3 window; its centre is not used.
-__device__ __forceinline__ void sobel(const float (&a)[3][3], double k, double& ix, double& iy) {
-  const double a00 = a[0][0], a01 = a[0][1], a02 = a[0][2], a10 = a[1][0], a12 = a[1][2], a20 = a[2][0], a21 = a[2][1],
-               a22 = a[2][2];
-  ix = ((a00 - a02) + 2.0 * (a10 - a12) + (a20 - a22)) * k;
-  iy = ((a00 - a20) + 2.0 * (a01 - a21) + (a02 - a22)) * k;
-}
-
-// n = (-sxy Ix, -sxy Iy, sz) / sqrt(nx^2 + ny^2 + nz^2 + eps)
-__device__ __forceinline__ void unit_normal(double ix, double iy, double sxy, double sz, double eps, double (&n)[3]) {
-  const double nx = -sxy * ix, ny = -sxy * iy;
-  const double norm = sqrt(((nx * nx + ny * ny) + sz * sz) + eps);
-  n[0] = nx / norm;
-  n[1] = ny / norm;
-  n[2] = sz / norm;
-}
-
-__device__ __forceinline__ void window_at(const float* __restrict__ df, int y, int x, int H, int W, float (&a)[3][3]) {
-  const int ys[3] = {refl_lo(y), y, refl_hi(y, H)}, xs[3] = {refl_lo(x), x, refl_hi(x, W)};
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a[r][c] = (r == 1 && c == 1) ? 0.f : df[(size_t)ys[r] * W + xs[c]];
-}
-
-// erosion at (y, x): the pixel and its neighbours inside the image are all non-zero
-__device__ __forceinline__ bool kept_at(const uint8_t* __restrict__ mf, int y, int x, int H, int W) {
-  bool k = true;
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      const int yy = y + dy, xx = x + dx;
-      if (yy >= 0 && yy < H && xx >= 0 && xx < W) k = k && mf[(size_t)yy * W + xx] != 0;
-    }
-  return k;
-}
-
 // F.cosine_similarity(a, b, dim, eps = 1e-8) of torch 2.x: sum_c (a_c / max(|a|, eps)) * (b_c / max(|b|, eps)), evaluated as
 // (a . b) / (max(|a|, eps) * max(|b|, eps)): the same number in exact arithmetic with one fp64 division in place of six
 // (the kernel is bound by its fp64 divisions and square roots, not by memory: profiles/normal_eval.md). Neither form can
 // overflow from float32 inputs, and inf or NaN components give NaN in both. The comparison (not fmax) keeps a NaN norm.
 __device__ __forceinline__ double cosine3(const double (&a)[3], const double (&b)[3]) {
-  double na = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-  double nb = sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
-  na = na < 1e-8 ? 1e-8 : na;
-  nb = nb < 1e-8 ? 1e-8 : nb;
+  const double na = clamp_norm(norm3(a)), nb = clamp_norm(norm3(b));
   return ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) / (na * nb);
 }
 
@@ -136,83 +92,22 @@ __global__ __launch_bounds__(256) void normal_eval_partial_kernel(const float* _
   const float* pf = pred + (size_t)f * 3 * hw;
   const float* tf = target + (size_t)f * (DEPTH ? 1 : 3) * hw;
   const uint8_t* mf = mask ? mask + (size_t)f * hw : nullptr;
-  const double eps = (double)1e-8f;  // normal_vector's default, as vdn_normal_vector receives it
   double sum = 0.0;
   int cnt = 0;
   for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)NE_BPF * 256 * PPL) {
     const int p0 = (int)q0;
     float pv[3][PPL], tv[3][PPL];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if (PPL == 4) {
-        const f32x4 v = *(const f32x4*)(pf + (size_t)c * hw + p0);
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) pv[c][j] = v[j];
-        if (!DEPTH) {
-          const f32x4 w = *(const f32x4*)(tf + (size_t)c * hw + p0);
-#pragma unroll
-          for (int j = 0; j < PPL; ++j) tv[c][j] = w[j];
-        }
-      } else {
-        pv[c][0] = pf[(size_t)c * hw + p0];
-        if (!DEPTH) tv[c][0] = tf[(size_t)c * hw + p0];
-      }
-    }
+    load3<PPL>(pf, hw, p0, pv);
+    if (!DEPTH) load3<PPL>(tf, hw, p0, tv);
     int y = p0 / W, x = p0 - y * W;
-    // A quad that lies in one row with a column to spare on either side shares its neighbours: per row six columns serve
-    // the four erosion tests and the four stencils (18 + 18 loads in place of 36 + 32). Other quads go pixel by pixel.
-    const bool fast = PPL == 4 && x >= 1 && x + PPL < W;
-    bool keepq[PPL];
-    float dq[3][PPL + 2];
-    if (fast) {
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) keepq[j] = true;
-      if (mf) {
-        bool v[PPL + 2];  // the column's pixels in rows y - 1 .. y + 1 inside the image are all non-zero
-#pragma unroll
-        for (int c = 0; c < PPL + 2; ++c) {
-          const size_t o = (size_t)y * W + (x - 1 + c);
-          bool k = mf[o] != 0;
-          if (y > 0) k &= mf[o - W] != 0;
-          if (y < H - 1) k &= mf[o + W] != 0;
-          v[c] = k;
-        }
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) keepq[j] = v[j] & v[j + 1] & v[j + 2];
-      }
-      bool any = false;
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) any |= keepq[j];
-      if (DEPTH && any) {
-        const int ys[3] = {refl_lo(y), y, refl_hi(y, H)};
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-          for (int c = 0; c < PPL + 2; ++c) dq[r][c] = tf[(size_t)ys[r] * W + (x - 1 + c)];
-      }
-    }
+    const Hood<PPL, DEPTH> hood(tf, mf, y, x, H, W);
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
-      const bool keep = fast ? keepq[j] : (!mf || kept_at(mf, y, x, H, W));
-      if (keep) {  // a dropped pixel is skipped: nothing under it is read into the sums
+      if (hood.keep(mf, j, y, x, H, W)) {  // a dropped pixel is skipped: nothing under it is read into the sums
         const double a[3] = {(double)pv[0][j], (double)pv[1][j], (double)pv[2][j]};
         double t[3];
-        if (DEPTH) {
-          float win[3][3];
-          if (fast) {
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-              for (int c = 0; c < 3; ++c) win[r][c] = dq[r][j + c];
-          } else {
-            window_at(tf, y, x, H, W, win);
-          }
-          double ix, iy;
-          sobel(win, 0.125, ix, iy);
-          unit_normal(ix, iy, 1.0, 1.0, eps, t);
-        } else {
-          t[0] = (double)tv[0][j], t[1] = (double)tv[1][j], t[2] = (double)tv[2][j];
-        }
+        if (DEPTH) hood.normal(tf, j, y, x, H, W, t);
+        else t[0] = (double)tv[0][j], t[1] = (double)tv[1][j], t[2] = (double)tv[2][j];
         sum += cosine3(a, t);
         cnt += 1;
       }

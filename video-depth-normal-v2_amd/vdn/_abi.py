@@ -133,6 +133,8 @@ EXPORTS = {
     "vdn_normal_vector": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp]),
     "vdn_erode_mask3": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_normal_eval": (C.c_int, [fp, fp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "vdn_normal_loss_backward_trip": (C.c_int, [C.c_int]),
+    "vdn_normal_loss_backward": (C.c_int, [fp, fp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, fp, vp]),
     "vdn_depth_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "vdn_depth_loss": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, vp, fp, vp, vp, vp,
                                  vp]),

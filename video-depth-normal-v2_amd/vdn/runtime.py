@@ -429,6 +429,22 @@ class Runtime:
         self._launch(abi.lib.vdn_normal_eval, pred.data_ptr(), target.data_ptr(), int(target.dim() == 3), self._p(mask), F, H, W,
                      ws.data_ptr(), self._p(frame_sums), self._p(frame_counts), out.data_ptr())
 
+    def normal_loss_backward(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], count: torch.Tensor,
+                             coeff: torch.Tensor, grad: torch.Tensor):
+        """grad f32 [F, 3, H, W] <- coeff * d normal_loss / d pred (vdn_normal_loss_backward). pred, target and mask as for
+        normal_eval; count float64 [1] is the out[1] normal_eval wrote for them and coeff float64 [1], both on the device."""
+        F, _, H, W = pred.shape
+        for t in (pred, grad):
+            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (F, 3, H, W), t.shape
+        assert target.is_contiguous() and target.dtype == torch.float32
+        assert tuple(target.shape) in ((F, 3, H, W), (F, H, W)), (pred.shape, target.shape)
+        if mask is not None:
+            assert self._frames3(mask, torch.uint8) == (F, H, W)
+        for t in (count, coeff):
+            assert t.dtype == torch.float64 and t.numel() == 1 and t.is_cuda
+        self._launch(abi.lib.vdn_normal_loss_backward, pred.data_ptr(), target.data_ptr(), int(target.dim() == 3), self._p(mask),
+                     F, H, W, count.data_ptr(), coeff.data_ptr(), grad.data_ptr())
+
     def depth_loss(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor],
                    alpha: float = 0.5, scales: int = 4, stable_scale: float = 10.0, scale_shift: Optional[torch.Tensor] = None,
                    frame_stats: Optional[torch.Tensor] = None, frame_counts: Optional[torch.Tensor] = None):

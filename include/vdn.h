@@ -544,6 +544,46 @@ int vdn_depth_loss_backward(const float* prediction, const float* target, const 
                             const double* frame_stats, const int64_t* frame_counts, const double* out, const float* coeff,
                             void* workspace, float* grad_prediction, vdn_stream stream);
 
+/* The batch preparation that scripts/train.py, train_v2.py .. train_v4.py and scripts/evaluate.py, evaluate_v2.py ..
+ * evaluate_v4.py repeat between the loader and the model: preprocess_rgb_sequences, preprocess_rgb_viz_sequences,
+ * preprocess_depth_sequences (with its batch_wise_min_max_norm) and gt = 1. / torch.clamp(gt, min=1e-8). Stateless, caller's
+ * stream, caller-owned buffers, no host synchronisation.
+ * Arithmetic: the reference's float32 operations, one IEEE rounding per reference operation (fsub_rn, fdiv_rn), nothing
+ * contracted or reassociated, so the results are the bits of the torch composition. The constants are the float32 nearest
+ * to 1e-8, to the means 0.485, 0.456, 0.406 and to the stds 0.229, 0.224, 0.225 (timm's IMAGENET_DEFAULT_MEAN / _STD).
+ * clamp(x, min = m) is x < m ? m : x and clamp(x, max = m) is x > m ? m : x: a NaN stays a NaN, as in torch.clamp. The sign
+ * of a zero result is not part of the contract.
+ * vdn_prep_rgb    in, out f32 [frames, 3, H, W]; in == out is allowed. c = clamp(x, 0, 1); normalize != 0:
+ *                 out = fdiv(fsub(c, mean[ch]), std[ch]) (torchvision's Normalize: sub_(mean).div_(std)); else out = c. The
+ *                 channel is found per element. One launch.
+ * vdn_prep_depth  in, out f32 [B, n] (n = S * H * W; in == out is allowed), mask u8 [B, n], non-zero = keep, or NULL = all
+ *                 kept (the reference's masks == None branch). Stages in this order, each optional:
+ *                   reciprocal  x = fdiv(1, clamp(x, min = 1e-8f))                  the ground-truth line
+ *                   clamp0      x = clamp(x, min = 0)
+ *                   normalize   lo, hi = the item's min and max of the staged x over its kept pixels (a NaN at a kept pixel
+ *                               makes both NaN, as torch's min / max do; a dropped pixel is skipped by a branch, so nothing
+ *                               under it reaches them); d = clamp(fsub(hi, lo), min = 1e-8f);
+ *                               out = clamp(fdiv(fsub(x, lo), d), 0, 1) at every pixel of the item, kept or not; an item
+ *                               with no kept pixel gives +0.0 everywhere.
+ *                 minmax f32 [B][2] (may be NULL) receives lo, hi (+inf, -inf for an item with no kept pixel); written only
+ *                 when normalising. One launch without the normalisation. Two with it: pass 1 leaves 256 per-block (lo, hi,
+ *                 any) partials of each item in `workspace` (vdn_prep_depth_workspace_bytes(B) bytes, a multiple of 8 that
+ *                 depends on B alone); in pass 2 every block reduces its item's partials itself and writes its share. No
+ *                 finalise launch, no atomics; min and max are exact in any order, so two runs give the same bits. Pass 2
+ *                 does not read the mask: 13 bytes per pixel cross the bus (rgb: 8).
+ * Load shapes: where n (H * W for rgb) is a multiple of 4, the float pointers are 16-byte aligned and the mask is 4-byte
+ * aligned, a lane handles four floats per 16-byte load and store; one element otherwise. The values are the same either way.
+ * vdn_prep_trip(wide): the elements of one item (frame) that one trip of the grid covers (256 blocks x 256 lanes x 4 or 1);
+ * a longer item sends the lanes round their stride loop again.
+ * Errors, all returned before anything is launched. VDN_EINVAL: a null required pointer, a size <= 0, normalize with a NULL
+ * workspace. VDN_EUNSUPPORTED: n or 3 * H * W above INT32_MAX, B (frames) above 65535. VDN_EALIGN: a float pointer off 4
+ * bytes, a workspace off 8.                                                                                              */
+int vdn_prep_trip(int wide);
+size_t vdn_prep_depth_workspace_bytes(int B);
+int vdn_prep_rgb(const float* in, float* out, int frames, int H, int W, int normalize, vdn_stream stream);
+int vdn_prep_depth(const float* in, const uint8_t* mask, float* out, int B, int64_t n, int reciprocal, int clamp0,
+                   int normalize, void* workspace, float* minmax, vdn_stream stream);
+
 /* The colourised depth the reference's front ends write to disk, made on the device. Replaces, per frame, run.py:59-71,
  * run_video.py:75-89 and metric_depth/run.py:67-78 (min/max of the frame, matplotlib palette or a grey triple, BGR,
  * optionally cv2.hconcat([raw, 50 white columns, depth])) and, per clip, save_video of utils/dc_utils.py:72-86 (one min/max

@@ -30,6 +30,18 @@ struct SumOp {
   }
 };
 
+// Minimum and maximum that keep a NaN, as torch.min / torch.max and numpy's do: once either side is a NaN the result is one,
+// whatever the order. Written as comparisons (v_min / v_max and fminf / fmaxf return the other operand instead).
+struct NanMinOp {
+  __device__ __forceinline__ float operator()(float a, float b) const { return (b < a || b != b) ? b : a; }
+};
+struct NanMaxOp {
+  __device__ __forceinline__ float operator()(float a, float b) const { return (b > a || b != b) ? b : a; }
+};
+struct OrOp {
+  __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a | b; }
+};
+
 template <typename T>
 __device__ __forceinline__ T shfl_xor_words(T v, int o) {
   static_assert(std::is_trivially_copyable<T>::value && sizeof(T) % 4 == 0, "a value of whole 32-bit words");

@@ -39,4 +39,10 @@ def __getattr__(name):
     if name == "loss":   # VideoDepthLoss on the device (vdn/loss.py)
         import importlib
         return importlib.import_module(".loss", __name__)
+    if name == "prep":   # the scripts' batch preparation on the device (vdn/prep.py)
+        import importlib
+        return importlib.import_module(".prep", __name__)
+    if name == "steps":  # the bodies of the scripts' validate and evaluate loops, without host synchronisation (vdn/steps.py)
+        import importlib
+        return importlib.import_module(".steps", __name__)
     raise AttributeError(name)

@@ -141,6 +141,10 @@ EXPORTS = {
     "vdn_depth_loss_backward_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vdn_depth_loss_backward": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, fp, vp, vp, vp,
                                           fp, vp, fp, vp]),
+    "vdn_prep_trip": (C.c_int, [C.c_int]),
+    "vdn_prep_depth_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "vdn_prep_rgb": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_prep_depth": (C.c_int, [fp, vp, fp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, vp, fp, vp]),
     "vdn_minmax_workspace_bytes": (C.c_size_t, [C.c_int]),
     "vdn_minmax_f32": (C.c_int, [fp, C.c_int, C.c_size_t, vp, fp, vp]),
     "vdn_colorize": (C.c_int, [fp, fp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),

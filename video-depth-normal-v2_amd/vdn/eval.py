@@ -52,6 +52,60 @@ def _on_device(x, device: torch.device, dtype: torch.dtype) -> torch.Tensor:
     return t.to(device=device if not t.is_cuda else t.device, dtype=dtype).contiguous()
 
 
+def _check_clip(pred_disp, gt_disp, seq_len, domain, mask) -> int:
+    if domain not in _DOMAINS:
+        raise ValueError(f"domain must be 'depth' or 'disp', got {domain!r}")
+    if pred_disp.ndim != 3 or gt_disp.ndim != 3:
+        raise ValueError(f"pred and gt must be [T, H, W], got {tuple(pred_disp.shape)} and {tuple(gt_disp.shape)}")
+    seq_len = min(int(seq_len), pred_disp.shape[0])
+    if gt_disp.shape[0] < seq_len:
+        raise ValueError(f"gt has {gt_disp.shape[0]} frames, the prediction {seq_len} after truncation")
+    if mask is not None and tuple(mask.shape) != tuple(gt_disp.shape):
+        raise ValueError(f"mask shape {tuple(mask.shape)} is not gt's {tuple(gt_disp.shape)}")
+    if seq_len == 0 or 0 in tuple(pred_disp.shape) or 0 in tuple(gt_disp.shape):
+        raise ValueError("empty clip")
+    return seq_len
+
+
+def _clip_launches(rt, pred_disp, gt_disp, mask, seq_len: int, domain, lo: float, hi: float, tgm_over_time: bool, res):
+    """The launches of one clip: res float64 [9] on the device <- coef[2] | the seven metrics."""
+    dev = rt.device
+    pred = _on_device(pred_disp[:seq_len], dev, torch.float32)
+    gt = _on_device(gt_disp[:seq_len], dev, torch.float32)
+    m = None if mask is None else _on_device(mask[:seq_len], dev, torch.uint8)
+    if pred.shape[1:] != gt.shape[1:]:
+        resized = torch.empty_like(gt)
+        rt.resize_bilinear_hp(pred, resized)
+        pred = resized
+    rt.eval_fit(pred, gt, m, lo, hi, _DOMAINS[domain], res[:2])
+    rt.eval_metrics(pred, gt, m, lo, hi, _DOMAINS[domain], abi.EVAL_TGM_FRAMES if tgm_over_time else abi.EVAL_TGM_ROWS,
+                    res[:2], res[2:])
+
+
+def eval_batch_by_data(pred, gt, device="cuda", seq_len=98, domain="depth", dataset_min_depth=1e-3, dataset_max_depth=70,
+                       mask=None, *, tgm_over_time=False) -> torch.Tensor:
+    """eval_single_by_data for every item of a batch, left on the device: pred [B, S, h, w], gt [B, S, H, W] and the optional
+    mask [B, S, H, W] (numpy arrays or torch tensors) -> float64 [B, 7], row b the seven `eval_metrics` of item b with the bits
+    eval_single_by_data(pred[b], gt[b], ..., mask=mask[b]) returns. Per item it makes that function's launches and nothing
+    else; nothing is copied to the host and nothing synchronises. An item without a valid pixel gives a row of NaN."""
+    if pred.ndim != 4 or gt.ndim != 4:
+        raise ValueError(f"pred and gt must be [B, S, H, W], got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    if pred.shape[0] != gt.shape[0] or pred.shape[0] == 0:
+        raise ValueError(f"pred has {pred.shape[0]} items, gt {gt.shape[0]}")
+    if mask is not None and tuple(mask.shape) != tuple(gt.shape):
+        raise ValueError(f"mask shape {tuple(mask.shape)} is not gt's {tuple(gt.shape)}")
+    B = pred.shape[0]
+    n = _check_clip(pred[0], gt[0], seq_len, domain, None if mask is None else mask[0])
+    dev = next((t.device for t in (pred, gt) if isinstance(t, torch.Tensor) and t.is_cuda), torch.device(device))
+    rt = _runtime(dev)
+    with torch.cuda.device(rt.device):
+        res = torch.empty((B, 9), dtype=torch.float64, device=rt.device)   # per item coef[2] | out[7]
+        for b in range(B):
+            _clip_launches(rt, pred[b], gt[b], None if mask is None else mask[b], n, domain, float(dataset_min_depth),
+                           float(dataset_max_depth), tgm_over_time, res[b])
+    return res[:, 2:]
+
+
 def eval_single_by_data(pred_disp, gt_disp, device="cuda", seq_len=98, domain="depth", dataset_min_depth=1e-3,
                         dataset_max_depth=70, mask=None, *, tgm_over_time=False) -> List[float]:
     """The seven `eval_metrics` of a clip, with the reference's signature and semantics.

@@ -484,6 +484,26 @@ class Runtime:
                      float(alpha), int(scales), float(stable_scale), scale_shift.data_ptr(), frame_stats.data_ptr(),
                      frame_counts.data_ptr(), out.data_ptr(), coeff.data_ptr(), ws.data_ptr(), grad.data_ptr())
 
+    def prep_rgb(self, x: torch.Tensor, out: torch.Tensor, normalize: bool):
+        """out f32 [F, 3, H, W] <- clamp(x, 0, 1), then the ImageNet mean / std when `normalize` (vdn_prep_rgb); out may be x."""
+        F, _, H, W = x.shape
+        for t in (x, out):
+            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (F, 3, H, W), t.shape
+        self._launch(abi.lib.vdn_prep_rgb, x.data_ptr(), out.data_ptr(), F, H, W, int(normalize))
+
+    def prep_depth(self, x: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Tensor, reciprocal: bool, clamp0: bool,
+                   normalize: bool, minmax: Optional[torch.Tensor] = None):
+        """out f32 [B, n] <- the stages of vdn_prep_depth on f32 x [B, n] under the u8 mask [B, n] (None: all kept);
+        minmax f32 [B, 2] receives the (lo, hi) of the normalisation."""
+        B, n = x.shape
+        for t in (x, out):
+            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, n), t.shape
+        assert mask is None or (mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, n))
+        assert minmax is None or (minmax.is_contiguous() and minmax.dtype == torch.float32 and minmax.numel() == 2 * B)
+        ws = self.buf("prep_depth_ws", (abi.lib.vdn_prep_depth_workspace_bytes(B) // 8,), torch.float64) if normalize else None
+        self._launch(abi.lib.vdn_prep_depth, x.data_ptr(), self._p(mask), out.data_ptr(), B, n, int(reciprocal), int(clamp0),
+                     int(normalize), self._p(ws), self._p(minmax))
+
     def minmax(self, x: torch.Tensor, groups: int, out: torch.Tensor):
         """out f32 [groups, 2] <- {min, max} of each of the `groups` equal runs of contiguous f32 x (vdn_minmax_f32)."""
         assert x.is_contiguous() and x.dtype == torch.float32 and x.numel() % groups == 0

@@ -544,6 +544,63 @@ int vdn_depth_loss_backward(const float* prediction, const float* target, const 
                             const double* frame_stats, const int64_t* frame_counts, const double* out, const float* coeff,
                             void* workspace, float* grad_prediction, vdn_stream stream);
 
+/* The trimmed depth criterion: VideoDepthLoss(alpha, scales, trim, stable_scale) of loss/loss.py:326-367 with trim > 0 (its
+ * TrimmedMAELoss and TrimmedAbsRelLoss, loss/loss.py:164-219), batch-based reduction, no SSIM term. vdn_depth_loss and
+ * vdn_depth_loss_backward are unchanged; these two entry points stand beside them.
+ * The arguments are those of vdn_depth_loss plus keep = 1.0 - trim, computed once by the caller in double, in (0, 1]. The fit,
+ * the alignment, the robust normalisation, the grids g_k, d1 and every count are exactly vdn_depth_loss's (its kernels run
+ * first, on the same stream). Three terms change. Each has a set of counted residuals |r|, fp64, as vdn_depth_loss sums them:
+ *   data    |an - tn| over the kept pixels                          n = out[7]
+ *   stable  |pg - tg| over the temporal pairs that are counted      n = out[16]
+ *   absRel  |(a - t) / t| over the pixels absRel counts             n = out[17]
+ * and the reference sorts them, keeps the k smallest and divides their sum by n (not by k). Here, per term:
+ *   rank    k = (uint64) floor((double) n * keep), which is Python's int(len * (1.0 - trim)). n exists only on the device, so
+ *           k is computed there; no host synchronisation is added.
+ *   key     the float32 rounding of |r|. It is non-negative, so its bit pattern is ordered. A NaN residual has the one key
+ *           0x7FC00000 and sorts after +inf, as in torch.sort. Dropped and uncounted elements take no part: they are
+ *           skipped, not given a key. thr = the key of rank k - 1 among the n keys (an exact radix select over the batch).
+ *   value   n_less = #{key < thr}, n_tied = #{key == thr}, w = (k - n_less) / n_tied in fp64;
+ *           term = (sum_{key < thr} |r| + w * sum_{key == thr} |r|) / n, the fp64 residuals in the fixed order below.
+ *           term = 0 and k = n_less = n_tied = thr = w = 0 when k == 0 (which includes n == 0).
+ *           The reference keeps an arbitrary k - n_less of the tied elements (its sort is not stable). They are equal to
+ *           float32, so w gives its value to float32 rounding, and the same bits on every run.
+ * spatial_loss = data + alpha * sum_k g_k and total_loss = spatial_loss + stable_scale * stable_loss are formed from the
+ * trimmed terms as vdn_depth_loss forms them; g_k and d1 are not trimmed.
+ * out f64 [40]: 0..19 as vdn_depth_loss, with the trimmed values in 0, 1, 2, 4 and 5; for term i (0 data, 1 stable, 2 absRel)
+ *               20 + 5 i: k | n_less | n_tied | thr as f64 | w; 35..39 zero. out is required (there is no fit-only form).
+ * Passes after vdn_depth_loss's: a one-block kernel (per-frame scales once, the three k); the select of csrc/select.hpp over
+ * one set of all frames with three slots, so the three terms share one sweep of the inputs per radix pass, each rank read
+ * from device memory; per frame in 32 blocks the sums and counts below and at each threshold; a one-block finalise. Every
+ * pass recomputes the residuals from the inputs, by the expressions of vdn_depth_loss (one sweep writing float32 key planes
+ * for the select's passes, and three selects of one slot, were measured and dropped: DESIGN 5.14). Load shapes as
+ * vdn_depth_loss.
+ * Determinism: the sums have vdn_depth_loss's fixed order (lane stride, wave, block, a frame's blocks, frames in index order);
+ * the select's integer atomics count and cannot reorder anything. Two runs give the same bits.
+ * workspace: vdn_depth_loss_trimmed_workspace_bytes(B, T) bytes (it depends on B and T alone), 8-byte aligned.
+ * Errors as vdn_depth_loss, returned before anything is launched, and: VDN_EINVAL for out == NULL and for keep outside (0, 1]
+ * or NaN; VDN_EUNSUPPORTED when B * T * H * W > UINT32_MAX, the limit of the select's counters.                          */
+size_t vdn_depth_loss_trimmed_workspace_bytes(int B, int T);
+int vdn_depth_loss_trimmed(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                           double alpha, int scales, double stable_scale, double keep, void* workspace, float* scale_shift,
+                           double* frame_stats, int64_t* frame_counts, double* out, vdn_stream stream);
+/* The gradient of the trimmed criterion with respect to `prediction`: the contract of vdn_depth_loss_backward, with out the
+ * f64 [40] that vdn_depth_loss_trimmed wrote for the same inputs and arguments. The selection is piecewise constant, so each
+ * counted element of a term carries the weight u = 1 where key < thr, w where key == thr and 0 otherwise (0 everywhere when
+ * k == 0), the key recomputed from the inputs and compared with out[20 + 5 i + 3]. u multiplies three terms of the chain:
+ *   the data part of g_x         c_sp * u * sign(d) / M
+ *   the stable part of g_a       c_st * (u_later e_later - u_earlier e_earlier) / out[16], u of the pair each e belongs to
+ *   the absRel part of g_a       c_ar * u * sign(a - target) / (target * out[17])
+ * The regulariser, the frame chain (g_s, g_m, the median's holder) and the fit chain follow from these and do not change. With
+ * no tie at a threshold this is what autograd gives through the reference's sort and slice; with ties it is the mean over the
+ * reference's possible choices. No atomics; the sums have the forward's fixed order, so two runs give the same bits.
+ * workspace: vdn_depth_loss_trimmed_backward_workspace_bytes(B, T, H, W) bytes (that of vdn_depth_loss_backward). Errors as
+ * vdn_depth_loss_backward, and VDN_EUNSUPPORTED when B * T * H * W > UINT32_MAX, for which no forward can have run.        */
+size_t vdn_depth_loss_trimmed_backward_workspace_bytes(int B, int T, int H, int W);
+int vdn_depth_loss_trimmed_backward(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                                    double alpha, int scales, double stable_scale, const float* scale_shift,
+                                    const double* frame_stats, const int64_t* frame_counts, const double* out,
+                                    const float* coeff, void* workspace, float* grad_prediction, vdn_stream stream);
+
 /* The batch preparation that scripts/train.py, train_v2.py .. train_v4.py and scripts/evaluate.py, evaluate_v2.py ..
  * evaluate_v4.py repeat between the loader and the model: preprocess_rgb_sequences, preprocess_rgb_viz_sequences,
  * preprocess_depth_sequences (with its batch_wise_min_max_norm) and gt = 1. / torch.clamp(gt, min=1e-8). Stateless, caller's

@@ -1,5 +1,6 @@
 // The depth criterion of the reference's validate on the device: VideoDepthLoss of loss/loss.py:326-367 (trim = 0,
-// batch-based reduction, no SSIM term), forward only, for [B, T, H, W] tensors that already sit in HBM.
+// batch-based reduction, no SSIM term), forward only, for [B, T, H, W] tensors that already sit in HBM. The trimmed criterion
+// (trim > 0: vdn_depth_loss_trimmed) runs these passes and then its own, in the last section of the namespace.
 //   fit        per item, the masked sums of compute_scale_and_shift (fp64), per-frame counts and the masked min / max of
 //              the target; a one-block solve rounds scale and shift to float32 once
 //   select     the lower medians of keep ? aligned : 0 and keep ? target : 0 per frame (select.hpp, two slots)
@@ -170,7 +171,8 @@ struct LossKey {
   const float* ss;
   size_t hw;
   int T;
-  __device__ __forceinline__ void operator()(int f, size_t i, uint32_t& k0, uint32_t& k1) const {
+  static constexpr int SLOTS = 2, PER = 1;
+  __device__ __forceinline__ uint32_t operator()(int f, size_t i, uint32_t (&key)[1][2]) const {
     const size_t o = (size_t)f * hw + i;
     float a = 0.f, t = 0.f;
     if (mask[o] != 0) {
@@ -178,8 +180,9 @@ struct LossKey {
       a = aligned(ss[b * 2], pred[o], ss[b * 2 + 1]);
       t = target[o];
     }
-    k0 = ordered_key(a);
-    k1 = ordered_key(t);
+    key[0][0] = ordered_key(a);
+    key[0][1] = ordered_key(t);
+    return 3u;
   }
 };
 
@@ -379,16 +382,229 @@ __global__ __launch_bounds__(256) void loss_finalise_kernel(void* __restrict__ w
   out[19] = 0.0;
 }
 
+// ------------------------------------------------------------------------------------------------ trimmed criterion
+// vdn_depth_loss_trimmed: the untrimmed launch above runs first and leaves the fit, the medians, the deviation sums, g_k, d1
+// and all counts, none of which trim changes. Then
+//   prepare    one block: the per-frame scales once, and per term k = floor(n * keep) from the counts in out (on the device);
+//   select     one set of all frames, three slots (data, stable, absRel), rank k - 1 each: the thresholds (select.hpp);
+//   sums       per frame in DL_BPF blocks and per term: sum and count of the residuals below the threshold and of those at it;
+//   finalise   one block: blocks then frames in index order, w = (k - n_less) / n_tied, the five values and out[20..39].
+// The residuals are recomputed from the inputs by every pass (loss_px.hpp: the same expressions, so the same bits). One sweep
+// that writes float32 key planes for the select's passes, and three selects of one slot, were measured and dropped (DESIGN
+// 5.14, profiles/depth_loss_trim.md: 883 and 1209 against 824 us for the launch at [2, 32, 518, 518]).
+constexpr int NTR = 2 * TR_TERMS;            // per term {below the threshold, at it}: a sum (double) and a count (integer)
+
+struct Tw {  // the trimmed launch's own workspace, after the untrimmed one; in 8-byte slots
+  double* fsc;      // [F][2] s of the aligned prediction, of the target
+  uint32_t* rank;   // [3] (two slots)
+  double* sum_b;    // [F][DL_BPF][NTR]
+  int64_t* cnt_b;   // [F][DL_BPF][NTR]
+  double* sum_f;    // [F][NTR]
+  int64_t* cnt_f;   // [F][NTR]
+  void* select;     // one set of three slots
+  __host__ __device__ static size_t slots(size_t F) { return F * 2 + 2 + F * DL_BPF * 2 * NTR + F * 2 * NTR; }
+  __host__ __device__ Tw(void* p, int B, int T) {
+    const size_t F = (size_t)B * T, FB = F * DL_BPF;
+    double* q = (double*)p;
+    fsc = q, q += F * 2;
+    rank = (uint32_t*)q, q += 2;
+    sum_b = q, q += FB * NTR;
+    cnt_b = (int64_t*)q, q += FB * NTR;
+    sum_f = q, q += F * NTR;
+    cnt_f = (int64_t*)q, q += F * NTR;
+    select = q;
+  }
+};
+
+// What a pass of the trimmed criterion knows about frame f, and the residuals of a lane's pixels.
+struct TrimFrame {
+  const float* pf;
+  const float* tf;
+  const uint8_t* mf;
+  float sc, sh, th;
+  double mp, sp, mt, st;
+  int next;  // hw when the next frame belongs to the same item and the temporal term is on, else 0
+  __device__ __forceinline__ TrimFrame(const float* pred, const float* target, const uint8_t* mask, int T, int hw, int temporal,
+                                       const Ws& ws, const double* __restrict__ fsc, int f) {
+    pf = pred + (size_t)f * hw, tf = target + (size_t)f * hw, mf = mask + (size_t)f * hw;
+    sc = ws.ss[(f / T) * 2], sh = ws.ss[(f / T) * 2 + 1];
+    mp = (double)ws.med[f * 2], mt = (double)ws.med[f * 2 + 1], sp = fsc[(size_t)f * 2], st = fsc[(size_t)f * 2 + 1];
+    next = temporal && (f % T) + 1 < T ? hw : 0;
+    th = next ? ws.th[f + 1] : 0.f;
+  }
+  // r[j][term] of pixels p0 .. p0 + PPL - 1; bit j * TR_TERMS + term of the result: the forward counts the pixel for the term
+  template <int PPL>
+  __device__ __forceinline__ uint32_t residuals(int p0, double (&r)[PPL][TR_TERMS]) const {
+    const Px<PPL> q(pf, tf, mf, p0);
+    const Px<PPL> qn(pf + next, tf + next, mf + next, p0);
+    uint32_t on = 0;
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+      r[j][TR_DATA] = r[j][TR_STABLE] = r[j][TR_ABSREL] = 0.0;
+      if (q.k[j]) {
+        const float a = aligned(sc, q.p[j], sh), t = q.t[j];
+        r[j][TR_DATA] = res_data(a, t, mp, sp, mt, st);
+        on |= 1u << (j * TR_TERMS + TR_DATA);
+        if (t > 1e-3f && t < 70.f) {
+          r[j][TR_ABSREL] = res_absrel(a, t);
+          on |= 1u << (j * TR_TERMS + TR_ABSREL);
+        }
+        if (next && qn.k[j]) {
+          const float tg = qn.t[j] - t;
+          if (fabsf(tg) < th) {
+            r[j][TR_STABLE] = res_stable(aligned(sc, qn.p[j], sh) - a, tg);
+            on |= 1u << (j * TR_TERMS + TR_STABLE);
+          }
+        }
+      }
+    }
+    return on;
+  }
+};
+
+#define TRIM_ARGS                                                                                                              \
+  const float *__restrict__ pred, const float *__restrict__ target, const uint8_t *__restrict__ mask, int B, int T, int hw, \
+      int temporal, void *__restrict__ workspace, void *__restrict__ trim_workspace
+
+// the select's keys, recomputed from the inputs
+template <int PPL>
+struct TrimKey {
+  static constexpr int SLOTS = TR_TERMS, PER = PPL;
+  const float* pred;
+  const float* target;
+  const uint8_t* mask;
+  int B, T, hw, temporal;
+  void* workspace;
+  void* trim_workspace;
+  __device__ __forceinline__ uint32_t operator()(int f, size_t i, uint32_t (&key)[PPL][TR_TERMS]) const {
+    const Ws ws(workspace, B, T);
+    const Tw tw(trim_workspace, B, T);
+    const TrimFrame fr(pred, target, mask, T, hw, temporal, ws, tw.fsc, f);
+    double r[PPL][TR_TERMS];
+    const uint32_t on = fr.residuals<PPL>((int)i, r);
+#pragma unroll
+    for (int j = 0; j < PPL; ++j)
+#pragma unroll
+      for (int k = 0; k < TR_TERMS; ++k) key[j][k] = trim_key(r[j][k]);
+    return on;
+  }
+};
+
+// One block. out[7], out[16] and out[17] are the counts the untrimmed finalise just wrote.
+__global__ __launch_bounds__(256) void trim_prepare_kernel(void* __restrict__ workspace, void* __restrict__ trim_workspace, int B, int T,
+                                                           double keep, double* __restrict__ out) {
+  const Ws ws(workspace, B, T);
+  const Tw tw(trim_workspace, B, T);
+  const int F = B * T;
+  for (int i = threadIdx.x; i < F * 2; i += 256) tw.fsc[i] = frame_scale(ws, i >> 1, i & 1);
+  if (threadIdx.x < TR_TERMS) {
+    const double n = out[threadIdx.x == TR_DATA ? 7 : (threadIdx.x == TR_STABLE ? 16 : 17)];
+    const uint64_t k = (uint64_t)floor(n * keep);  // Python's int(n * (1.0 - trim)); n < 2^32 is exact in a double
+    out[20 + 5 * threadIdx.x] = (double)k;
+    tw.rank[threadIdx.x] = k ? (uint32_t)(k - 1) : 0u;
+  }
+}
+
+template <int PPL>
+__global__ __launch_bounds__(256) void trim_sum_kernel(TRIM_ARGS, const SelState* __restrict__ st) {
+  const Ws ws(workspace, B, T);
+  const Tw tw(trim_workspace, B, T);
+  const int f = blockIdx.x / DL_BPF, b = blockIdx.x % DL_BPF;
+  const TrimFrame fr(pred, target, mask, T, hw, temporal, ws, tw.fsc, f);
+  const uint32_t thr[TR_TERMS] = {st[0].prefix, st[1].prefix, st[2].prefix};
+  Tuple<double, NTR> acc;
+  Tuple<int, NTR> cnt;
+#pragma unroll
+  for (int i = 0; i < NTR; ++i) acc.v[i] = 0.0, cnt.v[i] = 0;
+  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+    double r[PPL][TR_TERMS];
+    const uint32_t on = fr.residuals<PPL>((int)q0, r);
+#pragma unroll
+    for (int j = 0; j < PPL; ++j)
+#pragma unroll
+      for (int k = 0; k < TR_TERMS; ++k)
+        if ((on >> (j * TR_TERMS + k)) & 1u) {
+          const uint32_t key = trim_key(r[j][k]);
+          if (key < thr[k]) acc.v[2 * k] += r[j][k], cnt.v[2 * k] += 1;
+          else if (key == thr[k]) acc.v[2 * k + 1] += r[j][k], cnt.v[2 * k + 1] += 1;
+        }
+  }
+  __shared__ WaveSlots<Tuple<double, NTR>> rs;
+  __shared__ WaveSlots<Tuple<int, NTR>> rc;
+  rs.put(acc, SumOp{});
+  rc.put(cnt, SumOp{});
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const Tuple<double, NTR> r = rs.get(SumOp{});
+    const Tuple<int, NTR> c = rc.get(SumOp{});
+#pragma unroll
+    for (int i = 0; i < NTR; ++i) {
+      tw.sum_b[(size_t)blockIdx.x * NTR + i] = r.v[i];
+      tw.cnt_b[(size_t)blockIdx.x * NTR + i] = (int64_t)c.v[i];
+    }
+  }
+}
+
+// One block: every frame's blocks in index order, then the frames in index order; then the trimmed values over the untrimmed.
+__global__ __launch_bounds__(256) void trim_finalise_kernel(void* __restrict__ trim_workspace, int B, int T, double alpha,
+                                                            double stable_scale, const SelState* __restrict__ st,
+                                                            double* __restrict__ out) {
+  const Tw tw(trim_workspace, B, T);
+  const int F = B * T;
+  for (int f = threadIdx.x; f < F; f += 256) {
+    double s[NTR];
+    int64_t n[NTR];
+#pragma unroll
+    for (int i = 0; i < NTR; ++i) s[i] = 0.0, n[i] = 0;
+    for (int b = 0; b < DL_BPF; ++b)
+#pragma unroll
+      for (int i = 0; i < NTR; ++i) {
+        s[i] += tw.sum_b[((size_t)f * DL_BPF + b) * NTR + i];
+        n[i] += tw.cnt_b[((size_t)f * DL_BPF + b) * NTR + i];
+      }
+#pragma unroll
+    for (int i = 0; i < NTR; ++i) tw.sum_f[(size_t)f * NTR + i] = s[i], tw.cnt_f[(size_t)f * NTR + i] = n[i];
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double s[NTR];
+  int64_t n[NTR];
+  for (int i = 0; i < NTR; ++i) s[i] = 0.0, n[i] = 0;
+  for (int f = 0; f < F; ++f)
+    for (int i = 0; i < NTR; ++i) s[i] += tw.sum_f[(size_t)f * NTR + i], n[i] += tw.cnt_f[(size_t)f * NTR + i];
+  const uint32_t thr[TR_TERMS] = {st[0].prefix, st[1].prefix, st[2].prefix};
+  const double count[TR_TERMS] = {out[7], out[16], out[17]};
+  double term[TR_TERMS];
+  for (int i = 0; i < TR_TERMS; ++i) {
+    double* tr = out + 20 + 5 * i;  // tr[0] = k, from the prepare kernel
+    term[i] = 0.0, tr[1] = tr[2] = tr[3] = tr[4] = 0.0;
+    if (tr[0] > 0.0) {              // k >= 1 means count >= 1 and at least one key at the threshold
+      const double w = (tr[0] - (double)n[2 * i]) / (double)n[2 * i + 1];
+      const double tied = w * s[2 * i + 1];
+      term[i] = (s[2 * i] + tied) / count[i];
+      tr[1] = (double)n[2 * i], tr[2] = (double)n[2 * i + 1], tr[3] = (double)__builtin_bit_cast(float, thr[i]), tr[4] = w;
+    }
+  }
+  const double spatial = alpha > 0.0 ? term[TR_DATA] + alpha * out[6] : term[TR_DATA];
+  out[0] = spatial;
+  out[1] = term[TR_STABLE];
+  out[2] = term[TR_ABSREL];
+  out[4] = stable_scale > 0.0 ? spatial + stable_scale * term[TR_STABLE] : spatial;
+  out[5] = term[TR_DATA];
+  for (int i = 35; i < 40; ++i) out[i] = 0.0;
+}
+
 }  // namespace
 
 extern "C" size_t vdn_depth_loss_workspace_bytes(int B, int T) {
   if (B <= 0 || T <= 0) return 0;
-  return sizeof(double) * Ws::slots((size_t)B, (size_t)B * T) + select2_workspace_bytes(B * T);
+  return sizeof(double) * Ws::slots((size_t)B, (size_t)B * T) + select_workspace_bytes(B * T, 2);
 }
 
-extern "C" int vdn_depth_loss(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
-                              double alpha, int scales, double stable_scale, void* workspace, float* scale_shift,
-                              double* frame_stats, int64_t* frame_counts, double* out, vdn_stream stream) {
+// the errors of vdn_depth_loss, which the trimmed entry point shares; nothing is launched
+static int depth_loss_check(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W, int scales,
+                            double stable_scale, void* workspace, float* scale_shift, double* frame_stats, int64_t* frame_counts,
+                            double* out) {
   if (!prediction || !target || !mask || !workspace || (!out && !scale_shift)) return VDN_EINVAL;
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || scales < 0) return VDN_EINVAL;
   if (out && stable_scale > 0.0 && T < 2) return VDN_EINVAL;  // the reference divides by a count of zero strides
@@ -396,19 +612,32 @@ extern "C" int vdn_depth_loss(const float* prediction, const float* target, cons
   if (((uintptr_t)prediction & 3) || ((uintptr_t)target & 3) || ((uintptr_t)scale_shift & 3)) return VDN_EALIGN;
   if (((uintptr_t)workspace & 7) || ((uintptr_t)frame_stats & 7) || ((uintptr_t)frame_counts & 7) || ((uintptr_t)out & 7))
     return VDN_EALIGN;
+  return VDN_OK;
+}
+
+// four pixels per lane when every frame of every plane starts on 16 bytes (the mask on 4) and holds whole quads
+static bool depth_loss_wide(const float* prediction, const float* target, const uint8_t* mask, int hw) {
+  return hw % 4 == 0 && !((uintptr_t)prediction & 15) && !((uintptr_t)target & 15) && !((uintptr_t)mask & 3);
+}
+
+extern "C" int vdn_depth_loss(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                              double alpha, int scales, double stable_scale, void* workspace, float* scale_shift,
+                              double* frame_stats, int64_t* frame_counts, double* out, vdn_stream stream) {
+  const int err = depth_loss_check(prediction, target, mask, B, T, H, W, scales, stable_scale, workspace, scale_shift, frame_stats,
+                                   frame_counts, out);
+  if (err != VDN_OK) return err;
   hipStream_t s = (hipStream_t)stream;
   const int F = B * T, hw = H * W;
   const dim3 grid((unsigned)F * DL_BPF), block(256);
-  // four pixels per lane when every frame of every plane starts on 16 bytes (the mask on 4) and holds whole quads
-  const bool wide = hw % 4 == 0 && !((uintptr_t)prediction & 15) && !((uintptr_t)target & 15) && !((uintptr_t)mask & 3);
+  const bool wide = depth_loss_wide(prediction, target, mask, hw);
   const Ws ws(workspace, B, T);
   if (wide) hipLaunchKernelGGL(fit_partial_kernel<4>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
   else hipLaunchKernelGGL(fit_partial_kernel<1>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
   hipLaunchKernelGGL(fit_solve_kernel, dim3(1), block, 0, s, workspace, B, T, frame_counts, scale_shift);
   if (out) {
     const uint32_t rank = (uint32_t)((hw - 1) / 2);  // torch.median: the lower of the two middle values
-    select2_launch(LossKey{prediction, target, mask, ws.ss, (size_t)hw, T}, F, (size_t)hw, rank, rank, ws.select, s);
-    hipLaunchKernelGGL(median_store_kernel, dim3(grid_for((size_t)F * 2, 1024)), block, 0, s, select2_state(ws.select, F), F, ws.med);
+    select_launch(LossKey{prediction, target, mask, ws.ss, (size_t)hw, T}, F, 1, (size_t)hw, SelRanks<2>{{rank, rank}, nullptr}, ws.select, s);
+    hipLaunchKernelGGL(median_store_kernel, dim3(grid_for((size_t)F * 2, 1024)), block, 0, s, select_state(ws.select, F, 2), F, ws.med);
     const int eff_scales = alpha > 0.0 ? scales : 0;  // the regulariser is skipped, as TrimmedProcrustesLoss skips it
     const int temporal = stable_scale > 0.0;
     if (wide) {
@@ -420,6 +649,42 @@ extern "C" int vdn_depth_loss(const float* prediction, const float* target, cons
     }
     hipLaunchKernelGGL(loss_finalise_kernel, dim3(1), block, 0, s, workspace, B, T, alpha, eff_scales, stable_scale, frame_stats, out);
   }
+  VDN_CHECK_LAUNCH();
+  return VDN_OK;
+}
+
+extern "C" size_t vdn_depth_loss_trimmed_workspace_bytes(int B, int T) {
+  if (B <= 0 || T <= 0) return 0;
+  return vdn_depth_loss_workspace_bytes(B, T) + sizeof(double) * Tw::slots((size_t)B * T) + select_workspace_bytes(1, TR_TERMS);
+}
+
+extern "C" int vdn_depth_loss_trimmed(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                                      double alpha, int scales, double stable_scale, double keep, void* workspace, float* scale_shift,
+                                      double* frame_stats, int64_t* frame_counts, double* out, vdn_stream stream) {
+  if (!out || !(keep > 0.0 && keep <= 1.0)) return VDN_EINVAL;  // a NaN fails both comparisons
+  int err = depth_loss_check(prediction, target, mask, B, T, H, W, scales, stable_scale, workspace, scale_shift, frame_stats,
+                             frame_counts, out);
+  if (err != VDN_OK) return err;
+  if ((uint64_t)B * T * (uint64_t)H * W > UINT32_MAX) return VDN_EUNSUPPORTED;  // the select's counters are 32-bit
+  err = vdn_depth_loss(prediction, target, mask, B, T, H, W, alpha, scales, stable_scale, workspace, scale_shift, frame_stats,
+                       frame_counts, out, stream);
+  if (err != VDN_OK) return err;
+  hipStream_t s = (hipStream_t)stream;
+  const int F = B * T, hw = H * W, temporal = stable_scale > 0.0;
+  const dim3 grid((unsigned)F * DL_BPF), block(256);
+  void* tws = (char*)workspace + vdn_depth_loss_workspace_bytes(B, T);
+  const Tw tw(tws, B, T);
+  const SelState* st = select_state(tw.select, 1, TR_TERMS);
+  hipLaunchKernelGGL(trim_prepare_kernel, dim3(1), block, 0, s, workspace, tws, B, T, keep, out);
+  auto run = [&](auto ppl) {
+    constexpr int PPL = decltype(ppl)::value;
+    select_launch(TrimKey<PPL>{prediction, target, mask, B, T, hw, temporal, workspace, tws}, F, F, (size_t)hw,
+                  SelRanks<TR_TERMS>{{0, 0, 0}, tw.rank}, tw.select, s);
+    hipLaunchKernelGGL(trim_sum_kernel<PPL>, grid, block, 0, s, prediction, target, mask, B, T, hw, temporal, workspace, tws, st);
+  };
+  if (depth_loss_wide(prediction, target, mask, hw)) run(IC<4>{});
+  else run(IC<1>{});
+  hipLaunchKernelGGL(trim_finalise_kernel, dim3(1), block, 0, s, tws, B, T, alpha, stable_scale, st, out);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

@@ -16,6 +16,9 @@
 // A lane owns four consecutive pixels whenever H * W is a multiple of 4, with 16-byte loads where the bases allow and a load
 // per pixel otherwise, so the sums and the gradient's bits do not depend on the tensors' alignment; one pixel per lane else.
 // Everything is fp64 computed from the float32 samples, contraction off; a dropped pixel is skipped by a branch.
+// The trimmed criterion (vdn_depth_loss_trimmed_backward) runs the same five passes: the data part of g_x and the temporal and
+// absRel parts of g_a carry the weight 1, w or 0 that the forward's selection gives their residual (loss_px.hpp), the key
+// recomputed from the inputs and compared with the threshold in out[20..34]. Untrimmed, every weight is an exact 1.
 #include "common.hpp"
 #include "reduce.hpp"
 #include <limits.h>
@@ -76,10 +79,12 @@ struct FrameCtx {
   float sc, sh;
   double mp, sp, mt, st, cnt;
   double alpha, c_sp, c_st, c_ar, Mtot, Mk[DL_MAX_SCALES], Mt, Mar;
+  const double* tr;  // out + 20 of vdn_depth_loss_trimmed: per term k | n_less | n_tied | thr | w; nullptr: every weight is 1
   bool has_prev, has_next;  // a frame of the same item before / after this one, when the temporal term is on
   __device__ FrameCtx(const float* pred, const float* target, const uint8_t* mask, int T, int H_, int W_, double alpha_, int scales_,
                       int temporal, const float* __restrict__ ss, const double* __restrict__ fs, const int64_t* __restrict__ fc,
-                      const double* __restrict__ out, const float* __restrict__ coeff, int f) {
+                      const double* __restrict__ out, const float* __restrict__ coeff, int trimmed, int f) {
+    tr = trimmed ? out + 20 : nullptr;
     H = H_, W = W_, hw = H_ * W_, scales = scales_, alpha = alpha_;
     pf = pred + (size_t)f * hw, tf = target + (size_t)f * hw, mf = mask + (size_t)f * hw;
     sc = ss[(f / T) * 2], sh = ss[(f / T) * 2 + 1];
@@ -95,6 +100,8 @@ struct FrameCtx {
   // the difference of the normalised maps at one pixel, exactly as the forward takes it
   __device__ __forceinline__ double diff(float a, float t) const { return ((double)a - mp) / sp - ((double)t - mt) / st; }
   __device__ __forceinline__ double diff_at(size_t o) const { return diff(aligned(sc, pf[o], sh), tf[o]); }
+  // the weight u of a counted element of `term` with residual r (loss_px.hpp): 1 when nothing is trimmed
+  __device__ __forceinline__ double weight(int term, double r) const { return tr ? trim_weight(tr + 5 * term, trim_key(r)) : 1.0; }
   // g_x of the kept pixel p = (y, x) whose difference is d: the data term's sign and, per grid, the integer sum of
   // sign(d_self - d_nb) over the kept neighbours, divided by the grid's kept points; grids in ascending order
   __device__ __forceinline__ double gx(int p, int y, int x, double d) const {
@@ -119,7 +126,7 @@ struct FrameCtx {
         reg += (double)n / Mk[k];
       }
     }
-    return c_sp * ((double)sgn(d) / Mtot + alpha * reg);
+    return c_sp * (weight(TR_DATA, fabs(d)) * (double)sgn(d) / Mtot + alpha * reg);
   }
   // g_a of the kept pixel p with aligned prediction a and target t, from its g_x; gs, gm, holder, th_self and th_next are
   // solve 1's results for this frame (th_next: of the next frame)
@@ -128,24 +135,24 @@ struct FrameCtx {
     double g = gxv / sp + gs * (double)sgn((double)a - mp) / cnt;
     if ((int64_t)p == holder) g += gm;
     if (Mt > 0.0) {
-      int later = 0, earlier = 0;
+      double later = 0.0, earlier = 0.0;
       if (has_prev && mf[(ptrdiff_t)p - hw] != 0) {  // the pair (f - 1, f): this frame is the later one
         const float tq = tf[(ptrdiff_t)p - hw], tg = t - tq;
         if (fabsf(tg) < th_self) {
           const float pg = a - aligned(sc, pf[(ptrdiff_t)p - hw], sh);
-          later = sgn((double)pg - (double)tg);
+          later = weight(TR_STABLE, res_stable(pg, tg)) * (double)sgn((double)pg - (double)tg);
         }
       }
       if (has_next && mf[(size_t)p + hw] != 0) {     // the pair (f, f + 1): this frame is the earlier one
         const float tq = tf[(size_t)p + hw], tg = tq - t;
         if (fabsf(tg) < th_next) {
           const float pg = aligned(sc, pf[(size_t)p + hw], sh) - a;
-          earlier = sgn((double)pg - (double)tg);
+          earlier = weight(TR_STABLE, res_stable(pg, tg)) * (double)sgn((double)pg - (double)tg);
         }
       }
-      g += c_st * (double)(later - earlier) / Mt;
+      g += c_st * (later - earlier) / Mt;
     }
-    if (Mar > 0.0 && t > 1e-3f && t < 70.f) g += c_ar * (double)sgn((double)a - (double)t) / ((double)t * Mar);
+    if (Mar > 0.0 && t > 1e-3f && t < 70.f) g += c_ar * (weight(TR_ABSREL, res_absrel(a, t)) * (double)sgn((double)a - (double)t)) / ((double)t * Mar);
     return g;
   }
 };
@@ -153,8 +160,8 @@ struct FrameCtx {
 #define GRAD_ARGS                                                                                                              \
   const float *__restrict__ pred, const float *__restrict__ target, const uint8_t *__restrict__ mask, int B, int T, int H, int W, \
       double alpha, int scales, int temporal, const float *__restrict__ ss, const double *__restrict__ fs,                      \
-      const int64_t *__restrict__ fc, const double *__restrict__ out, const float *__restrict__ coeff, void *__restrict__ workspace
-#define GRAD_CTX FrameCtx c(pred, target, mask, T, H, W, alpha, scales, temporal, ss, fs, fc, out, coeff, f)
+      const int64_t *__restrict__ fc, const double *__restrict__ out, const float *__restrict__ coeff, int trimmed, void *__restrict__ workspace
+#define GRAD_CTX FrameCtx c(pred, target, mask, T, H, W, alpha, scales, temporal, ss, fs, fc, out, coeff, trimmed, f)
 
 // ------------------------------------------------------------------------------------------------ pass 1
 template <int PPL, bool VEC>
@@ -362,15 +369,17 @@ extern "C" size_t vdn_depth_loss_backward_workspace_bytes(int B, int T, int H, i
   return sizeof(double) * (Gw::slots((size_t)B, F) + F * (size_t)H * W);
 }
 
-extern "C" int vdn_depth_loss_backward(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
-                                       double alpha, int scales, double stable_scale, const float* scale_shift,
-                                       const double* frame_stats, const int64_t* frame_counts, const double* out, const float* coeff,
-                                       void* workspace, float* grad_prediction, vdn_stream stream) {
+// trimmed: out is the f64 [40] of vdn_depth_loss_trimmed and out[20..34] weigh the three trimmed terms
+static int depth_loss_backward(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                               double alpha, int scales, double stable_scale, const float* scale_shift, const double* frame_stats,
+                               const int64_t* frame_counts, const double* out, const float* coeff, int trimmed, void* workspace,
+                               float* grad_prediction, vdn_stream stream) {
   if (!prediction || !target || !mask || !workspace || !scale_shift || !frame_stats || !frame_counts || !out || !coeff || !grad_prediction)
     return VDN_EINVAL;
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || scales < 0) return VDN_EINVAL;
   if (stable_scale > 0.0 && T < 2) return VDN_EINVAL;
   if ((int64_t)H * W > INT32_MAX || (int64_t)B * T > 65535 || scales > DL_MAX_SCALES) return VDN_EUNSUPPORTED;
+  if (trimmed && (uint64_t)B * T * (uint64_t)H * W > UINT32_MAX) return VDN_EUNSUPPORTED;  // as the trimmed forward
   if (((uintptr_t)prediction & 3) || ((uintptr_t)target & 3) || ((uintptr_t)scale_shift & 3) || ((uintptr_t)coeff & 3) ||
       ((uintptr_t)grad_prediction & 3))
     return VDN_EALIGN;
@@ -390,17 +399,37 @@ extern "C" int vdn_depth_loss_backward(const float* prediction, const float* tar
     constexpr int PPL = decltype(ppl)::value;
     constexpr bool VEC = decltype(v)::value != 0;
     hipLaunchKernelGGL((grad_stats_kernel<PPL, VEC>), grid, block, 0, s, prediction, target, mask, B, T, H, W, alpha, eff_scales,
-                       temporal, scale_shift, frame_stats, frame_counts, out, coeff, workspace);
+                       temporal, scale_shift, frame_stats, frame_counts, out, coeff, trimmed, workspace);
     hipLaunchKernelGGL(grad_solve1_kernel, dim3(1), block, 0, s, workspace, B, T, hw, frame_stats, frame_counts);
     hipLaunchKernelGGL((grad_fit_partial_kernel<PPL, VEC>), grid, block, 0, s, prediction, target, mask, B, T, H, W, alpha, eff_scales,
-                       temporal, scale_shift, frame_stats, frame_counts, out, coeff, workspace);
+                       temporal, scale_shift, frame_stats, frame_counts, out, coeff, trimmed, workspace);
     hipLaunchKernelGGL(grad_solve2_kernel, dim3(1), block, 0, s, workspace, B, T);
     hipLaunchKernelGGL((grad_write_kernel<PPL, VEC>), grid, block, 0, s, prediction, target, mask, B, T, H, W, alpha, eff_scales,
-                       temporal, scale_shift, frame_stats, frame_counts, out, coeff, workspace, grad_prediction);
+                       temporal, scale_shift, frame_stats, frame_counts, out, coeff, trimmed, workspace, grad_prediction);
   };
   if (vec) launch(IC<4>{}, IC<1>{});
   else if (quads) launch(IC<4>{}, IC<0>{});
   else launch(IC<1>{}, IC<0>{});
   VDN_CHECK_LAUNCH();
   return VDN_OK;
+}
+
+extern "C" int vdn_depth_loss_backward(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
+                                       double alpha, int scales, double stable_scale, const float* scale_shift,
+                                       const double* frame_stats, const int64_t* frame_counts, const double* out, const float* coeff,
+                                       void* workspace, float* grad_prediction, vdn_stream stream) {
+  return depth_loss_backward(prediction, target, mask, B, T, H, W, alpha, scales, stable_scale, scale_shift, frame_stats, frame_counts,
+                             out, coeff, 0, workspace, grad_prediction, stream);
+}
+
+extern "C" size_t vdn_depth_loss_trimmed_backward_workspace_bytes(int B, int T, int H, int W) {
+  return vdn_depth_loss_backward_workspace_bytes(B, T, H, W);
+}
+
+extern "C" int vdn_depth_loss_trimmed_backward(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H,
+                                               int W, double alpha, int scales, double stable_scale, const float* scale_shift,
+                                               const double* frame_stats, const int64_t* frame_counts, const double* out,
+                                               const float* coeff, void* workspace, float* grad_prediction, vdn_stream stream) {
+  return depth_loss_backward(prediction, target, mask, B, T, H, W, alpha, scales, stable_scale, scale_shift, frame_stats, frame_counts,
+                             out, coeff, 1, workspace, grad_prediction, stream);
 }

@@ -23,6 +23,28 @@ __device__ __forceinline__ float aligned(float scale, float p, float shift) {
   return m + shift;
 }
 
+// The trimmed criterion (vdn_depth_loss_trimmed and its backward): the three residuals |r| it selects among, in fp64 exactly
+// as the untrimmed passes sum them, and the selection key of one. The forward's select, its sums and the backward's weights
+// all come through these, so they decide on the same bits.
+enum { TR_DATA = 0, TR_STABLE = 1, TR_ABSREL = 2, TR_TERMS = 3 };
+__device__ __forceinline__ double res_data(float a, float t, double mp, double sp, double mt, double st) {
+  return fabs(((double)a - mp) / sp - ((double)t - mt) / st);
+}
+__device__ __forceinline__ double res_stable(float pg, float tg) { return fabs((double)pg - (double)tg); }
+__device__ __forceinline__ double res_absrel(float a, float t) { return fabs(((double)a - (double)t) / (double)t); }
+// The float32 rounding of |r| >= 0: its bit pattern is ordered. Every NaN is the one key above +inf's, as torch.sort puts it.
+__device__ __forceinline__ uint32_t trim_key(double r) {
+  const float v = (float)r;
+  return v != v ? 0x7FC00000u : __builtin_bit_cast(uint32_t, v);
+}
+// The weight of a counted element with key `key`: 1 below the threshold, w at it, 0 above. tr = out + 20 + 5 * term:
+// k | n_less | n_tied | thr | w; k == 0 keeps nothing.
+__device__ __forceinline__ double trim_weight(const double* __restrict__ tr, uint32_t key) {
+  if (!(tr[0] > 0.0)) return 0.0;
+  const uint32_t thr = __builtin_bit_cast(uint32_t, (float)tr[3]);
+  return key < thr ? 1.0 : (key == thr ? tr[4] : 0.0);
+}
+
 // PPL consecutive pixels of a frame: 4 or 1. VEC: the four come by one 16-byte load per float plane and one 4-byte load of the
 // mask (the bases must allow it); otherwise every pixel by a load of its own, the lane owning the same pixels either way.
 template <int PPL, bool VEC = (PPL == 4)>

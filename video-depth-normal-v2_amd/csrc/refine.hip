@@ -135,15 +135,15 @@ int launch_elementwise(const float* a, const float* b, float* out, size_t n, Op 
 }  // namespace
 
 extern "C" size_t vdn_frame_median_workspace_bytes(int frames) {
-  return frames <= 0 ? 0 : select2_workspace_bytes(frames);
+  return frames <= 0 ? 0 : select_workspace_bytes(frames, 2);
 }
 
 extern "C" int vdn_frame_median(const float* x, int frames, size_t n, float* median, void* workspace, vdn_stream stream) {
   if (!x || !median || !workspace || frames <= 0 || n == 0) return VDN_EINVAL;
   if (n >= ((size_t)1 << 32)) return VDN_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  select2_launch(SampleKey{x, n}, frames, n, (uint32_t)((n - 1) / 2), (uint32_t)(n / 2), workspace, s);  // floor / ceil of 0.5 (n - 1)
-  hipLaunchKernelGGL(median_final_kernel, dim3((frames + 63) / 64), dim3(64), 0, s, select2_state(workspace, frames), frames, n, median);
+  select_launch(SampleKey{x, n}, frames, 1, n, SelRanks<2>{{(uint32_t)((n - 1) / 2), (uint32_t)(n / 2)}, nullptr}, workspace, s);  // floor / ceil of 0.5 (n - 1)
+  hipLaunchKernelGGL(median_final_kernel, dim3((frames + 63) / 64), dim3(64), 0, s, select_state(workspace, frames, 2), frames, n, median);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

@@ -1,12 +1,20 @@
-// The exact three-pass radix select on order-preserving 32-bit keys, stated once: per frame, TWO selections run in the
-// same passes (slot 0 and slot 1). A key functor gives the two keys of element i of frame f; the two requested ranks
-// (0-based, in the sorted order of the slot's n keys) are the same for every frame.
-//   vdn_frame_median (refine.hip)  one key per element, ranks floor and ceil of (n - 1) / 2: both middle order statistics;
-//   vdn_depth_loss   (loss.hip)    slot 0 the aligned prediction, slot 1 the target, both under the mask, one rank.
-// Passes take the top 11, the next 11 and the last 10 bits: a histogram per (frame, slot) of the keys that match the
-// prefix decided so far (integer atomics, in LDS and then in `hist`: counts do not depend on the order, so two runs give
-// the same bits), then a one-block scan that finds the bin holding the rank, extends the prefix and clears the bins. After
-// select2_launch, st[f * 2 + slot].prefix is the selected key.
+// The exact three-pass radix select on order-preserving 32-bit keys, stated once. A SET is `group` consecutive frames whose
+// elements are selected among together; per set, SLOTS selections run in the same passes. A key functor states
+//   static constexpr int SLOTS   selections per set;
+//   static constexpr int PER     consecutive elements of a frame it takes per call (n must be a multiple of PER);
+//   uint32_t operator()(int f, size_t i, uint32_t (&key)[PER][SLOTS]) const
+//                                the keys of elements i .. i + PER - 1 of frame f; bit e * SLOTS + s of the result says that
+//                                element i + e takes part in slot s. An element that does not is skipped: it has no key.
+// The requested ranks (0-based, in the sorted order of the slot's keys) are the same for every set; they are given by value
+// or read from device memory when the select starts (SelRanks), so a rank may be the result of an earlier kernel.
+//   vdn_frame_median       (refine.hip)  a set per frame, one key per element, ranks floor and ceil of (n - 1) / 2;
+//   vdn_depth_loss         (loss.hip)    a set per frame, slot 0 the aligned prediction, slot 1 the target, one rank;
+//   vdn_depth_loss_trimmed (loss.hip)    one set of all frames, slots data / stable / absRel, ranks computed on the device.
+// Passes take the top 11, the next 11 and the last 10 bits: a histogram per (set, slot) of the keys that match the prefix
+// decided so far (integer atomics, in LDS and then in `hist`: counts do not depend on the order, so two runs give the same
+// bits), then a one-block scan that finds the bin holding the rank, extends the prefix and clears the bins. After
+// select_launch, st[set * SLOTS + slot].prefix is the selected key. A slot with fewer keys than its rank + 1 ends on its last
+// bin; its prefix means nothing.
 #pragma once
 #include "common.hpp"
 
@@ -23,58 +31,73 @@ __device__ __forceinline__ float key_value(uint32_t k) {
   return __builtin_bit_cast(float, u);
 }
 
-struct SelState {  // per (frame, slot)
+struct SelState {  // per (set, slot)
   uint32_t prefix;  // key bits decided so far (right-aligned)
   uint32_t k;       // remaining rank inside the prefix
 };
 
+template <int SLOTS>
+struct SelRanks {
+  uint32_t host[SLOTS];  // used when dev == nullptr
+  const uint32_t* dev;   // [SLOTS] in device memory, read by the select's first kernel
+};
+
 // the plain sample: both slots select among the same keys
 struct SampleKey {
+  static constexpr int SLOTS = 2, PER = 1;
   const float* x;
   size_t n;
-  __device__ __forceinline__ void operator()(int f, size_t i, uint32_t& k0, uint32_t& k1) const {
-    k0 = k1 = ordered_key(x[(size_t)f * n + i]);
+  __device__ __forceinline__ uint32_t operator()(int f, size_t i, uint32_t (&key)[1][2]) const {
+    key[0][0] = key[0][1] = ordered_key(x[(size_t)f * n + i]);
+    return 3u;
   }
 };
 
-__global__ void select_init_kernel(SelState* st, uint32_t* hist, int F, uint32_t rank0, uint32_t rank1) {
+template <int SLOTS>
+__global__ void select_init_kernel(SelState* st, uint32_t* hist, int sets, SelRanks<SLOTS> ranks) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < F * 2) {
+  if (i < sets * SLOTS) {
     st[i].prefix = 0;
-    st[i].k = (i & 1) ? rank1 : rank0;
+    st[i].k = ranks.dev ? ranks.dev[i % SLOTS] : ranks.host[i % SLOTS];
   }
-  for (size_t j = i; j < (size_t)F * 2 * NBIN; j += (size_t)gridDim.x * blockDim.x) hist[j] = 0;
+  for (size_t j = i; j < (size_t)sets * SLOTS * NBIN; j += (size_t)gridDim.x * blockDim.x) hist[j] = 0;
 }
 
 // PASS 0: top 11 bits; PASS 1: next 11 among keys whose top 11 equal the prefix; PASS 2: last 10
 template <int PASS, typename KeyFn>
-__global__ __launch_bounds__(256) void select_hist_kernel(const KeyFn key_of, size_t n, const SelState* __restrict__ st,
+__global__ __launch_bounds__(256) void select_hist_kernel(const KeyFn key_of, size_t n, int group, const SelState* __restrict__ st,
                                                           uint32_t* __restrict__ hist) {
-  __shared__ uint32_t h[2][NBIN];
-  const int f = blockIdx.y;
-  for (int i = threadIdx.x; i < 2 * NBIN; i += 256) (&h[0][0])[i] = 0;
+  constexpr int S = KeyFn::SLOTS, E = KeyFn::PER;
+  static_assert(S * E <= 32, "one bit per (element, slot)");
+  __shared__ uint32_t h[S][NBIN];
+  const int f = blockIdx.y, set = f / group;
+  for (int i = threadIdx.x; i < S * NBIN; i += 256) (&h[0][0])[i] = 0;
   __syncthreads();
-  const uint32_t p[2] = {st[f * 2].prefix, st[f * 2 + 1].prefix};
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    uint32_t key[2];
-    key_of(f, i, key[0], key[1]);
+  uint32_t p[S];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      uint32_t bin, pre;
-      if (PASS == 0) { bin = key[s] >> (32 - BITS0); pre = 0; }
-      else if (PASS == 1) { bin = (key[s] >> BITS2) & ((1u << BITS1) - 1); pre = key[s] >> (BITS1 + BITS2); }
-      else { bin = key[s] & ((1u << BITS2) - 1); pre = key[s] >> BITS2; }
-      if (PASS == 0 || pre == p[s]) atomicAdd(&h[s][bin], 1u);
-    }
+  for (int s = 0; s < S; ++s) p[s] = st[set * S + s].prefix;
+  for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * E; i < n; i += (size_t)gridDim.x * 256 * E) {
+    uint32_t key[E][S];
+    const uint32_t on = key_of(f, i, key);
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        uint32_t bin, pre;
+        if (PASS == 0) { bin = key[e][s] >> (32 - BITS0); pre = 0; }
+        else if (PASS == 1) { bin = (key[e][s] >> BITS2) & ((1u << BITS1) - 1); pre = key[e][s] >> (BITS1 + BITS2); }
+        else { bin = key[e][s] & ((1u << BITS2) - 1); pre = key[e][s] >> BITS2; }
+        if (((on >> (e * S + s)) & 1u) && (PASS == 0 || pre == p[s])) atomicAdd(&h[s][bin], 1u);
+      }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < 2 * NBIN; i += 256) {
+  for (int i = threadIdx.x; i < S * NBIN; i += 256) {
     const uint32_t v = (&h[0][0])[i];
-    if (v) atomicAdd(hist + (size_t)f * 2 * NBIN + i, v);
+    if (v) atomicAdd(hist + (size_t)set * S * NBIN + i, v);
   }
 }
 
-// One block of 256 lanes per (frame, slot): find the bin holding rank k, extend the prefix, clear the bins. The bin is the
+// One block of 256 lanes per (set, slot): find the bin holding rank k, extend the prefix, clear the bins. The bin is the
 // first one whose inclusive running count exceeds k (the last bin if none does). Each lane sums its own run of bins, the
 // lane whose run holds the rank walks it: the same bin and the same remaining rank as one lane walking all bins (which took
 // a dependent load per bin, and most of the select's time), found by integer adds in any order.
@@ -111,21 +134,26 @@ __global__ __launch_bounds__(256) void select_scan_kernel(SelState* st, uint32_t
   for (int i = threadIdx.x; i < NBIN; i += 256) h[i] = 0;
 }
 
-inline size_t select2_workspace_bytes(int frames) { return (size_t)frames * 2 * (NBIN * sizeof(uint32_t) + sizeof(SelState)); }
-inline SelState* select2_state(void* workspace, int frames) { return (SelState*)((uint32_t*)workspace + (size_t)frames * 2 * NBIN); }
+inline size_t select_workspace_bytes(int sets, int slots) { return (size_t)sets * slots * (NBIN * sizeof(uint32_t) + sizeof(SelState)); }
+inline SelState* select_state(void* workspace, int sets, int slots) { return (SelState*)((uint32_t*)workspace + (size_t)sets * slots * NBIN); }
 
-// n < 2^32 keys per frame; workspace of select2_workspace_bytes(frames), 4-byte aligned. Seven launches on s.
+// `frames` frames of n elements each (n a multiple of KeyFn::PER, n < 2^32), `group` frames to a set (frames a multiple of
+// group; fewer than 2^32 keys per set); workspace of select_workspace_bytes(frames / group, KeyFn::SLOTS), 4-byte aligned.
+// Seven launches on s.
 template <typename KeyFn>
-inline void select2_launch(const KeyFn& key_of, int frames, size_t n, uint32_t rank0, uint32_t rank1, void* workspace, hipStream_t s) {
+inline void select_launch(const KeyFn& key_of, int frames, int group, size_t n, const SelRanks<KeyFn::SLOTS>& ranks, void* workspace,
+                          hipStream_t s) {
+  constexpr int S = KeyFn::SLOTS;
+  const int sets = frames / group;
   uint32_t* hist = (uint32_t*)workspace;
-  SelState* st = select2_state(workspace, frames);
-  const dim3 grid(grid_for(n, 64), frames), scan(frames * 2), block(256);
-  hipLaunchKernelGGL(select_init_kernel, dim3(grid_for((size_t)frames * 2 * NBIN, 1024)), block, 0, s, st, hist, frames, rank0, rank1);
-  hipLaunchKernelGGL((select_hist_kernel<0, KeyFn>), grid, block, 0, s, key_of, n, st, hist);
+  SelState* st = select_state(workspace, sets, S);
+  const dim3 grid(grid_for((n + KeyFn::PER - 1) / KeyFn::PER, 64), frames), scan(sets * S), block(256);
+  hipLaunchKernelGGL(select_init_kernel<S>, dim3(grid_for((size_t)sets * S * NBIN, 1024)), block, 0, s, st, hist, sets, ranks);
+  hipLaunchKernelGGL((select_hist_kernel<0, KeyFn>), grid, block, 0, s, key_of, n, group, st, hist);
   hipLaunchKernelGGL(select_scan_kernel<0>, scan, block, 0, s, st, hist);
-  hipLaunchKernelGGL((select_hist_kernel<1, KeyFn>), grid, block, 0, s, key_of, n, st, hist);
+  hipLaunchKernelGGL((select_hist_kernel<1, KeyFn>), grid, block, 0, s, key_of, n, group, st, hist);
   hipLaunchKernelGGL(select_scan_kernel<1>, scan, block, 0, s, st, hist);
-  hipLaunchKernelGGL((select_hist_kernel<2, KeyFn>), grid, block, 0, s, key_of, n, st, hist);
+  hipLaunchKernelGGL((select_hist_kernel<2, KeyFn>), grid, block, 0, s, key_of, n, group, st, hist);
   hipLaunchKernelGGL(select_scan_kernel<2>, scan, block, 0, s, st, hist);
 }
 

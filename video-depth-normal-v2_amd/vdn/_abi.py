@@ -141,6 +141,12 @@ EXPORTS = {
     "vdn_depth_loss_backward_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vdn_depth_loss_backward": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, fp, vp, vp, vp,
                                           fp, vp, fp, vp]),
+    "vdn_depth_loss_trimmed_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "vdn_depth_loss_trimmed": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, vp,
+                                         fp, vp, vp, vp, vp]),
+    "vdn_depth_loss_trimmed_backward_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vdn_depth_loss_trimmed_backward": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, fp,
+                                                  vp, vp, vp, fp, vp, fp, vp]),
     "vdn_prep_trip": (C.c_int, [C.c_int]),
     "vdn_prep_depth_workspace_bytes": (C.c_size_t, [C.c_int]),
     "vdn_prep_rgb": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

@@ -484,6 +484,43 @@ class Runtime:
                      float(alpha), int(scales), float(stable_scale), scale_shift.data_ptr(), frame_stats.data_ptr(),
                      frame_counts.data_ptr(), out.data_ptr(), coeff.data_ptr(), ws.data_ptr(), grad.data_ptr())
 
+    def depth_loss_trimmed(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, out: torch.Tensor, keep: float,
+                           alpha: float = 0.5, scales: int = 4, stable_scale: float = 10.0, scale_shift: Optional[torch.Tensor] = None,
+                           frame_stats: Optional[torch.Tensor] = None, frame_counts: Optional[torch.Tensor] = None):
+        """out[0:40] (float64) <- the trimmed VideoDepthLoss, keep = 1 - trim in (0, 1] (vdn_depth_loss_trimmed; include/vdn.h
+        has the layout)."""
+        B, T, H, W = prediction.shape
+        for t in (prediction, target):
+            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, T, H, W), t.shape
+        assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, T, H, W)
+        assert out.dtype == torch.float64 and out.numel() >= 40 and out.is_contiguous()
+        assert scale_shift is None or (scale_shift.dtype == torch.float32 and scale_shift.numel() == 2 * B and scale_shift.is_contiguous())
+        assert frame_stats is None or (frame_stats.dtype == torch.float64 and frame_stats.numel() == 4 * B * T and frame_stats.is_contiguous())
+        assert frame_counts is None or (frame_counts.dtype == torch.int64 and frame_counts.numel() == B * T and frame_counts.is_contiguous())
+        ws = self.buf("depth_loss_trimmed_ws", (abi.lib.vdn_depth_loss_trimmed_workspace_bytes(B, T) // 8,), torch.float64)
+        self._launch(abi.lib.vdn_depth_loss_trimmed, prediction.data_ptr(), target.data_ptr(), mask.data_ptr(), B, T, H, W, float(alpha),
+                     int(scales), float(stable_scale), float(keep), ws.data_ptr(), self._p(scale_shift), self._p(frame_stats),
+                     self._p(frame_counts), out.data_ptr())
+
+    def depth_loss_trimmed_backward(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, alpha: float, scales: int,
+                                    stable_scale: float, scale_shift: torch.Tensor, frame_stats: torch.Tensor,
+                                    frame_counts: torch.Tensor, out: torch.Tensor, coeff: torch.Tensor, grad: torch.Tensor):
+        """As depth_loss_backward for the trimmed criterion (vdn_depth_loss_trimmed_backward): out is the float64 [40] that
+        depth_loss_trimmed wrote for the same inputs and arguments."""
+        B, T, H, W = prediction.shape
+        for t in (prediction, target, grad):
+            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, T, H, W), t.shape
+        assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, T, H, W)
+        assert scale_shift.dtype == torch.float32 and scale_shift.numel() == 2 * B and scale_shift.is_contiguous()
+        assert frame_stats.dtype == torch.float64 and frame_stats.numel() == 4 * B * T and frame_stats.is_contiguous()
+        assert frame_counts.dtype == torch.int64 and frame_counts.numel() == B * T and frame_counts.is_contiguous()
+        assert out.dtype == torch.float64 and out.numel() >= 40 and out.is_contiguous()
+        assert coeff.dtype == torch.float32 and coeff.numel() == 3 and coeff.is_contiguous()
+        ws = self.buf("depth_loss_backward_ws", (abi.lib.vdn_depth_loss_trimmed_backward_workspace_bytes(B, T, H, W) // 8,), torch.float64)
+        self._launch(abi.lib.vdn_depth_loss_trimmed_backward, prediction.data_ptr(), target.data_ptr(), mask.data_ptr(), B, T, H, W,
+                     float(alpha), int(scales), float(stable_scale), scale_shift.data_ptr(), frame_stats.data_ptr(),
+                     frame_counts.data_ptr(), out.data_ptr(), coeff.data_ptr(), ws.data_ptr(), grad.data_ptr())
+
     def prep_rgb(self, x: torch.Tensor, out: torch.Tensor, normalize: bool):
         """out f32 [F, 3, H, W] <- clamp(x, 0, 1), then the ImageNet mean / std when `normalize` (vdn_prep_rgb); out may be x."""
         F, _, H, W = x.shape

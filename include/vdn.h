@@ -641,6 +641,58 @@ int vdn_prep_rgb(const float* in, float* out, int frames, int H, int W, int norm
 int vdn_prep_depth(const float* in, const uint8_t* mask, float* out, int B, int64_t n, int reciprocal, int clamp0,
                    int normalize, void* workspace, float* minmax, vdn_stream stream);
 
+/* The metric-depth branch's criterion and scores: metric_depth/util/loss.py (SiLogLoss), metric_depth/util/metric.py
+ * (eval_depth) and the body of the validation loop of metric_depth/train.py:160-177. Stateless, caller's stream, caller-owned
+ * buffers, no host synchronisation, no atomics: two runs give the same bits.
+ * Kept pixels. A pixel is kept when its mask byte EQUALS 1 (the reference's valid_mask == 1: a byte of 2 drops, unlike the
+ * "non-zero = keep" masks of vdn_depth_loss) and, with bounded != 0, depth >= min_depth and depth <= max_depth, the bounds
+ * rounded to float32 and compared in float32 (torch's rule for a float32 tensor against a Python number); a NaN depth fails
+ * them. mask NULL: every byte is 1. A dropped pixel is skipped by a branch, so nothing under it (a NaN, an inf) reaches a
+ * sum, where the reference indexes with the mask: the two agree.
+ * Arithmetic. float32, one IEEE rounding per operation, nothing contracted: the resampled prediction, thresh =
+ * max(fdiv(t, p), fdiv(p, t)) (a NaN wins, as torch.max) compared with 1.25, 1.5625 and 1.953125, and d_k = fdiv((float)
+ * count_k, (float)n). fp64 from the float32 inputs on, products and sums rounded separately: the differences, log and log10,
+ * the per-pixel terms, every sum, the means and the square roots. A non-positive prediction under a kept pixel gives what
+ * IEEE log gives. Sums have a fixed order: a lane's stride through its block's share, the wave and the block (four waves of
+ * 64 lanes, a butterfly and ((w0 + w1) + (w2 + w3))), then the item's 256 per-block partials the same way.
+ * vdn_metric_eval  pred f32 [items, ph, pw], depth f32 [items, H, W], valid u8 [items, H, W] or NULL -> out f64 [items][10] =
+ *                  n | d1 d2 d3 abs_rel sq_rel rmse rmse_log log10 silog, n the item's kept pixels; an item with n == 0 gets
+ *                  nine NaN (0 / 0), as the reference's eval_depth of an empty vector. (ph, pw) != (H, W): the prediction is
+ *                  sampled at each ground-truth pixel as F.interpolate(mode='bilinear', align_corners=True) places it, scale
+ *                  = (in - 1) / (out - 1) in float32 (0 for out == 1), src = fl(scale * dst), i0 = min((int)src, in - 1), l =
+ *                  fl(src - i0), top = fl(fl(fl(1 - lx) a00) + fl(lx a01)), bot the same on the lower row, v = fl(fl(fl(1 -
+ *                  ly) top) + fl(ly bot)); the resized map is never written. Two launches: per-block partials into
+ *                  `workspace` (vdn_metric_workspace_bytes(items) bytes), then one block per item.
+ * vdn_silog_loss   pred, target f32 [count], mask u8 [count] or NULL -> out f64 [4] = loss | n | sum dl | sum dl^2 over the
+ *                  kept pixels, dl = log(target) - log(pred), loss = sqrt(sum dl^2 / n - lambd (sum dl / n)^2). `target` is
+ *                  what the bounds test. Two launches; workspace of vdn_silog_loss_workspace_bytes() bytes.
+ * vdn_silog_loss_backward  grad f32 [count] <- (float)(coeff[0] * -(dl - lambd * sum dl / n) / (n * loss * pred)) at kept
+ *                  pixels, +0.0 at dropped ones; `state` is the out[4] that vdn_silog_loss wrote for the same inputs and
+ *                  arguments, coeff f32 [1] on the device (the gradient of whatever follows with respect to the loss). One
+ *                  launch, elementwise.
+ *                    case                                          loss   gradient
+ *                    no kept pixel                                 NaN    +0.0 everywhere
+ *                    pred == target at every kept pixel (sqrt(0))  0      NaN at kept pixels, +0.0 at dropped ones
+ *                    negative radicand                             NaN    NaN at kept pixels, +0.0 at dropped ones
+ *                  as the reference's autograd gives them on the CPU.
+ * Load shapes: where the item's length (count) is a multiple of 4, the float pointers are 16-byte aligned and the mask is
+ * 4-byte aligned, a lane handles four floats per 16-byte load; one element otherwise. The values are the same either way.
+ * vdn_metric_trip(wide): the elements of one item that one trip of the grid covers (256 blocks x 256 lanes x 4 or 1); a
+ * lane issues the loads of four trips together, and a longer item sends it round its loop again.
+ * Errors, all returned before anything is launched. VDN_EINVAL: a null required pointer, a size <= 0, bounded with a NaN
+ * bound. VDN_EUNSUPPORTED: H * W, ph * pw or count above INT32_MAX, items above 65535. VDN_EALIGN: a float pointer off 4
+ * bytes; workspace, out or state off 8.                                                                                  */
+int vdn_metric_trip(int wide);
+size_t vdn_metric_workspace_bytes(int items);
+int vdn_metric_eval(const float* pred, const float* depth, const uint8_t* valid, int items, int ph, int pw, int H, int W,
+                    int bounded, double min_depth, double max_depth, void* workspace, double* out, vdn_stream stream);
+size_t vdn_silog_loss_workspace_bytes(void);
+int vdn_silog_loss(const float* pred, const float* target, const uint8_t* mask, int64_t count, double lambd, int bounded,
+                   double min_depth, double max_depth, void* workspace, double* out, vdn_stream stream);
+int vdn_silog_loss_backward(const float* pred, const float* target, const uint8_t* mask, int64_t count, double lambd, int bounded,
+                            double min_depth, double max_depth, const double* state, const float* coeff, float* grad,
+                            vdn_stream stream);
+
 /* The colourised depth the reference's front ends write to disk, made on the device. Replaces, per frame, run.py:59-71,
  * run_video.py:75-89 and metric_depth/run.py:67-78 (min/max of the frame, matplotlib palette or a grey triple, BGR,
  * optionally cv2.hconcat([raw, 50 white columns, depth])) and, per clip, save_video of utils/dc_utils.py:72-86 (one min/max

@@ -42,6 +42,9 @@ def __getattr__(name):
     if name == "prep":   # the scripts' batch preparation on the device (vdn/prep.py)
         import importlib
         return importlib.import_module(".prep", __name__)
+    if name == "metric":  # SiLogLoss and eval_depth's nine metrics of the metric-depth branch on the device (vdn/metric.py)
+        import importlib
+        return importlib.import_module(".metric", __name__)
     if name == "steps":  # the bodies of the scripts' validate and evaluate loops, without host synchronisation (vdn/steps.py)
         import importlib
         return importlib.import_module(".steps", __name__)

@@ -151,6 +151,12 @@ EXPORTS = {
     "vdn_prep_depth_workspace_bytes": (C.c_size_t, [C.c_int]),
     "vdn_prep_rgb": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_prep_depth": (C.c_int, [fp, vp, fp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, vp, fp, vp]),
+    "vdn_metric_trip": (C.c_int, [C.c_int]),
+    "vdn_metric_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "vdn_metric_eval": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]),
+    "vdn_silog_loss_workspace_bytes": (C.c_size_t, []),
+    "vdn_silog_loss": (C.c_int, [fp, fp, vp, C.c_int64, C.c_double, C.c_int, C.c_double, C.c_double, vp, vp, vp]),
+    "vdn_silog_loss_backward": (C.c_int, [fp, fp, vp, C.c_int64, C.c_double, C.c_int, C.c_double, C.c_double, vp, fp, fp, vp]),
     "vdn_minmax_workspace_bytes": (C.c_size_t, [C.c_int]),
     "vdn_minmax_f32": (C.c_int, [fp, C.c_int, C.c_size_t, vp, fp, vp]),
     "vdn_colorize": (C.c_int, [fp, fp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),

@@ -541,6 +541,48 @@ class Runtime:
         self._launch(abi.lib.vdn_prep_depth, x.data_ptr(), self._p(mask), out.data_ptr(), B, n, int(reciprocal), int(clamp0),
                      int(normalize), self._p(ws), self._p(minmax))
 
+    @staticmethod
+    def _bounds(bounds):
+        return (0, 0.0, 0.0) if bounds is None else (1, float(bounds[0]), float(bounds[1]))
+
+    def metric_eval(self, pred: torch.Tensor, depth: torch.Tensor, valid: Optional[torch.Tensor], out: torch.Tensor, bounds=None):
+        """out f64 [B, 10] <- n and eval_depth's nine metrics of f32 pred [B, h, w] against f32 depth [B, H, W] under the u8
+        mask [B, H, W] (byte == 1 keeps; None: all kept) and, with bounds = (min_depth, max_depth), those (vdn_metric_eval)."""
+        B, H, W = depth.shape
+        assert pred.is_contiguous() and pred.dtype == torch.float32 and pred.dim() == 3 and pred.shape[0] == B, pred.shape
+        assert depth.is_contiguous() and depth.dtype == torch.float32
+        assert valid is None or (valid.is_contiguous() and valid.dtype == torch.uint8 and tuple(valid.shape) == (B, H, W))
+        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (B, 10)
+        ws = self.buf("metric_ws", (abi.lib.vdn_metric_workspace_bytes(B) // 8,), torch.float64)
+        self._launch(abi.lib.vdn_metric_eval, pred.data_ptr(), depth.data_ptr(), self._p(valid), B, pred.shape[1], pred.shape[2],
+                     H, W, *self._bounds(bounds), ws.data_ptr(), out.data_ptr())
+
+    def silog_loss(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Tensor, lambd: float,
+                   bounds=None):
+        """out f64 [4] <- loss | n | sum dl | sum dl^2 of SiLogLoss over f32 pred, target and the u8 mask of equal size
+        (vdn_silog_loss)."""
+        n = pred.numel()
+        for t in (pred, target):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == n, t.shape
+        assert mask is None or (mask.is_contiguous() and mask.dtype == torch.uint8 and mask.numel() == n)
+        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == 4
+        ws = self.buf("silog_ws", (abi.lib.vdn_silog_loss_workspace_bytes() // 8,), torch.float64)
+        self._launch(abi.lib.vdn_silog_loss, pred.data_ptr(), target.data_ptr(), self._p(mask), n, float(lambd),
+                     *self._bounds(bounds), ws.data_ptr(), out.data_ptr())
+
+    def silog_loss_backward(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], state: torch.Tensor,
+                            coeff: torch.Tensor, grad: torch.Tensor, lambd: float, bounds=None):
+        """grad f32 <- coeff * d loss / d pred (vdn_silog_loss_backward); state is what silog_loss wrote for the same inputs
+        and arguments, coeff f32 [1] on the device."""
+        n = pred.numel()
+        for t in (pred, target, grad):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == n, t.shape
+        assert mask is None or (mask.is_contiguous() and mask.dtype == torch.uint8 and mask.numel() == n)
+        assert state.is_contiguous() and state.dtype == torch.float64 and state.numel() == 4
+        assert coeff.is_contiguous() and coeff.dtype == torch.float32 and coeff.numel() == 1 and coeff.is_cuda
+        self._launch(abi.lib.vdn_silog_loss_backward, pred.data_ptr(), target.data_ptr(), self._p(mask), n, float(lambd),
+                     *self._bounds(bounds), state.data_ptr(), coeff.data_ptr(), grad.data_ptr())
+
     def minmax(self, x: torch.Tensor, groups: int, out: torch.Tensor):
         """out f32 [groups, 2] <- {min, max} of each of the `groups` equal runs of contiguous f32 x (vdn_minmax_f32)."""
         assert x.is_contiguous() and x.dtype == torch.float32 and x.numel() % groups == 0

@@ -10,7 +10,16 @@ MetricMeter.means() when the loop has ended.
     avg_losses = meter.averages()
 
 `model` is any callable: model(input_depth, rgb) -> (depth, normals) as scripts/train.py and evaluate.py call it (with_rgb=True),
-or model(input_depth) -> depth as the _v2 .. _v4 scripts do (with_rgb=False). Nothing here knows the engines."""
+or model(input_depth) -> depth as the _v2 .. _v4 scripts do (with_rgb=False). Nothing here knows the engines.
+
+The metric-depth branch (metric_depth/train.py:149-177) has the same loop around vdn.metric: metric_validate_step is its body,
+DepthMetricMeter its `results` and `nsamples`.
+
+    meter = DepthMetricMeter()
+    for sample in valloader:
+        metric_validate_step(model, sample, min_depth=args.min_depth, max_depth=args.max_depth, meter=meter)
+    dist.reduce(meter.state(), dst=0)        # as the script reduces its ten tensors
+    results = meter.means()"""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -19,6 +28,7 @@ import torch
 
 from . import prep
 from .eval import eval_batch_by_data
+from .metric import KEYS as DEPTH_METRIC_KEYS, eval_depth_batch
 
 
 def prepare_batch(batch, *, input_key="depth_anything_v2", normalize_input=False, device="cuda") -> Dict[str, torch.Tensor]:
@@ -134,6 +144,74 @@ def evaluate_step(model, batch, *, with_rgb=True, meter: Optional[MetricMeter] =
     depth, _ = _predict(model, t, with_rgb)
     rows = eval_batch_by_data(depth, t["gt"], device=device, seq_len=t["gt"].shape[1], domain=domain,
                               dataset_max_depth=dataset_max_depth)
+    if meter is not None:
+        meter.add(rows)
+    return rows
+
+
+class DepthMetricMeter:
+    """`results` and `nsamples` of metric_depth/train.py:149-177, on the device: a float64 [10] of the sums of the nine
+    metrics and the number of items counted. add() takes the [B, 10] rows of vdn.metric.eval_depth_batch (n, then the nine) and
+    counts an item only where n >= 10, the script's `if valid_mask.sum() < 10: continue`, decided on the device by torch.where
+    with no synchronisation; a skipped item's NaN reaches nothing. Rows are added one by one in the order they came.
+    One difference from the script: it accumulates each metric's Python float into a float32 tensor, this meter in float64."""
+
+    MIN_PIXELS = 10
+
+    def __init__(self):
+        self.sums: Optional[torch.Tensor] = None
+
+    def add(self, rows: torch.Tensor):
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[1] != 1 + len(DEPTH_METRIC_KEYS):
+            raise ValueError(f"rows must be [B, {1 + len(DEPTH_METRIC_KEYS)}], got {tuple(getattr(rows, 'shape', ()))}")
+        rows = rows.detach().to(torch.float64)
+        counted = rows[:, :1] >= self.MIN_PIXELS
+        one = torch.ones_like(rows[:, :1])
+        terms = torch.where(counted, torch.cat((rows[:, 1:], one), 1), torch.zeros_like(rows))   # the nine, then 1 per item
+        if self.sums is None:
+            self.sums = torch.zeros_like(terms[0])
+        for b in range(terms.shape[0]):
+            self.sums = self.sums + terms[b]
+
+    def state(self) -> torch.Tensor:
+        """float64 [10] on the device: the sums of d1 .. silog over the counted items, then their number. What a distributed
+        run reduces; load_state() takes the reduced tensor back."""
+        if self.sums is None:
+            raise ValueError("nothing was added")
+        return self.sums
+
+    def load_state(self, sums: torch.Tensor):
+        if not isinstance(sums, torch.Tensor) or tuple(sums.shape) != (1 + len(DEPTH_METRIC_KEYS),):
+            raise ValueError(f"state must be [{1 + len(DEPTH_METRIC_KEYS)}], got {tuple(getattr(sums, 'shape', ()))}")
+        self.sums = sums.detach().to(torch.float64)
+
+    def means(self) -> Dict[str, float]:
+        """{'d1': ..., 'silog': ...}: each sum over the number of counted items (NaN when none was), with the one copy to the
+        host."""
+        if self.sums is None:
+            return {}
+        host = (self.sums[:-1] / self.sums[-1]).cpu().tolist()
+        return dict(zip(DEPTH_METRIC_KEYS, host))
+
+
+@torch.no_grad()
+def metric_validate_step(model, sample, *, min_depth, max_depth, meter: Optional[DepthMetricMeter] = None,
+                         device="cuda") -> torch.Tensor:
+    """One pass of the validation loop's body of metric_depth/train.py:160-177 for sample = {'image' [B, 3, h, w], 'depth'
+    [B, H, W], 'valid_mask' [B, H, W]} and any callable model(image) -> [B, h', w'] -> float64 [B, 10] on the device: per item
+    the kept pixels and the nine metrics of the prediction, resized to (H, W) with align_corners=True, under (valid_mask == 1)
+    & (depth >= min_depth) & (depth <= max_depth) (vdn.metric.eval_depth_batch: the resized prediction and the mask are never
+    stored), also added to `meter`. The script runs one item per pass; any B is taken here. No host synchronisation."""
+    depth, valid = sample["depth"], sample["valid_mask"]
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+        raise ValueError(f"sample['depth'] must be [B, H, W], got {tuple(getattr(depth, 'shape', ()))}")
+    if not isinstance(valid, torch.Tensor) or tuple(valid.shape) != tuple(depth.shape):
+        raise ValueError(f"sample['valid_mask'] must be [B, H, W] = {tuple(depth.shape)}, got {tuple(getattr(valid, 'shape', ()))}")
+    image = sample["image"]
+    if not image.is_cuda:
+        image = image.to(device)
+    pred = model(image.float())
+    rows = eval_depth_batch(pred, depth, valid, min_depth=min_depth, max_depth=max_depth, device=device)
     if meter is not None:
         meter.add(rows)
     return rows

@@ -295,6 +295,20 @@ int vdn_add_vec(const float* x, const float* vec, float alpha, float* y, int row
 int vdn_head_out(int dt, const void* feat, const void* feat_lo, const float* w, float bias, float* depth, int M,
                  int C, int relu, vdn_stream stream);
 
+/* Final activation of a DPT head's last 1x1 convolution (vdn_head_out_act, vdn_depth_tail_act):
+ *   VDN_OUT_NONE     v                          (the signed map in front of the activation)
+ *   VDN_OUT_RELU     max(v, 0), NaN passes      (depth_anything_v2/dpt.py:112)
+ *   VDN_OUT_SIGMOID  out_scale * sigmoid(v)     (metric_depth/depth_anything_v2/dpt.py:112-113 composed with the
+ *                    `* max_depth` of its callers: dpt.py:183, metric_depth/train.py:131,165-166), the sigmoid in fp32 and
+ *                    ONE multiply by out_scale; v -> -inf gives exactly 0, v -> +inf exactly out_scale, NaN passes.
+ * out_scale is read by VDN_OUT_SIGMOID only.                                                                              */
+enum { VDN_OUT_NONE = 0, VDN_OUT_RELU = 1, VDN_OUT_SIGMOID = 2 };
+
+/* vdn_head_out with the final activation `act` (the unfused end of the metric-depth head, metric_depth/depth_anything_v2/
+ * dpt.py:112-113). vdn_head_out(relu) is this entry with act = relu ? VDN_OUT_RELU : VDN_OUT_NONE.                        */
+int vdn_head_out_act(int dt, const void* feat, const void* feat_lo, const float* w, float bias, float* depth, int M,
+                     int C, int act, float out_scale, vdn_stream stream);
+
 /* MaskDownSampler stages of memory_block.py:72-75 (sam2/modeling/memory_encoder.py:36-58):
  * stage 1: sigmoid -> conv3x3 s2 p1 (1->4) -> LayerNorm2d -> GELU -> conv1x1 (4->1)
  * stage 2:            conv7x7 s7    (1->49) -> LayerNorm2d -> GELU -> conv1x1 (49->1)
@@ -762,6 +776,19 @@ int vdn_refine_mix(const float* depth, const float* x, float a0, float a1, float
 int vdn_depth_tail(int dt, const float* x, int B, int IH, int IW, int C, const void* w, const void* w_lo, int ldb,
                    const float* bias2, const float* w1, float b1, float* depth, int OH, int OW, int relu,
                    vdn_stream stream);
+/* The same with the final activation `act` (VDN_OUT_*): VDN_OUT_SIGMOID is the tail of the metric-depth head
+ * (metric_depth/depth_anything_v2/dpt.py:146-147 with output_conv2 of :109-114, times max_depth as dpt.py:183 has it).
+ * vdn_depth_tail(relu) is this entry with act = relu ? VDN_OUT_RELU : VDN_OUT_NONE, and runs the kernel it always ran.   */
+int vdn_depth_tail_act(int dt, const float* x, int B, int IH, int IW, int C, const void* w, const void* w_lo, int ldb,
+                       const float* bias2, const float* w1, float b1, float* depth, int OH, int OW, int act,
+                       float out_scale, vdn_stream stream);
+
+/* Point cloud of a metric depth map (metric_depth/depth_to_pointcloud.py:99-104), one launch: depth f32 [h, w] and
+ * rgb u8 [h, w, 3] -> points f64 [h*w, 3] = (x z, y z, z) with x = (col - w / 2) / fx, y = (row - h / 2) / fy in float64
+ * and z widened from float32, colors f64 [h*w, 3] = rgb / 255.0. Subtractions, divisions and products only, each
+ * correctly rounded and none contracted: the bits numpy gives. points and colors 16-byte aligned; fx, fy non-zero.     */
+int vdn_depth_to_points(const float* depth, const uint8_t* rgb, int h, int w, double fx, double fy, double* points,
+                        double* colors, vdn_stream stream);
 
 /* output_conv1 of a 2x up-sampled map without the up-sampled map (depth_anything_v2/dpt.py:145 on the path_1 of
  * util/blocks.py:144-146): Conv3x3(pad 1) o bilinear(align_corners=True) o Conv1x1 is linear with no activation in between,

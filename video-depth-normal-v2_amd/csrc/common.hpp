@@ -77,6 +77,12 @@ __device__ __forceinline__ float gelu_erf(float x) {  // nn.GELU() default (exac
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
 
+// Final activation of the metric-depth head (metric_depth/depth_anything_v2/dpt.py:113 with the `* max_depth` of its
+// callers): ONE multiply of the fp32 sigmoid 1 / (1 + e^-v) by out_scale. e^-v overflows to +inf for v < -88.7 (then 1 / inf
+// = 0, the result is exactly 0) and vanishes beside 1 for v > 17 (exactly out_scale): no inf / inf anywhere. NaN in, NaN out.
+// The division is the correctly rounded one (no fast-math in this build).
+__device__ __forceinline__ float scaled_sigmoid(float v, float out_scale) { return out_scale * (1.0f / (1.0f + expf(-v))); }
+
 // Exact-form GELU, 4 values at a time, fp32-level accuracy (|error| <= 2.5e-7 on [-8, 8], i.e. the
 // rounding of the result itself; measured against float64 erf in tools/fit_gelu.py, which also produced
 // the coefficients). With t = |x|/sqrt2:  0.5(1+erf(x/sqrt2)) = 1 - 0.5 erfc(t) for x >= 0, 0.5 erfc(t) for

@@ -178,7 +178,7 @@ template <int DT>
 __global__ __launch_bounds__(256) void head_out_kernel(const typename Half<DT>::T* __restrict__ feat,
                                                        const typename Half<DT>::T* __restrict__ feat_lo,
                                                        const float* __restrict__ w, float bias,
-                                                       float* __restrict__ depth, int M, int C, int relu) {
+                                                       float* __restrict__ depth, int M, int C, int act, float out_scale) {
   using V8 = typename Half<DT>::V8;
   __shared__ float sw[64];
   if (threadIdx.x < C) sw[threadIdx.x] = w[threadIdx.x];
@@ -195,7 +195,8 @@ __global__ __launch_bounds__(256) void head_out_kernel(const typename Half<DT>::
         for (int e = 0; e < 8; ++e) acc += sw[c + e] * (float)vl[e];
       }
     }
-    depth[m] = relu ? fmaxf(acc, 0.f) : acc;
+    // `act` is the same for the whole grid; the sum in front of it is the same instructions for all three
+    depth[m] = act == VDN_OUT_SIGMOID ? scaled_sigmoid(acc, out_scale) : act == VDN_OUT_RELU ? fmaxf(acc, 0.f) : acc;
   }
 }
 
@@ -536,19 +537,25 @@ extern "C" int vdn_preprocess(const uint8_t* frames, int n, int h, int w, int sw
   return VDN_OK;
 }
 
-extern "C" int vdn_head_out(int dt, const void* feat, const void* feat_lo, const float* w, float bias, float* depth,
-                            int M, int C, int relu, vdn_stream stream) {
+extern "C" int vdn_head_out_act(int dt, const void* feat, const void* feat_lo, const float* w, float bias, float* depth,
+                                int M, int C, int act, float out_scale, vdn_stream stream) {
   if (!feat || !w || !depth || M <= 0 || C <= 0 || C > 64) return VDN_EINVAL;
+  if (act != VDN_OUT_NONE && act != VDN_OUT_RELU && act != VDN_OUT_SIGMOID) return VDN_EINVAL;
   if ((C & 7) || ((uintptr_t)feat & 15)) return VDN_EALIGN;
   const unsigned g = grid_for((size_t)M, 8192);
   hipStream_t s = (hipStream_t)stream;
   return with_half(dt, [&](auto t) -> int {
     using T = typename Half<decltype(t)::value>::T;
     hipLaunchKernelGGL(head_out_kernel<decltype(t)::value>, dim3(g), dim3(256), 0, s, (const T*)feat, (const T*)feat_lo, w, bias, depth,
-                       M, C, relu);
+                       M, C, act, out_scale);
     VDN_CHECK_LAUNCH();
     return VDN_OK;
   });
+}
+
+extern "C" int vdn_head_out(int dt, const void* feat, const void* feat_lo, const float* w, float bias, float* depth,
+                            int M, int C, int relu, vdn_stream stream) {
+  return vdn_head_out_act(dt, feat, feat_lo, w, bias, depth, M, C, relu ? VDN_OUT_RELU : VDN_OUT_NONE, 1.f, stream);
 }
 
 extern "C" int vdn_mask_down1(const float* depth, float* out, int B, int H, int W, int OH, int OW, const float* w,

@@ -2,6 +2,8 @@
 //   out = F.interpolate(out1, (14 ph, 14 pw), bilinear, align_corners=True)      [B, C, OH, OW]   (C = features / 2)
 //   out = ReLU(Conv3x3(C -> 32, pad 1)(out))
 //   depth = [ReLU](Conv1x1(32 -> 1)(out))                                          [B, OH, OW] f32
+// or, for the metric-depth head (metric_depth/depth_anything_v2/dpt.py:109-114 and the `* max_depth` of its callers),
+//   depth = out_scale * Sigmoid(Conv1x1(32 -> 1)(out))
 // in ONE kernel: the x1.75 up-sampled map (1.1 GB of split planes at batch 8, ViT-L) and the 32-channel map never
 // reach HBM. Round 1 ran this as upsample_kernel -> implicit-GEMM conv (N = 32: 9.9 GB moved L2 -> LDS per launch,
 // feed-bound) -> head_out_kernel = 1.6 ms per batch-8 step.
@@ -20,7 +22,10 @@
 //          v_mfma_f32_16x16x32 (weights as the A operand: a lane then holds 4 output channels of ONE pixel), three
 //          products per term (hi*lo + lo*hi + hi*hi). The pass's 9 weight fragments per plane live in registers.
 // Epilogue: bias + ReLU + each wave's half of the 32 -> 1 dot product in registers, two cross-lane adds, the two
-//          halves summed through LDS, one coalesced store per tile row.
+//          halves summed through LDS, the final activation, one coalesced store per tile row. The sigmoid is a template
+//          instantiation of its own (SIG): the no-activation / ReLU kernel is the code it was before the sigmoid existed.
+//          One expf and one division per OUTPUT pixel, after 73.7 kFLOP of MFMA for that pixel at C = 128: the quarter
+//          rate of a transcendental does not show, so the exact expf is used rather than an exp2 of a rounded product.
 // Roofline: MFMA (19.8 GF per 518 x 518 frame at C = 128, x3 executed); HBM traffic = out1 once (+ halo) + depth.
 #include "common.hpp"
 #include "resample.hpp"
@@ -38,12 +43,12 @@ constexpr int SLOADS = (SP * SP * 4 * 2 + 255) / 256;                       // 1
 // rounded-product weight of upsample_kernel (resample.hpp; tests/test_gpu_resample.py holds it in place).
 constexpr AcWeight FUSED = AcWeight::fused;
 
-template <int DT>
+template <int DT, bool SIG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void depth_tail_kernel(const float* __restrict__ x, int B, int IH, int IW,
                                                          int C, const typename Half<DT>::T* __restrict__ w,
                                                          const typename Half<DT>::T* __restrict__ wl, int ldb,
                                                          const float* __restrict__ b2, const float* __restrict__ w1, float b1,
-                                                         float* __restrict__ depth, int OH, int OW, int relu) {
+                                                         float* __restrict__ depth, int OH, int OW, int relu, float out_scale) {
   using H = Half<DT>;
   using T = typename H::T;
   using V8 = typename H::V8;
@@ -223,7 +228,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   {
     const int py = tid >> 4, px = tid & 15;  // 256 threads = 16 x 16 pixels
     float v = part[py * TW + px] + part[TH * TW + py * TW + px] + b1;
-    if (relu) v = (v < 0.f) ? 0.f : v;
+    if (SIG) v = scaled_sigmoid(v, out_scale);
+    else if (relu) v = (v < 0.f) ? 0.f : v;
     const int oy = ty0 + py, ox = tx0 + px;
     if (oy < OH && ox < OW) depth[((size_t)b * OH + oy) * OW + ox] = v;
   }
@@ -231,10 +237,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 }  // namespace
 
-extern "C" int vdn_depth_tail(int dt, const float* x, int B, int IH, int IW, int C, const void* w,
-                              const void* w_lo, int ldb, const float* bias2, const float* w1, float b1, float* depth, int OH,
-                              int OW, int relu, vdn_stream stream) {
+extern "C" int vdn_depth_tail_act(int dt, const float* x, int B, int IH, int IW, int C, const void* w,
+                                  const void* w_lo, int ldb, const float* bias2, const float* w1, float b1, float* depth, int OH,
+                                  int OW, int act, float out_scale, vdn_stream stream) {
   if (!x || !w || !w_lo || !bias2 || !w1 || !depth || B <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return VDN_EINVAL;
+  if (act != VDN_OUT_NONE && act != VDN_OUT_RELU && act != VDN_OUT_SIGMOID) return VDN_EINVAL;
   if (C <= 0 || (C % CB) || ldb < 9 * C || (ldb & 7)) return VDN_EALIGN;
   // the 13 x 13 source patch must cover the 18-pixel halo of a tile: floor(17 s) + 3 <= 13 for both scales
   if ((int)(17.f * ac_scale(IH, OH)) + 3 > SP || (int)(17.f * ac_scale(IW, OW)) + 3 > SP) return VDN_EUNSUPPORTED;
@@ -242,10 +249,23 @@ extern "C" int vdn_depth_tail(int dt, const float* x, int B, int IH, int IW, int
   const int tiles = B * ((OH + TH - 1) / TH) * ((OW + TW - 1) / TW);
   hipStream_t s = (hipStream_t)stream;
   return with_half(dt, [&](auto t) -> int {
-    using T = typename Half<decltype(t)::value>::T;
-    hipLaunchKernelGGL(depth_tail_kernel<decltype(t)::value>, dim3(tiles), dim3(256), 2 * PLANE + 2 * SPLANE, s, x, B, IH, IW, C,
-                       (const T*)w, (const T*)w_lo, ldb, bias2, w1, b1, depth, OH, OW, relu);
+    constexpr int DT = decltype(t)::value;
+    using T = typename Half<DT>::T;
+    const int relu = act == VDN_OUT_RELU;
+    if (act == VDN_OUT_SIGMOID)
+      hipLaunchKernelGGL((depth_tail_kernel<DT, true>), dim3(tiles), dim3(256), 2 * PLANE + 2 * SPLANE, s, x, B, IH, IW, C, (const T*)w,
+                         (const T*)w_lo, ldb, bias2, w1, b1, depth, OH, OW, relu, out_scale);
+    else
+      hipLaunchKernelGGL((depth_tail_kernel<DT, false>), dim3(tiles), dim3(256), 2 * PLANE + 2 * SPLANE, s, x, B, IH, IW, C, (const T*)w,
+                         (const T*)w_lo, ldb, bias2, w1, b1, depth, OH, OW, relu, out_scale);
     VDN_CHECK_LAUNCH();
     return VDN_OK;
   });
+}
+
+extern "C" int vdn_depth_tail(int dt, const float* x, int B, int IH, int IW, int C, const void* w,
+                              const void* w_lo, int ldb, const float* bias2, const float* w1, float b1, float* depth, int OH,
+                              int OW, int relu, vdn_stream stream) {
+  return vdn_depth_tail_act(dt, x, B, IH, IW, C, w, w_lo, ldb, bias2, w1, b1, depth, OH, OW, relu ? VDN_OUT_RELU : VDN_OUT_NONE, 1.f,
+                            stream);
 }

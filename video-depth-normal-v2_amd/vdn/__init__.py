@@ -45,6 +45,12 @@ def __getattr__(name):
     if name == "metric":  # SiLogLoss and eval_depth's nine metrics of the metric-depth branch on the device (vdn/metric.py)
         import importlib
         return importlib.import_module(".metric", __name__)
+    if name == "metric_depth":  # the metric-depth model, DepthAnythingV2(max_depth), under the reference's module path (vdn/metric_depth/)
+        import importlib
+        return importlib.import_module(".metric_depth", __name__)
+    if name == "points":  # the point cloud of a metric depth map on the device (vdn/points.py)
+        import importlib
+        return importlib.import_module(".points", __name__)
     if name == "steps":  # the bodies of the scripts' validate and evaluate loops, without host synchronisation (vdn/steps.py)
         import importlib
         return importlib.import_module(".steps", __name__)

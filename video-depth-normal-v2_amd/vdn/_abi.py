@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("VDN_LIB") or os.path.join(PKG, "lib", "libvdn_hip.so"
 
 F16, BF16, F32, NONE = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SILU = 0, 1, 2, 3
+OUT_NONE, OUT_RELU, OUT_SIGMOID = 0, 1, 2   # final activation of a DPT head (include/vdn.h VDN_OUT_*)
 A_PLAIN, A_CONV3X3 = 0, 1
 ST_PLAIN, ST_HEADS, ST_CONVT, ST_GEGLU = 0, 1, 2, 3
 EVAL_DEPTH, EVAL_DISP = 0, 1
@@ -90,6 +91,10 @@ EXPORTS = {
     "vdn_head_out": (C.c_int, [C.c_int, vp, vp, fp, C.c_float, fp, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_depth_tail": (C.c_int, [C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, fp, fp, C.c_float, fp,
                                  C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_head_out_act": (C.c_int, [C.c_int, vp, vp, fp, C.c_float, fp, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
+    "vdn_depth_tail_act": (C.c_int, [C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, fp, fp, C.c_float, fp,
+                                     C.c_int, C.c_int, C.c_int, C.c_float, vp]),
+    "vdn_depth_to_points": (C.c_int, [fp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]),
     "vdn_oc1_combine": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_pack_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vdn_pack_ldb": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

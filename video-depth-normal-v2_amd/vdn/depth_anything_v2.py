@@ -89,7 +89,48 @@ class _EngineOwner(nn.Module):
         return rt.preprocess_u8(frames_u8.contiguous(), nh, nw, _MEAN, _STD, swap_rb)
 
 
-class DepthAnythingV2(_EngineOwner):
+class _SingleImage(_EngineOwner):
+    """The single-image driver of an engine owner whose forward(image f32 [1,3,H,W]) returns f32 [1,H,W] and whose _engines()
+    holds the runtime under "rt": upload + pre-processing, the forward, the resize back to the frame and the range check,
+    written once for vdn.depth_anything_v2 and vdn.metric_depth (depth_anything_v2.py:57-92; the commented class of
+    metric_depth/depth_anything_v2/dpt.py:187-222 has the same statements)."""
+
+    def _upload(self, raw_image: np.ndarray, input_size: int):
+        rt = self._engines()["rt"]
+        h, w = raw_image.shape[:2]
+        img = torch.from_numpy(np.ascontiguousarray(raw_image)).to(rt.device)[None]   # BGR u8: the kernel swaps the channels
+        return self.preprocess(rt, img, input_size, swap_rb=True), (h, w), img
+
+    def image2tensor(self, raw_image: np.ndarray, input_size: int = 518):
+        """depth_anything_v2.py:67-92."""
+        image, hw, _ = self._upload(raw_image, input_size)
+        return image, hw
+
+    def _infer_image_device(self, raw_image: np.ndarray, input_size: int, what: str):
+        """infer_image up to its device-to-host copy: (depth f32 [1,h,w], the uploaded BGR frame u8 [1,h,w,3]), both on the
+        device. The one statement of the forward, the resize and the range check that infer_image and infer_image_vis share."""
+        image, (h, w), img = self._upload(raw_image, input_size)
+        depth = self.forward(image)
+        rt = self._engines()["rt"]
+        if tuple(depth.shape[-2:]) != (h, w):
+            out = torch.empty((1, h, w), dtype=torch.float32, device=rt.device)
+            rt.upsample_f32(depth.contiguous(), out, 1, depth.shape[-2], depth.shape[-1], h, w)
+            depth = out
+        from .util import check_finite
+        check_finite(depth, what)
+        return depth, img
+
+    def _infer_image_vis(self, raw_image, input_size, pred_only, grayscale, palette) -> np.ndarray:
+        from . import vis
+        vis._check(palette, "bgr", "frame", grayscale, 3)
+        depth, img = self._infer_image_device(raw_image, input_size, "infer_image_vis")
+        with torch.cuda.device(depth.device):
+            out = vis._colorize(self._engines()["rt"], depth.contiguous(), palette, "bgr", "frame", grayscale, 3,
+                                None if pred_only else img, 50, None)
+        return out[0].cpu().numpy()
+
+
+class DepthAnythingV2(_SingleImage):
     def __init__(self, encoder="vitl", features=256, out_channels=[256, 512, 1024, 1024], use_bn=False,
                  use_clstoken=False, max_memory_length=6):
         super().__init__()
@@ -190,20 +231,6 @@ class DepthAnythingV2(_EngineOwner):
         """BGR u8 [h,w,3] -> f32 [h,w] (depth_anything_v2.py:57-65)."""
         return self._infer_image_device(raw_image, input_size, "infer_image")[0][0].cpu().numpy()
 
-    def _infer_image_device(self, raw_image: np.ndarray, input_size: int, what: str):
-        """infer_image up to its device-to-host copy: (depth f32 [1,h,w], the uploaded BGR frame u8 [1,h,w,3]), both on the
-        device. The one statement of the forward, the resize and the range check that infer_image and infer_image_vis share."""
-        image, (h, w), img = self._upload(raw_image, input_size)
-        depth = self.forward(image)
-        rt = self._engines()["rt"]
-        if tuple(depth.shape[-2:]) != (h, w):
-            out = torch.empty((1, h, w), dtype=torch.float32, device=rt.device)
-            rt.upsample_f32(depth.contiguous(), out, 1, depth.shape[-2], depth.shape[-1], h, w)
-            depth = out
-        from .util import check_finite
-        check_finite(depth, what)
-        return depth, img
-
     @torch.no_grad()
     def infer_image_vis(self, raw_image: np.ndarray, input_size: int = 518, pred_only: bool = False, grayscale: bool = False,
                         palette: str = "Spectral_r") -> np.ndarray:
@@ -211,21 +238,4 @@ class DepthAnythingV2(_EngineOwner):
         run.py:59-73 / run_video.py:75-89 build on the host from infer_image's result and hand to cv2.imwrite /
         VideoWriter.write, byte for byte, made on the device (vdn.vis) from the same forward and the same resize; only the
         uint8 picture is copied back. palette 'Spectral' gives metric_depth/run.py's. Mutates the memory bank like infer_image."""
-        from . import vis
-        vis._check(palette, "bgr", "frame", grayscale, 3)
-        depth, img = self._infer_image_device(raw_image, input_size, "infer_image_vis")
-        with torch.cuda.device(depth.device):
-            out = vis._colorize(self._engines()["rt"], depth.contiguous(), palette, "bgr", "frame", grayscale, 3,
-                                None if pred_only else img, 50, None)
-        return out[0].cpu().numpy()
-
-    def _upload(self, raw_image: np.ndarray, input_size: int):
-        rt = self._engines()["rt"]
-        h, w = raw_image.shape[:2]
-        img = torch.from_numpy(np.ascontiguousarray(raw_image)).to(rt.device)[None]   # BGR u8: the kernel swaps the channels
-        return self.preprocess(rt, img, input_size, swap_rb=True), (h, w), img
-
-    def image2tensor(self, raw_image: np.ndarray, input_size: int = 518):
-        """depth_anything_v2.py:67-92."""
-        image, hw, _ = self._upload(raw_image, input_size)
-        return image, hw
+        return self._infer_image_vis(raw_image, input_size, pred_only, grayscale, palette)

@@ -425,9 +425,12 @@ class DPTEngine:
         return p
 
     def run(self, taps: List[torch.Tensor], Bf: int, ph: int, pw: int, T: Optional[int] = None, relu: bool = True,
-            exch=None, stream=None, out: Optional[torch.Tensor] = None):
+            exch=None, stream=None, out: Optional[torch.Tensor] = None, act: Optional[int] = None, out_scale: float = 1.0):
         """`out` (f32 [Bf, 14 ph, 14 pw], contiguous): the caller's result tensor, written by the last kernel directly;
-        without it the depth lands in this engine's arena (valid until the next run)."""
+        without it the depth lands in this engine's arena (valid until the next run).
+        `act` (abi.OUT_*; default: relu -> OUT_RELU / OUT_NONE) is the head's final activation and `out_scale` the factor of
+        OUT_SIGMOID (the metric head, metric_depth/depth_anything_v2/dpt.py:112-113,183); both are launch arguments of the
+        last kernel, whichever of the three endings below runs."""
         rt, C, F, oc = self.rt, self.C, self.F, self.oc
         P = ph * pw
         pr = []
@@ -493,20 +496,20 @@ class DPTEngine:
             rt.gemm(u, self.oc1_low[0], M1, 9 * (F // 2), F, bias=self.oc1_low[1], out=z)
             o1 = rt.fbuf("out1_f32", (Bf * s0[0] * s0[1], F // 2))
             rt.oc1_combine(z, self.oc1[1], o1, Bf, s1[0], s1[1], s0[0], s0[1], F // 2)
-            rt.depth_tail(o1, self.oc2_taps, self.oc2[1], self.w_last, self.b_last, depth, Bf, s0[0], s0[1], F // 2, H, W, relu)
+            rt.depth_tail(o1, self.oc2_taps, self.oc2[1], self.w_last, self.b_last, depth, Bf, s0[0], s0[1], F // 2, H, W, relu, act, out_scale)
             return depth
         p1 = self._fusion(1, Bf, s1, s0, p2, r1)
         if fused:
             # resize -> conv3x3 + ReLU -> conv1x1 (+ ReLU) without leaving the chip (the scale is 8/14 for every DPT head);
             # output_conv1 then writes ONE fp32 plane, which is what the fused kernel interpolates from
             o1 = self._conv3(p1, self.oc1[0], Bf, s0[0], s0[1], F, F // 2, "out1_f32", bias=self.oc1[1], f32_out=True)
-            rt.depth_tail(o1, self.oc2_taps, self.oc2[1], self.w_last, self.b_last, depth, Bf, s0[0], s0[1], F // 2, H, W, relu)
+            rt.depth_tail(o1, self.oc2_taps, self.oc2[1], self.w_last, self.b_last, depth, Bf, s0[0], s0[1], F // 2, H, W, relu, act, out_scale)
             return depth
         o1 = self._conv3(p1, self.oc1[0], Bf, s0[0], s0[1], F, F // 2, "out1", bias=self.oc1[1])
         up = rt.hbuf("out_up", (Bf * H * W, F // 2))
         rt.upsample(o1, up, Bf, s0[0], s0[1], H, W, F // 2)
         o2 = self._conv3(up, self.oc2[0], Bf, H, W, F // 2, 32, "out2", bias=self.oc2[1], act=RELU)
-        rt.head_out(o2, self.w_last, self.b_last, depth, Bf * H * W, 32, relu)
+        rt.head_out(o2, self.w_last, self.b_last, depth, Bf * H * W, 32, relu, act, out_scale)
         return depth
 
 

@@ -710,12 +710,23 @@ class Runtime:
     def add_vec(self, x, vec, alpha: float, y, rows: int, Cn: int):
         self._launch(abi.lib.vdn_add_vec, x.data_ptr(), vec.data_ptr(), alpha, y.data_ptr(), rows, Cn)
 
+    @staticmethod
+    def _out_act(relu: bool, act: Optional[int]) -> int:
+        """Final activation of a DPT head (include/vdn.h VDN_OUT_*): `act` where given, else the older relu flag."""
+        if act is None:
+            return abi.OUT_RELU if relu else abi.OUT_NONE
+        if act not in (abi.OUT_NONE, abi.OUT_RELU, abi.OUT_SIGMOID):
+            raise ValueError(f"act must be one of OUT_NONE, OUT_RELU, OUT_SIGMOID (0, 1, 2), got {act!r}")
+        return act
+
     def depth_tail(self, x: torch.Tensor, w: HL, bias2, w1, b1: float, depth, B: int, IH: int, IW: int, Cn: int, OH: int,
-                   OW: int, relu: bool):
-        """resize(align_corners) -> conv3x3 + ReLU -> conv1x1 [+ ReLU] in one launch; x f32 NHWC (split-plane modes only)."""
+                   OW: int, relu: bool = False, act: Optional[int] = None, out_scale: float = 1.0):
+        """resize(align_corners) -> conv3x3 + ReLU -> conv1x1 -> final activation in one launch; x f32 NHWC (split-plane modes
+        only). act (abi.OUT_*) overrides relu; OUT_SIGMOID writes out_scale * sigmoid (include/vdn.h vdn_depth_tail_act)."""
         assert x.dtype == torch.float32 and x.is_contiguous() and w.lo is not None and w.hi.shape[0] == 32
-        self._launch(abi.lib.vdn_depth_tail, self.dt, x.data_ptr(), B, IH, IW, Cn, w.hi.data_ptr(), w.lo.data_ptr(),
-                     w.hi.shape[1], bias2.data_ptr(), w1.data_ptr(), b1, depth.data_ptr(), OH, OW, int(relu))
+        self._launch(abi.lib.vdn_depth_tail_act, self.dt, x.data_ptr(), B, IH, IW, Cn, w.hi.data_ptr(), w.lo.data_ptr(),
+                     w.hi.shape[1], bias2.data_ptr(), w1.data_ptr(), b1, depth.data_ptr(), OH, OW, self._out_act(relu, act),
+                     float(out_scale))
 
     @staticmethod
     def lowres_oc1_rows(M: int) -> bool:
@@ -729,10 +740,23 @@ class Runtime:
         assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * OH * OW * Cn, (out.shape, out.dtype)
         self._launch(abi.lib.vdn_oc1_combine, z.data_ptr(), bias.data_ptr(), out.data_ptr(), B, IH, IW, OH, OW, Cn)
 
-    def head_out(self, feat, w, bias: float, depth, M: int, Cn: int, relu: bool):
+    def head_out(self, feat, w, bias: float, depth, M: int, Cn: int, relu: bool = False, act: Optional[int] = None,
+                 out_scale: float = 1.0):
+        """The closing 1x1 convolution and its final activation, as depth_tail takes it (include/vdn.h vdn_head_out_act)."""
         feat, fl = _hl(feat)
-        self._launch(abi.lib.vdn_head_out, self.dt, feat.data_ptr(), fl, w.data_ptr(), bias, depth.data_ptr(), M, Cn,
-                     int(relu))
+        self._launch(abi.lib.vdn_head_out_act, self.dt, feat.data_ptr(), fl, w.data_ptr(), bias, depth.data_ptr(), M, Cn,
+                     self._out_act(relu, act), float(out_scale))
+
+    def depth_to_points(self, depth: torch.Tensor, rgb: torch.Tensor, fx: float, fy: float, points: torch.Tensor,
+                        colors: torch.Tensor):
+        """points, colors f64 [h*w, 3] <- the point cloud of depth f32 [h, w] and rgb u8 [h, w, 3] (vdn_depth_to_points)."""
+        h, w = depth.shape
+        assert depth.dtype == torch.float32 and depth.is_contiguous() and rgb.dtype == torch.uint8 and rgb.is_contiguous()
+        assert tuple(rgb.shape) == (h, w, 3), (rgb.shape, depth.shape)
+        for t in (points, colors):
+            assert t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (h * w, 3), (t.shape, t.dtype)
+        self._launch(abi.lib.vdn_depth_to_points, depth.data_ptr(), rgb.data_ptr(), h, w, float(fx), float(fy), points.data_ptr(),
+                     colors.data_ptr())
 
     def mask_down1(self, depth, out, B, H, W, OH, OW, w):
         self._launch(abi.lib.vdn_mask_down1, depth.data_ptr(), out.data_ptr(), B, H, W, OH, OW, w.data_ptr())

@@ -5,11 +5,12 @@
 //   vdn_resize_bilinear_hp  half-pixel bilinear resize of the prediction to the ground truth's size
 // Everything the reference computes in float64 is fp64 here, with its roundings (separate multiply and add: contraction
 // is off for this file); what it computes in float32 (the valid test, the TGM gradient of gt and its threshold, the three
-// delta accuracies) is float32 here. Sums have a fixed order: a lane's stride through its block's share, the wave and the
-// block as reduce.hpp states them, a frame's EVAL_BPF blocks in index order, the frames in index order. No atomics:
+// delta accuracies) is float32 here. Sums have the fixed order of frame_sums.hpp, with EVAL_BPF blocks per frame. No atomics:
 // two runs give the same bits. Loads are one float per lane (coalesced), so any 4-byte-aligned pointer is accepted.
+// The two kernels of vdn_eval_metrics keep their interleaved row (MET_SLOTS) and spell that header's block row and block fold
+// out; keep them equal to block_row and fold_blocks (profiles/criteria_refactor.md says why they are not calls).
 #include "common.hpp"
-#include "reduce.hpp"
+#include "frame_sums.hpp"
 #include "resample.hpp"
 #include <math.h>
 
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void eval_fit_partial_kernel(const float* __re
   const size_t f = blockIdx.x / EVAL_BPF, b = blockIdx.x % EVAL_BPF, base = f * hw;
   FitSums a = {{0, 0, 0, 0}, INFINITY, -INFINITY};
   int cnt = 0;
-  for (size_t i = b * 256 + threadIdx.x; i < hw; i += (size_t)EVAL_BPF * 256) {
+  for (size_t i = sweep_first<1>((int)b); i < hw; i += sweep_stride<EVAL_BPF, 1>()) {
     const float g = gt[base + i];
     if (!is_valid(g, mask, base + i, r)) continue;
     const double p = clip_low((double)pred[base + i], r.lo);
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256) void eval_fit_solve_kernel(void* __restrict__ 
   const Ws ws(workspace, T);
   for (int f = threadIdx.x; f < T; f += 256) {
     int64_t n = 0;
-    for (int b = 0; b < EVAL_BPF; ++b) n += ((const int64_t*)(ws.fit + ((size_t)f * EVAL_BPF + b) * FIT_SLOTS))[4];
+    for (const size_t o : frame_blocks<EVAL_BPF>(f)) n += ((const int64_t*)(ws.fit + o * FIT_SLOTS))[4];
     ws.nvalid[f] = n;
   }
   FitSums a = {{0, 0, 0, 0}, INFINITY, -INFINITY};
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(256) void eval_metrics_partial_kernel(const float* 
   const size_t nb_end = over_time ? (nf >= 0 ? hw : 0) : (hw > row_stride ? hw - row_stride : 0);
   Tuple<double, 4> s = {{0, 0, 0, 0}};  // |d|, |d|/g, d*d, TGM
   Tuple<int, 5> c = {{0, 0, 0, 0, 0}};  // n, delta1..3, TGM count
-  for (size_t i = b * 256 + threadIdx.x; i < hw; i += (size_t)EVAL_BPF * 256) {
+  for (size_t i = sweep_first<1>((int)b); i < hw; i += sweep_stride<EVAL_BPF, 1>()) {
     const float g32 = gt[base + i];
     if (!is_valid(g32, mask, base + i, r)) continue;  // the TGM mask also needs the first pixel of the pair valid
     const double g = (double)g32;
@@ -301,7 +302,7 @@ extern "C" int vdn_eval_fit(const float* pred, const float* gt, const uint8_t* m
   if (!pred || !gt || !workspace || !coef || frames <= 0 || hw == 0 || !make_range(dmin, dmax, r)) return VDN_EINVAL;
   if (domain != VDN_EVAL_DEPTH && domain != VDN_EVAL_DISP) return VDN_EINVAL;
   if (frames > INT32_MAX / EVAL_BPF) return VDN_EINVAL;
-  if (((uintptr_t)pred & 3) || ((uintptr_t)gt & 3) || ((uintptr_t)workspace & 7) || ((uintptr_t)coef & 7)) return VDN_EALIGN;
+  if (misaligned(4, pred, gt) || misaligned(8, workspace, coef)) return VDN_EALIGN;
   hipStream_t s = (hipStream_t)stream;
   const Ws ws(workspace, frames);
   hipLaunchKernelGGL(eval_fit_partial_kernel, dim3((unsigned)frames * EVAL_BPF), dim3(256), 0, s, pred, gt, mask, hw, r,
@@ -320,8 +321,7 @@ extern "C" int vdn_eval_metrics(const float* pred, const float* gt, const uint8_
   if (domain != VDN_EVAL_DEPTH && domain != VDN_EVAL_DISP) return VDN_EINVAL;
   if (tgm != VDN_EVAL_TGM_ROWS && tgm != VDN_EVAL_TGM_FRAMES) return VDN_EINVAL;
   if (frames > INT32_MAX / EVAL_BPF) return VDN_EINVAL;
-  if (((uintptr_t)pred & 3) || ((uintptr_t)gt & 3) || ((uintptr_t)workspace & 7) || ((uintptr_t)coef & 7) || ((uintptr_t)out & 7))
-    return VDN_EALIGN;
+  if (misaligned(4, pred, gt) || misaligned(8, workspace, coef, out)) return VDN_EALIGN;
   hipStream_t s = (hipStream_t)stream;
   const size_t hw = (size_t)H * W;
   hipLaunchKernelGGL(eval_metrics_partial_kernel, dim3((unsigned)frames * EVAL_BPF), dim3(256), 0, s, pred, gt, mask, frames, hw,
@@ -333,7 +333,7 @@ extern "C" int vdn_eval_metrics(const float* pred, const float* gt, const uint8_
 
 extern "C" int vdn_resize_bilinear_hp(const float* x, float* y, int frames, int IH, int IW, int OH, int OW, vdn_stream stream) {
   if (!x || !y || frames <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return VDN_EINVAL;
-  if (((uintptr_t)x & 3) || ((uintptr_t)y & 3)) return VDN_EALIGN;
+  if (misaligned(4, x, y)) return VDN_EALIGN;
   const size_t total = (size_t)frames * OH * OW;
   hipLaunchKernelGGL(resize_bilinear_hp_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, (hipStream_t)stream, x, y, total,
                      IH, IW, OH, OW);

@@ -10,15 +10,14 @@
 // The aligned prediction a = fl32(fl32(scale * p) + shift) is never stored: every pass recomputes it bit for bit, so
 // thresholds, medians and differences are taken on the float32 numbers the reference holds. Everything else is fp64
 // computed from the float32 samples with separate multiply and add roundings (contraction is off for this file). A dropped
-// pixel is skipped by a branch: NaN or inf under it reaches nothing. Sums have a fixed order: a lane's stride through its
-// block's share, the wave and the block as reduce.hpp states them, a frame's DL_BPF blocks in index order, the frames in
-// index order. The only atomics are the integer ones of the select's histograms: two runs give the same bits.
+// pixel is skipped by a branch: NaN or inf under it reaches nothing. Sums have the fixed order of frame_sums.hpp, with DL_BPF
+// blocks per frame. The only atomics are the integer ones of the select's histograms: two runs give the same bits.
 // Any 4-byte-aligned pointer is accepted; where H * W is a multiple of 4, prediction and target are 16-byte aligned and the
 // mask 4-byte aligned, a lane reads four consecutive pixels with one load per plane, one pixel otherwise. Neighbours
 // (x + 2^k, y + 2^k) that belong to other lanes are read through the cache; the right-hand neighbour of the finest grid
 // comes from the lane's own quad, and the next frame's pixels are read like the frame's own.
 #include "common.hpp"
-#include "reduce.hpp"
+#include "frame_sums.hpp"
 #include "select.hpp"
 #include <math.h>
 
@@ -32,10 +31,10 @@ constexpr int NACC = 3 + DL_MAX_SCALES;
 // d1 hits, temporal count, M_0 .. M_3}
 enum { A_DATA = 0, A_ABSREL = 1, A_TEMP = 2, A_G = 3 };
 
-// workspace, in 8-byte slots
+// workspace, in 8-byte slots; a pass's rows (frame_sums.hpp) are a sums array and a counts array
 struct Ws {
   double* fit_b;     // [F][DL_BPF][4] block sums p^2, p, p t, t
-  int64_t* cnt_b;    // [F][DL_BPF]
+  int64_t* cnt_b;    // [F][DL_BPF] their counts: kept pixels
   float* mm_b;       // [F][DL_BPF][2] block min, max of the kept target
   double* fit_f;     // [F][4]
   int64_t* cnt_f;    // [F]
@@ -82,10 +81,11 @@ __global__ __launch_bounds__(256) void fit_partial_kernel(const float* __restric
   const float* tf = target + (size_t)f * hw;
   const uint8_t* mf = mask + (size_t)f * hw;
   Tuple<double, 4> s = {{0.0, 0.0, 0.0, 0.0}};
-  int cnt = 0;
+  Tuple<int, 1> cnt = {{0}};
   float mn = INFINITY, mx = -INFINITY;
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
-    const Px<PPL> q(pf, tf, mf, (int)q0);
+  for (int64_t q0 = sweep_first<PPL>(b); q0 < hw; q0 += sweep_stride<DL_BPF, PPL>()) {
+    const int p0 = (int)q0;
+    const Px<PPL> q(pf, tf, mf, p0);
 #pragma unroll
     for (int j = 0; j < PPL; ++j)
       if (q.k[j]) {
@@ -94,30 +94,22 @@ __global__ __launch_bounds__(256) void fit_partial_kernel(const float* __restric
         s.v[1] += p;
         s.v[2] += p * t;
         s.v[3] += t;
-        cnt += 1;
+        cnt.v[0] += 1;
         mn = MinOp{}(mn, q.t[j]);
         mx = MaxOp{}(mx, q.t[j]);
       }
   }
-  __shared__ WaveSlots<Tuple<double, 4>> rs;
-  __shared__ WaveSlots<int> rc;
   __shared__ WaveSlots<float> rmn, rmx;
-  rs.put(s, SumOp{});
-  rc.put(cnt, SumOp{});
   rmn.put(mn, MinOp{});
   rmx.put(mx, MaxOp{});
-  __syncthreads();
+  block_row<4, 1>(s, cnt, ws.fit_b, ws.cnt_b);
   if (threadIdx.x == 0) {
-    const Tuple<double, 4> r = rs.get(SumOp{});
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ws.fit_b[(size_t)blockIdx.x * 4 + i] = r.v[i];
-    ws.cnt_b[blockIdx.x] = (int64_t)rc.get(SumOp{});
     ws.mm_b[(size_t)blockIdx.x * 2] = rmn.get(MinOp{});
     ws.mm_b[(size_t)blockIdx.x * 2 + 1] = rmx.get(MaxOp{});
   }
 }
 
-// One block: every frame's blocks in index order, then every item's frames in index order, then the 2 x 2 solve.
+// One block: the fold of frame_sums.hpp, a lane per frame and then a lane per item, then the 2 x 2 solve.
 __global__ __launch_bounds__(256) void fit_solve_kernel(void* __restrict__ workspace, int B, int T, int64_t* __restrict__ frame_counts,
                                                         float* __restrict__ scale_shift) {
   const Ws ws(workspace, B, T);
@@ -126,30 +118,21 @@ __global__ __launch_bounds__(256) void fit_solve_kernel(void* __restrict__ works
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     int64_t n = 0;
     float mn = INFINITY, mx = -INFINITY;
-    for (int b = 0; b < DL_BPF; ++b) {
-      const size_t o = (size_t)f * DL_BPF + b;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) s[i] += ws.fit_b[o * 4 + i];
-      n += ws.cnt_b[o];
+    for (const size_t o : frame_blocks<DL_BPF>(f)) {
+      add_row<4, 1>(ws.fit_b, ws.cnt_b, o, s, &n);
       mn = MinOp{}(mn, ws.mm_b[o * 2]);
       mx = MaxOp{}(mx, ws.mm_b[o * 2 + 1]);
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ws.fit_f[(size_t)f * 4 + i] = s[i];
-    ws.cnt_f[f] = n;
+    store_row<4, 1>(ws.fit_f, ws.cnt_f, (size_t)f, s, &n);
     ws.th[f] = (mx - mn) * 0.05f;  // -inf for a frame without a kept pixel: nothing is below it
     if (frame_counts) frame_counts[f] = n;
   }
   __syncthreads();
   for (int b = threadIdx.x; b < B; b += 256) {
-    double a00 = 0.0, a01 = 0.0, b0 = 0.0, b1 = 0.0;
-    int64_t n = 0;
-    for (int t = 0; t < T; ++t) {
-      const size_t f = (size_t)b * T + t;
-      a00 += ws.fit_f[f * 4], a01 += ws.fit_f[f * 4 + 1], b0 += ws.fit_f[f * 4 + 2], b1 += ws.fit_f[f * 4 + 3];
-      n += ws.cnt_f[f];
-    }
-    const double a11 = (double)n;
+    double s[4];
+    int64_t n;
+    fold_frames<4, 1>(ws.fit_f, ws.cnt_f, b * T, T, s, &n);
+    const double a00 = s[0], a01 = s[1], b0 = s[2], b1 = s[3], a11 = (double)n;
     const double det = a00 * a11 - a01 * a01;
     double scale = 0.0, shift = 0.0;
     if (det != 0.0) {
@@ -203,8 +186,9 @@ __global__ __launch_bounds__(256) void deviation_partial_kernel(const float* __r
   const float sc = ws.ss[(f / T) * 2], sh = ws.ss[(f / T) * 2 + 1];
   const double mp = (double)ws.med[f * 2], mt = (double)ws.med[f * 2 + 1];
   Tuple<double, 2> s = {{0.0, 0.0}};
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
-    const Px<PPL> q(pf, tf, mf, (int)q0);
+  for (int64_t q0 = sweep_first<PPL>(b); q0 < hw; q0 += sweep_stride<DL_BPF, PPL>()) {
+    const int p0 = (int)q0;
+    const Px<PPL> q(pf, tf, mf, p0);
 #pragma unroll
     for (int j = 0; j < PPL; ++j)
       if (q.k[j]) {
@@ -212,14 +196,7 @@ __global__ __launch_bounds__(256) void deviation_partial_kernel(const float* __r
         s.v[1] += fabs((double)q.t[j] - mt);
       }
   }
-  __shared__ WaveSlots<Tuple<double, 2>> rs;
-  rs.put(s, SumOp{});
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const Tuple<double, 2> r = rs.get(SumOp{});
-    ws.dev_b[(size_t)blockIdx.x * 2] = r.v[0];
-    ws.dev_b[(size_t)blockIdx.x * 2 + 1] = r.v[1];
-  }
+  block_row<2>(s, ws.dev_b);
 }
 
 // s of normalize_prediction_robust: max(sum |x - m| / n, 1e-6), 1 for a frame without a kept pixel; which = 0 prediction, 1 target
@@ -227,7 +204,7 @@ __device__ double frame_scale(const Ws& ws, int f, int which) {
   const int64_t n = ws.cnt_f[f];
   if (n == 0) return 1.0;
   double s = 0.0;
-  for (int b = 0; b < DL_BPF; ++b) s += ws.dev_b[((size_t)f * DL_BPF + b) * 2 + which];
+  for (const size_t o : frame_blocks<DL_BPF>(f)) s += ws.dev_b[o * 2 + which];
   s = s / (double)n;
   return s < 1e-6 ? 1e-6 : s;
 }
@@ -256,12 +233,15 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restri
   Tuple<int, NACC> cnt;
 #pragma unroll
   for (int i = 0; i < NACC; ++i) acc.v[i] = 0.0, cnt.v[i] = 0;
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+  // The start below IS sweep_first<PPL>(b) of frame_sums.hpp, spelled out, and must stay equal to it (the lane owns the pixels
+  // every other pass gives it). With the call the compiler leaves neighbour loads and their addresses of this kernel unmerged
+  // (profiles/criteria_refactor.md).
+  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += sweep_stride<DL_BPF, PPL>()) {
     const int p0 = (int)q0;
     const Px<PPL> q(pf, tf, mf, p0);
     // the same pixels of the next frame: frames are hw apart, so these are the same kind of load as q's
     const Px<PPL> qn(pf + (has_next ? hw : 0), tf + (has_next ? hw : 0), mf + (has_next ? hw : 0), p0);
-    int y = p0 / W, x = p0 - y * W;
+    RowWalk at(p0, W);
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
       if (q.k[j]) {  // a dropped pixel is skipped: nothing under it is read into the sums
@@ -286,10 +266,10 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restri
 #pragma unroll
         for (int k = 0; k < DL_MAX_SCALES; ++k) {
           const int step = 1 << k;
-          on = on && k < scales && ((x | y) & (step - 1)) == 0;  // a point of the grid [::step, ::step]
+          on = on && k < scales && ((at.x | at.y) & (step - 1)) == 0;  // a point of the grid [::step, ::step]
           if (on) {
             cnt.v[A_G + k] += 1;
-            if (x + step < W) {
+            if (at.x + step < W) {
               const int jn = (j + 1) % PPL;
               if (PPL == 4 && k == 0 && jn > 0) {  // the next pixel of the quad, in the same row
                 if (q.k[jn]) acc.v[A_G + k] += fabs(diff(aligned(sc, q.p[jn], sh), q.t[jn]) - d);
@@ -297,51 +277,33 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restri
                 acc.v[A_G + k] += fabs(diff(aligned(sc, pf[p + step], sh), tf[p + step]) - d);
               }
             }
-            if (y + step < H) {
+            if (at.y + step < H) {
               const size_t o = (size_t)p + (size_t)step * W;
               if (mf[o] != 0) acc.v[A_G + k] += fabs(diff(aligned(sc, pf[o], sh), tf[o]) - d);
             }
           }
         }
       }
-      if (++x == W) x = 0, ++y;
+      at.step(W);
     }
   }
-  __shared__ WaveSlots<Tuple<double, NACC>> rs;
-  __shared__ WaveSlots<Tuple<int, NACC>> rc;
-  rs.put(acc, SumOp{});
-  rc.put(cnt, SumOp{});
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const Tuple<double, NACC> r = rs.get(SumOp{});
-    const Tuple<int, NACC> c = rc.get(SumOp{});
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) {
-      ws.acc_b[(size_t)blockIdx.x * NACC + i] = r.v[i];
-      ws.cnt_acc_b[(size_t)blockIdx.x * NACC + i] = (int64_t)c.v[i];
-    }
-  }
+  block_row<NACC, NACC>(acc, cnt, ws.acc_b, ws.cnt_acc_b);
 }
 
-// One block: every frame's blocks in index order, then the frames in index order. The integer slot of A_DATA holds the d1 hits.
+// One block: the fold of frame_sums.hpp. The integer slot of A_DATA holds the d1 hits.
 __global__ __launch_bounds__(256) void loss_finalise_kernel(void* __restrict__ workspace, int B, int T, double alpha, int scales,
                                                             double stable_scale, double* __restrict__ frame_stats,
                                                             double* __restrict__ out) {
   const Ws ws(workspace, B, T);
   const int F = B * T;
   for (int f = threadIdx.x; f < F; f += 256) {
-    double s[NACC];
-    int64_t n[NACC];
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) s[i] = 0.0, n[i] = 0;
-    for (int b = 0; b < DL_BPF; ++b)
-#pragma unroll
-      for (int i = 0; i < NACC; ++i) {
-        s[i] += ws.acc_b[((size_t)f * DL_BPF + b) * NACC + i];
-        n[i] += ws.cnt_acc_b[((size_t)f * DL_BPF + b) * NACC + i];
-      }
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) ws.acc_f[(size_t)f * NACC + i] = s[i], ws.cnt_acc_f[(size_t)f * NACC + i] = n[i];
+    // fold_blocks, with one row per trip: unrolled, the 2 * NACC accumulators and two rows in flight cost this kernel a wave
+    // of occupancy
+    double s[NACC] = {};
+    int64_t n[NACC] = {};
+#pragma unroll 1
+    for (const size_t o : frame_blocks<DL_BPF>(f)) add_row<NACC, NACC>(ws.acc_b, ws.cnt_acc_b, o, s, n);
+    store_row<NACC, NACC>(ws.acc_f, ws.cnt_acc_f, (size_t)f, s, n);
     if (frame_stats) {
       frame_stats[(size_t)f * 4] = (double)ws.med[f * 2];
       frame_stats[(size_t)f * 4 + 1] = frame_scale(ws, f, 0);
@@ -352,12 +314,12 @@ __global__ __launch_bounds__(256) void loss_finalise_kernel(void* __restrict__ w
   __syncthreads();
   if (threadIdx.x != 0) return;
   double s[NACC];
-  int64_t n[NACC], kept = 0;
-  for (int i = 0; i < NACC; ++i) s[i] = 0.0, n[i] = 0;
-  for (int f = 0; f < F; ++f) {
-    for (int i = 0; i < NACC; ++i) s[i] += ws.acc_f[(size_t)f * NACC + i], n[i] += ws.cnt_acc_f[(size_t)f * NACC + i];
-    kept += ws.cnt_f[f];
-  }
+  int64_t n[NACC + 1];  // the fused pass's counts, and the fit's kept pixels beside them
+  fold_frames<NACC, NACC + 1>(0, F, s, n, [&](int f, double* fs, int64_t* fn) {
+    load_row<NACC, NACC>(ws.acc_f, ws.cnt_acc_f, (size_t)f, fs, fn);
+    fn[NACC] = ws.cnt_f[f];
+  });
+  const int64_t kept = n[NACC];
   const double data = kept > 0 ? s[A_DATA] / (double)kept : 0.0;
   double reg = 0.0;
   for (int k = 0; k < DL_MAX_SCALES; ++k) {
@@ -388,7 +350,7 @@ __global__ __launch_bounds__(256) void loss_finalise_kernel(void* __restrict__ w
 //   prepare    one block: the per-frame scales once, and per term k = floor(n * keep) from the counts in out (on the device);
 //   select     one set of all frames, three slots (data, stable, absRel), rank k - 1 each: the thresholds (select.hpp);
 //   sums       per frame in DL_BPF blocks and per term: sum and count of the residuals below the threshold and of those at it;
-//   finalise   one block: blocks then frames in index order, w = (k - n_less) / n_tied, the five values and out[20..39].
+//   finalise   one block: the fold of frame_sums.hpp, w = (k - n_less) / n_tied, the five values and out[20..39].
 // The residuals are recomputed from the inputs by every pass (loss_px.hpp: the same expressions, so the same bits). One sweep
 // that writes float32 key planes for the select's passes, and three selects of one slot, were measured and dropped (DESIGN
 // 5.14, profiles/depth_loss_trim.md: 883 and 1209 against 824 us for the launch at [2, 32, 518, 518]).
@@ -516,9 +478,10 @@ __global__ __launch_bounds__(256) void trim_sum_kernel(TRIM_ARGS, const SelState
   Tuple<int, NTR> cnt;
 #pragma unroll
   for (int i = 0; i < NTR; ++i) acc.v[i] = 0.0, cnt.v[i] = 0;
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+  for (int64_t q0 = sweep_first<PPL>(b); q0 < hw; q0 += sweep_stride<DL_BPF, PPL>()) {
+    const int p0 = (int)q0;
     double r[PPL][TR_TERMS];
-    const uint32_t on = fr.residuals<PPL>((int)q0, r);
+    const uint32_t on = fr.residuals<PPL>(p0, r);
 #pragma unroll
     for (int j = 0; j < PPL; ++j)
 #pragma unroll
@@ -529,23 +492,10 @@ __global__ __launch_bounds__(256) void trim_sum_kernel(TRIM_ARGS, const SelState
           else if (key == thr[k]) acc.v[2 * k + 1] += r[j][k], cnt.v[2 * k + 1] += 1;
         }
   }
-  __shared__ WaveSlots<Tuple<double, NTR>> rs;
-  __shared__ WaveSlots<Tuple<int, NTR>> rc;
-  rs.put(acc, SumOp{});
-  rc.put(cnt, SumOp{});
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const Tuple<double, NTR> r = rs.get(SumOp{});
-    const Tuple<int, NTR> c = rc.get(SumOp{});
-#pragma unroll
-    for (int i = 0; i < NTR; ++i) {
-      tw.sum_b[(size_t)blockIdx.x * NTR + i] = r.v[i];
-      tw.cnt_b[(size_t)blockIdx.x * NTR + i] = (int64_t)c.v[i];
-    }
-  }
+  block_row<NTR, NTR>(acc, cnt, tw.sum_b, tw.cnt_b);
 }
 
-// One block: every frame's blocks in index order, then the frames in index order; then the trimmed values over the untrimmed.
+// One block: the fold of frame_sums.hpp; then the trimmed values over the untrimmed.
 __global__ __launch_bounds__(256) void trim_finalise_kernel(void* __restrict__ trim_workspace, int B, int T, double alpha,
                                                             double stable_scale, const SelState* __restrict__ st,
                                                             double* __restrict__ out) {
@@ -554,24 +504,14 @@ __global__ __launch_bounds__(256) void trim_finalise_kernel(void* __restrict__ t
   for (int f = threadIdx.x; f < F; f += 256) {
     double s[NTR];
     int64_t n[NTR];
-#pragma unroll
-    for (int i = 0; i < NTR; ++i) s[i] = 0.0, n[i] = 0;
-    for (int b = 0; b < DL_BPF; ++b)
-#pragma unroll
-      for (int i = 0; i < NTR; ++i) {
-        s[i] += tw.sum_b[((size_t)f * DL_BPF + b) * NTR + i];
-        n[i] += tw.cnt_b[((size_t)f * DL_BPF + b) * NTR + i];
-      }
-#pragma unroll
-    for (int i = 0; i < NTR; ++i) tw.sum_f[(size_t)f * NTR + i] = s[i], tw.cnt_f[(size_t)f * NTR + i] = n[i];
+    fold_blocks<NTR, NTR, DL_BPF>(tw.sum_b, tw.cnt_b, f, s, n);
+    store_row<NTR, NTR>(tw.sum_f, tw.cnt_f, (size_t)f, s, n);
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
   double s[NTR];
   int64_t n[NTR];
-  for (int i = 0; i < NTR; ++i) s[i] = 0.0, n[i] = 0;
-  for (int f = 0; f < F; ++f)
-    for (int i = 0; i < NTR; ++i) s[i] += tw.sum_f[(size_t)f * NTR + i], n[i] += tw.cnt_f[(size_t)f * NTR + i];
+  fold_frames<NTR, NTR>(tw.sum_f, tw.cnt_f, 0, F, s, n);
   const uint32_t thr[TR_TERMS] = {st[0].prefix, st[1].prefix, st[2].prefix};
   const double count[TR_TERMS] = {out[7], out[16], out[17]};
   double term[TR_TERMS];
@@ -609,15 +549,8 @@ static int depth_loss_check(const float* prediction, const float* target, const 
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || scales < 0) return VDN_EINVAL;
   if (out && stable_scale > 0.0 && T < 2) return VDN_EINVAL;  // the reference divides by a count of zero strides
   if ((int64_t)H * W > INT32_MAX || (int64_t)B * T > 65535 || scales > DL_MAX_SCALES) return VDN_EUNSUPPORTED;
-  if (((uintptr_t)prediction & 3) || ((uintptr_t)target & 3) || ((uintptr_t)scale_shift & 3)) return VDN_EALIGN;
-  if (((uintptr_t)workspace & 7) || ((uintptr_t)frame_stats & 7) || ((uintptr_t)frame_counts & 7) || ((uintptr_t)out & 7))
-    return VDN_EALIGN;
+  if (misaligned(4, prediction, target, scale_shift) || misaligned(8, workspace, frame_stats, frame_counts, out)) return VDN_EALIGN;
   return VDN_OK;
-}
-
-// four pixels per lane when every frame of every plane starts on 16 bytes (the mask on 4) and holds whole quads
-static bool depth_loss_wide(const float* prediction, const float* target, const uint8_t* mask, int hw) {
-  return hw % 4 == 0 && !((uintptr_t)prediction & 15) && !((uintptr_t)target & 15) && !((uintptr_t)mask & 3);
 }
 
 extern "C" int vdn_depth_loss(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
@@ -629,26 +562,21 @@ extern "C" int vdn_depth_loss(const float* prediction, const float* target, cons
   hipStream_t s = (hipStream_t)stream;
   const int F = B * T, hw = H * W;
   const dim3 grid((unsigned)F * DL_BPF), block(256);
-  const bool wide = depth_loss_wide(prediction, target, mask, hw);
   const Ws ws(workspace, B, T);
-  if (wide) hipLaunchKernelGGL(fit_partial_kernel<4>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
-  else hipLaunchKernelGGL(fit_partial_kernel<1>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
-  hipLaunchKernelGGL(fit_solve_kernel, dim3(1), block, 0, s, workspace, B, T, frame_counts, scale_shift);
-  if (out) {
+  with_ppl(wide_ok((size_t)hw, {prediction, target}, {mask}), [&](auto ppl) {
+    constexpr int PPL = decltype(ppl)::value;
+    hipLaunchKernelGGL(fit_partial_kernel<PPL>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
+    hipLaunchKernelGGL(fit_solve_kernel, dim3(1), block, 0, s, workspace, B, T, frame_counts, scale_shift);
+    if (!out) return;
     const uint32_t rank = (uint32_t)((hw - 1) / 2);  // torch.median: the lower of the two middle values
     select_launch(LossKey{prediction, target, mask, ws.ss, (size_t)hw, T}, F, 1, (size_t)hw, SelRanks<2>{{rank, rank}, nullptr}, ws.select, s);
     hipLaunchKernelGGL(median_store_kernel, dim3(grid_for((size_t)F * 2, 1024)), block, 0, s, select_state(ws.select, F, 2), F, ws.med);
     const int eff_scales = alpha > 0.0 ? scales : 0;  // the regulariser is skipped, as TrimmedProcrustesLoss skips it
     const int temporal = stable_scale > 0.0;
-    if (wide) {
-      hipLaunchKernelGGL(deviation_partial_kernel<4>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
-      hipLaunchKernelGGL(loss_partial_kernel<4>, grid, block, 0, s, prediction, target, mask, B, T, H, W, eff_scales, temporal, workspace);
-    } else {
-      hipLaunchKernelGGL(deviation_partial_kernel<1>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
-      hipLaunchKernelGGL(loss_partial_kernel<1>, grid, block, 0, s, prediction, target, mask, B, T, H, W, eff_scales, temporal, workspace);
-    }
+    hipLaunchKernelGGL(deviation_partial_kernel<PPL>, grid, block, 0, s, prediction, target, mask, B, T, hw, workspace);
+    hipLaunchKernelGGL(loss_partial_kernel<PPL>, grid, block, 0, s, prediction, target, mask, B, T, H, W, eff_scales, temporal, workspace);
     hipLaunchKernelGGL(loss_finalise_kernel, dim3(1), block, 0, s, workspace, B, T, alpha, eff_scales, stable_scale, frame_stats, out);
-  }
+  });
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }
@@ -676,14 +604,12 @@ extern "C" int vdn_depth_loss_trimmed(const float* prediction, const float* targ
   const Tw tw(tws, B, T);
   const SelState* st = select_state(tw.select, 1, TR_TERMS);
   hipLaunchKernelGGL(trim_prepare_kernel, dim3(1), block, 0, s, workspace, tws, B, T, keep, out);
-  auto run = [&](auto ppl) {
+  with_ppl(wide_ok((size_t)hw, {prediction, target}, {mask}), [&](auto ppl) {
     constexpr int PPL = decltype(ppl)::value;
     select_launch(TrimKey<PPL>{prediction, target, mask, B, T, hw, temporal, workspace, tws}, F, F, (size_t)hw,
                   SelRanks<TR_TERMS>{{0, 0, 0}, tw.rank}, tw.select, s);
     hipLaunchKernelGGL(trim_sum_kernel<PPL>, grid, block, 0, s, prediction, target, mask, B, T, hw, temporal, workspace, tws, st);
-  };
-  if (depth_loss_wide(prediction, target, mask, hw)) run(IC<4>{});
-  else run(IC<1>{});
+  });
   hipLaunchKernelGGL(trim_finalise_kernel, dim3(1), block, 0, s, tws, B, T, alpha, stable_scale, st, out);
   VDN_CHECK_LAUNCH();
   return VDN_OK;

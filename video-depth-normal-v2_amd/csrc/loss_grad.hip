@@ -9,7 +9,7 @@
 //   solve 2    one block: an item's frames in index order
 //   write      g_p = sc g_a + keep * (fit correction), rounded to float32 once; +0.0 at a dropped pixel
 // g_x is a gather: a pixel reads its left, right, upper and lower neighbour at stride 2^k on every grid it belongs to, inside
-// its own frame, and no lane writes another lane's pixel. There are no atomics; sums have the forward's fixed order.
+// its own frame, and no lane writes another lane's pixel. There are no atomics; sums have the fixed order of frame_sums.hpp.
 // Pass 1 leaves g_x in an fp64 plane of the workspace, pass 3 turns it into g_a in place and pass 5 reads it, so the stencil is
 // evaluated once. The alternative, every pass recomputing g_x from the inputs with a workspace that depends on B and T alone,
 // was measured and dropped: 679 against 380 us for the launch at [1, 32, 518, 518] (profiles/depth_loss_grad.md).
@@ -20,7 +20,7 @@
 // absRel parts of g_a carry the weight 1, w or 0 that the forward's selection gives their residual (loss_px.hpp), the key
 // recomputed from the inputs and compared with the threshold in out[20..34]. Untrimmed, every weight is an exact 1.
 #include "common.hpp"
-#include "reduce.hpp"
+#include "frame_sums.hpp"
 #include <limits.h>
 #include <math.h>
 
@@ -29,17 +29,17 @@
 
 namespace {
 
-constexpr int NSUM = 7;  // sum g_x, sum g_x x, sum |a - m|, sum p^2, sum p, sum p t, sum t
+constexpr int NSUM = 7;  // sum g_x, sum g_x x, sum |a - m|, sum p^2, sum p, sum p t, sum t; the row's one count is sigma
 enum { I_A00 = 0, I_A01, I_A11, I_B0, I_B1, I_D, I_OK, I_G0, I_G1, I_SLOTS };
 
 struct IntMinOp {
   __device__ __forceinline__ int operator()(int a, int b) const { return b < a ? b : a; }
 };
 
-// workspace, in 8-byte slots
+// workspace, in 8-byte slots; a pass's rows (frame_sums.hpp) are a sums array and a counts array
 struct Gw {
   double* sum_b;     // [F][DL_BPF][NSUM]
-  int64_t* sig_b;    // [F][DL_BPF] sigma
+  int64_t* sig_b;    // [F][DL_BPF] their counts: sigma
   int64_t* hold_b;   // [F][DL_BPF] lowest index with a == m, INT_MAX for none
   float* mm_b;       // [F][DL_BPF][2] block min, max of the kept target
   double* G_b;       // [F][DL_BPF][2] block sums g_a p, g_a
@@ -173,18 +173,19 @@ __global__ __launch_bounds__(256) void grad_stats_kernel(GRAD_ARGS) {
   Tuple<double, NSUM> s;
 #pragma unroll
   for (int i = 0; i < NSUM; ++i) s.v[i] = 0.0;
-  int sigma = 0, hold = INT_MAX;
+  Tuple<int, 1> sigma = {{0}};
+  int hold = INT_MAX;
   float mn = INFINITY, mx = -INFINITY;
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < c.hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+  for (int64_t q0 = sweep_first<PPL>(b); q0 < c.hw; q0 += sweep_stride<DL_BPF, PPL>()) {
     const int p0 = (int)q0;
     const Px<PPL, VEC> q(c.pf, c.tf, c.mf, p0);
-    int y = p0 / W, x = p0 - y * W;
+    RowWalk at(p0, W);
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
       double g = 0.0;
       if (q.k[j]) {
         const float a = aligned(c.sc, q.p[j], c.sh), t = q.t[j];
-        g = c.gx(p0 + j, y, x, c.diff(a, t));
+        g = c.gx(p0 + j, at.y, at.x, c.diff(a, t));
         const double dev = (double)a - c.mp, pd = (double)q.p[j], td = (double)t;
         s.v[0] += g;
         s.v[1] += g * (dev / c.sp);
@@ -193,51 +194,39 @@ __global__ __launch_bounds__(256) void grad_stats_kernel(GRAD_ARGS) {
         s.v[4] += pd;
         s.v[5] += pd * td;
         s.v[6] += td;
-        sigma += sgn(dev);
+        sigma.v[0] += sgn(dev);
         if (a == mpf) hold = IntMinOp{}(hold, p0 + j);
         mn = MinOp{}(mn, t);
         mx = MaxOp{}(mx, t);
       }
       ws.plane[(size_t)f * c.hw + p0 + j] = g;
-      if (++x == W) x = 0, ++y;
+      at.step(W);
     }
   }
-  __shared__ WaveSlots<Tuple<double, NSUM>> rs;
-  __shared__ WaveSlots<int> rg, rh;
+  __shared__ WaveSlots<int> rh;
   __shared__ WaveSlots<float> rmn, rmx;
-  rs.put(s, SumOp{});
-  rg.put(sigma, SumOp{});
   rh.put(hold, IntMinOp{});
   rmn.put(mn, MinOp{});
   rmx.put(mx, MaxOp{});
-  __syncthreads();
+  block_row<NSUM, 1>(s, sigma, ws.sum_b, ws.sig_b);
   if (threadIdx.x == 0) {
-    const Tuple<double, NSUM> r = rs.get(SumOp{});
-#pragma unroll
-    for (int i = 0; i < NSUM; ++i) ws.sum_b[(size_t)blockIdx.x * NSUM + i] = r.v[i];
-    ws.sig_b[blockIdx.x] = (int64_t)rg.get(SumOp{});
     ws.hold_b[blockIdx.x] = (int64_t)rh.get(IntMinOp{});
     ws.mm_b[(size_t)blockIdx.x * 2] = rmn.get(MinOp{});
     ws.mm_b[(size_t)blockIdx.x * 2 + 1] = rmx.get(MaxOp{});
   }
 }
 
-// One block: every frame's blocks in index order, then every item's frames in index order.
+// One block: the fold of frame_sums.hpp, a lane per frame and then a lane per item.
 __global__ __launch_bounds__(256) void grad_solve1_kernel(void* __restrict__ workspace, int B, int T, int hw, const double* __restrict__ fs,
                                                           const int64_t* __restrict__ fc) {
   const Gw ws(workspace, B, T);
   const int F = B * T;
   for (int f = threadIdx.x; f < F; f += 256) {
-    double s[NSUM];
-#pragma unroll
-    for (int i = 0; i < NSUM; ++i) s[i] = 0.0;
+    double s[NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     int64_t sigma = 0, hold = INT_MAX;
     float mn = INFINITY, mx = -INFINITY;
-    for (int b = 0; b < DL_BPF; ++b) {
-      const size_t o = (size_t)f * DL_BPF + b;
-#pragma unroll
-      for (int i = 0; i < NSUM; ++i) s[i] += ws.sum_b[o * NSUM + i];
-      sigma += ws.sig_b[o];
+    for (const size_t o : frame_blocks<DL_BPF>(f)) {
+      add_row<NSUM, 1>(ws.sum_b, ws.sig_b, o, s, &sigma);
       hold = ws.hold_b[o] < hold ? ws.hold_b[o] : hold;
       mn = MinOp{}(mn, ws.mm_b[o * 2]);
       mx = MaxOp{}(mx, ws.mm_b[o * 2 + 1]);
@@ -254,19 +243,17 @@ __global__ __launch_bounds__(256) void grad_solve1_kernel(void* __restrict__ wor
     // a median of 0 in a frame with a dropped pixel is taken to be a dropped pixel's 0: mask * a has the derivative 0 there
     ws.hold_f[f] = (n == 0 || hold == INT_MAX || (m == 0.0 && n < (int64_t)hw)) ? -1 : hold;
     ws.th[f] = (mx - mn) * 0.05f;  // -inf for a frame without a kept pixel: nothing is below it
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ws.fit_f[(size_t)f * 4 + i] = s[3 + i];
+    store_row<4, 0>(ws.fit_f, nullptr, (size_t)f, s + 3, nullptr);
   }
   __syncthreads();
   for (int b = threadIdx.x; b < B; b += 256) {
-    double a00 = 0.0, a01 = 0.0, b0 = 0.0, b1 = 0.0;
-    int64_t n = 0;
-    for (int t = 0; t < T; ++t) {
-      const size_t f = (size_t)b * T + t;
-      a00 += ws.fit_f[f * 4], a01 += ws.fit_f[f * 4 + 1], b0 += ws.fit_f[f * 4 + 2], b1 += ws.fit_f[f * 4 + 3];
-      n += fc[f];
-    }
-    const double a11 = (double)n, det = a00 * a11 - a01 * a01;
+    double s[4];
+    int64_t n;  // the forward's kept pixels, beside the fit's sums
+    fold_frames<4, 1>(b * T, T, s, &n, [&](int f, double* row_s, int64_t* row_n) {
+      load_row<4, 0>(ws.fit_f, nullptr, (size_t)f, row_s, nullptr);
+      row_n[0] = fc[f];
+    });
+    const double a00 = s[0], a01 = s[1], b0 = s[2], b1 = s[3], a11 = (double)n, det = a00 * a11 - a01 * a01;
     double* it = ws.item + (size_t)b * I_SLOTS;
     it[I_A00] = a00, it[I_A01] = a01, it[I_A11] = a11, it[I_B0] = b0, it[I_B1] = b1, it[I_D] = det + 1e-6;
     it[I_OK] = det != 0.0 ? 1.0 : 0.0;
@@ -283,7 +270,7 @@ __global__ __launch_bounds__(256) void grad_fit_partial_kernel(GRAD_ARGS) {
   const int64_t holder = ws.hold_f[f];
   const float th_self = ws.th[f], th_next = c.has_next ? ws.th[f + 1] : 0.f;
   Tuple<double, 2> s = {{0.0, 0.0}};
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < c.hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+  for (int64_t q0 = sweep_first<PPL>(b); q0 < c.hw; q0 += sweep_stride<DL_BPF, PPL>()) {
     const int p0 = (int)q0;
     const Px<PPL, VEC> q(c.pf, c.tf, c.mf, p0);
 #pragma unroll
@@ -298,17 +285,11 @@ __global__ __launch_bounds__(256) void grad_fit_partial_kernel(GRAD_ARGS) {
       }
     }
   }
-  __shared__ WaveSlots<Tuple<double, 2>> rs;
-  rs.put(s, SumOp{});
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const Tuple<double, 2> r = rs.get(SumOp{});
-    ws.G_b[(size_t)blockIdx.x * 2] = r.v[0];
-    ws.G_b[(size_t)blockIdx.x * 2 + 1] = r.v[1];
-  }
+  block_row<2>(s, ws.G_b);
 }
 
-// One block, a lane per item: every frame's blocks in index order, the frames in index order.
+// One block, a lane per item: the fold of frame_sums.hpp (every frame's blocks in index order, the frames in index order),
+// spelled out; keep it equal to fold_frames over fold_blocks (profiles/criteria_refactor.md says why it is not a call).
 __global__ __launch_bounds__(256) void grad_solve2_kernel(void* __restrict__ workspace, int B, int T) {
   const Gw ws(workspace, B, T);
   for (int b = threadIdx.x; b < B; b += 256) {
@@ -337,7 +318,9 @@ __global__ __launch_bounds__(256) void grad_write_kernel(GRAD_ARGS, float* __res
   const bool ok = it[I_OK] != 0.0;
   const double scd = (double)c.sc, shd = (double)c.sh;
   float* gf = grad + (size_t)f * c.hw;
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < c.hw; q0 += (int64_t)DL_BPF * 256 * PPL) {
+  // the start IS sweep_first<PPL>(b) of frame_sums.hpp, spelled out, and must stay equal to it (profiles/criteria_refactor.md
+  // says why it is not a call)
+  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < c.hw; q0 += sweep_stride<DL_BPF, PPL>()) {
     const int p0 = (int)q0;
     const Px<PPL, VEC> q(c.pf, c.tf, c.mf, p0);
     float r[PPL];
@@ -352,12 +335,7 @@ __global__ __launch_bounds__(256) void grad_write_kernel(GRAD_ARGS, float* __res
         r[j] = (float)(scd * g + fit);
       }
     }
-    if (VEC) {
-      *(f32x4*)(gf + p0) = f32x4{r[0], r[1], r[2], r[3]};
-    } else {
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) gf[p0 + j] = r[j];
-    }
+    store_px<PPL, VEC>(gf + p0, r);
   }
 }
 
@@ -380,19 +358,15 @@ static int depth_loss_backward(const float* prediction, const float* target, con
   if (stable_scale > 0.0 && T < 2) return VDN_EINVAL;
   if ((int64_t)H * W > INT32_MAX || (int64_t)B * T > 65535 || scales > DL_MAX_SCALES) return VDN_EUNSUPPORTED;
   if (trimmed && (uint64_t)B * T * (uint64_t)H * W > UINT32_MAX) return VDN_EUNSUPPORTED;  // as the trimmed forward
-  if (((uintptr_t)prediction & 3) || ((uintptr_t)target & 3) || ((uintptr_t)scale_shift & 3) || ((uintptr_t)coeff & 3) ||
-      ((uintptr_t)grad_prediction & 3))
-    return VDN_EALIGN;
-  if (((uintptr_t)workspace & 7) || ((uintptr_t)frame_stats & 7) || ((uintptr_t)frame_counts & 7) || ((uintptr_t)out & 7))
+  if (misaligned(4, prediction, target, scale_shift, coeff, grad_prediction) || misaligned(8, workspace, frame_stats, frame_counts, out))
     return VDN_EALIGN;
   hipStream_t s = (hipStream_t)stream;
   const int F = B * T, hw = H * W;
   const dim3 grid((unsigned)F * DL_BPF), block(256);
   // A lane owns four consecutive pixels whenever a frame holds whole quads, so the sums do not depend on where the tensors
-  // start; the 16-byte loads and stores are taken when every frame of every plane starts on 16 bytes (the mask on 4).
+  // start; the 16-byte loads and stores are taken when wide_ok allows them.
   const bool quads = hw % 4 == 0;
-  const bool vec = quads && !((uintptr_t)prediction & 15) && !((uintptr_t)target & 15) && !((uintptr_t)mask & 3) &&
-                   !((uintptr_t)grad_prediction & 15);
+  const bool vec = wide_ok((size_t)hw, {prediction, target, grad_prediction}, {mask});
   const int eff_scales = alpha > 0.0 ? scales : 0;  // as the forward: the regulariser is skipped
   const int temporal = stable_scale > 0.0;
   auto launch = [&](auto ppl, auto v) {
@@ -408,8 +382,7 @@ static int depth_loss_backward(const float* prediction, const float* target, con
                        temporal, scale_shift, frame_stats, frame_counts, out, coeff, trimmed, workspace, grad_prediction);
   };
   if (vec) launch(IC<4>{}, IC<1>{});
-  else if (quads) launch(IC<4>{}, IC<0>{});
-  else launch(IC<1>{}, IC<0>{});
+  else with_ppl(quads, [&](auto ppl) { launch(ppl, IC<0>{}); });  // quads on unaligned bases: a load per pixel
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

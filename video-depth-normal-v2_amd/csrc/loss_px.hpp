@@ -1,8 +1,9 @@
-// What the passes of the depth criterion share (loss.hip forward, loss_grad.hip backward): the block layout of a frame, the
-// aligned prediction and the load of a lane's pixels. Include it AFTER the unit's `#pragma clang fp contract(off)`: aligned()
+// What the passes of the depth criterion share (loss.hip forward, loss_grad.hip backward): the blocks per frame, the aligned
+// prediction, the trimmed criterion's residuals and a lane's pixels (swept, loaded and summed as frame_sums.hpp states). Include it AFTER the unit's `#pragma clang fp contract(off)`: aligned()
 // is a multiply that feeds an add, and both units must round it twice.
 #pragma once
 #include "common.hpp"
+#include "frame_sums.hpp"
 
 namespace {
 
@@ -45,23 +46,18 @@ __device__ __forceinline__ double trim_weight(const double* __restrict__ tr, uin
   return key < thr ? 1.0 : (key == thr ? tr[4] : 0.0);
 }
 
-// PPL consecutive pixels of a frame: 4 or 1. VEC: the four come by one 16-byte load per float plane and one 4-byte load of the
-// mask (the bases must allow it); otherwise every pixel by a load of its own, the lane owning the same pixels either way.
+// PPL consecutive pixels of a frame, loaded as frame_sums.hpp loads them (VEC: one 16-byte load per float plane and one 4-byte
+// load of the mask, which the bases must allow; the lane owns the same pixels either way), and which of them the mask keeps.
 template <int PPL, bool VEC = (PPL == 4)>
 struct Px {
   float p[PPL], t[PPL];
   bool k[PPL];
   __device__ __forceinline__ Px(const float* __restrict__ pf, const float* __restrict__ tf, const uint8_t* __restrict__ mf, int i) {
-    if (VEC) {
-      static_assert(!VEC || PPL == 4, "the vector loads take four pixels");
-      const f32x4 v = *(const f32x4*)(pf + i), w = *(const f32x4*)(tf + i);
-      const uint32_t m = *(const uint32_t*)(mf + i);
+    load_px<PPL, VEC>(pf + i, p);
+    load_px<PPL, VEC>(tf + i, t);
+    const uint32_t m = load_mask<PPL, VEC>(mf + i);
 #pragma unroll
-      for (int j = 0; j < PPL; ++j) p[j] = v[j], t[j] = w[j], k[j] = ((m >> (8 * j)) & 0xFFu) != 0;
-    } else {
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) p[j] = pf[i + j], t[j] = tf[i + j], k[j] = mf[i + j] != 0;
-    }
+    for (int j = 0; j < PPL; ++j) k[j] = mask_byte(m, j) != 0;
   }
 };
 

@@ -13,14 +13,14 @@
 // What decides something in float32 in the reference (the mask's comparisons, the resampled prediction, thresh and the three
 // quotients d_k) is the same float32 operation here, one rounding each; everything else is fp64 from the float32 inputs on.
 // Contraction is off: a product and the sum it feeds are rounded separately. Sums have a fixed order (a lane's stride through
-// its block's share, the wave and the block as reduce.hpp states them, the MT_BPI partials the same way): no atomics, two
-// runs give the same bits.
+// its block's share and the block's row as frame_sums.hpp states them, the MT_BPI partials one per lane through the same block
+// reduction): no atomics, two runs give the same bits.
 // A lane owns four consecutive elements (16-byte loads, one 4-byte load of the mask) where the item's length is a multiple of
 // 4 and the bases allow it, one element otherwise; the values do not depend on which. It issues the loads of MT_INFLIGHT
 // trips of the grid before it uses the first (sweep below): an item has only MT_BPI blocks, and the validation loop has one
 // item per launch.
 #include "common.hpp"
-#include "reduce.hpp"
+#include "frame_sums.hpp"
 #include "resample.hpp"
 #include <math.h>
 
@@ -42,12 +42,19 @@ struct Keep {
   __device__ __forceinline__ bool operator()(uint32_t m, float t) const { return m == 1u && (!on || (t >= lo && t <= hi)); }
 };
 
+// what a lane loaded at one visit
 template <int PPL>
-struct Px {
+struct Elems {
   float p[PPL], t[PPL];
   uint32_t m;  // PPL mask bytes, the first in the low byte
 };
 
+// A lane's share of an item of n elements: the PPL elements at (b * 256 + lane) * PPL + k * trip, k = 0, 1, ..., trip =
+// MT_BPI * 256 * PPL. body(i, px) gets the element index and what was loaded there: the target, the mask bytes (all 1 without
+// a mask) and, with LOAD_P, the prediction. This is the sweep of frame_sums.hpp with MT_INFLIGHT visits taken at a time, so that
+// the loads of all of them stand before the first use.
+// load_px of frame_sums.hpp for a plane and an index, spelled out: keep it equal to load_px. Through load_px the two resampling
+// kernels compile to other, longer code (profiles/criteria_refactor.md).
 template <int PPL>
 __device__ __forceinline__ void load_f(const float* p, int i, float (&v)[PPL]) {
   if (PPL == 4) {
@@ -59,14 +66,11 @@ __device__ __forceinline__ void load_f(const float* p, int i, float (&v)[PPL]) {
   }
 }
 
-// A lane's share of an item of n elements: the PPL elements at (b * 256 + lane) * PPL + k * trip, k = 0, 1, ..., trip =
-// MT_BPI * 256 * PPL. body(i, px) gets the element index and what was loaded there: the target, the mask bytes (all 1 without
-// a mask) and, with LOAD_P, the prediction.
 template <int PPL, bool LOAD_P, typename Body>
 __device__ __forceinline__ void sweep(const float* pf, const float* tf, const uint8_t* mf, int b, int n, Body body) {
-  const int64_t trip = (int64_t)MT_BPI * 256 * PPL;
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < n; q0 += trip * MT_INFLIGHT) {
-    Px<PPL> v[MT_INFLIGHT];
+  const int64_t trip = sweep_stride<MT_BPI, PPL>();
+  for (int64_t q0 = sweep_first<PPL>(b); q0 < n; q0 += trip * MT_INFLIGHT) {
+    Elems<PPL> v[MT_INFLIGHT];
 #pragma unroll
     for (int u = 0; u < MT_INFLIGHT; ++u)
       if (q0 + u * trip < n) {
@@ -74,7 +78,7 @@ __device__ __forceinline__ void sweep(const float* pf, const float* tf, const ui
         load_f<PPL>(tf, i, v[u].t);
         if (LOAD_P) load_f<PPL>(pf, i, v[u].p);
         v[u].m = 0x01010101u;
-        if (mf) v[u].m = PPL == 4 ? *(const uint32_t*)(mf + i) : (uint32_t)mf[i];
+        if (mf) v[u].m = load_mask<PPL>(mf + i);
       }
 #pragma unroll
     for (int u = 0; u < MT_INFLIGHT; ++u)
@@ -114,12 +118,12 @@ __global__ __launch_bounds__(256) void metric_partial_kernel(const float* __rest
   const Sampler sample{pf, ph, pw, ac_scale(ph, H), ac_scale(pw, W)};
   Tuple<double, EV_D> s = {{0, 0, 0, 0, 0, 0}};
   Tuple<int, EV_C> c = {{0, 0, 0, 0}};
-  sweep<PPL, !RESAMPLE>(pf, tf, mf, b, n, [&](int i, Px<PPL>& v) {
+  sweep<PPL, !RESAMPLE>(pf, tf, mf, b, n, [&](int i, Elems<PPL>& v) {
     int y = 0, x = 0;
     if (RESAMPLE) y = i / W, x = i - y * W;
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
-      if (keep((v.m >> (8 * j)) & 0xFFu, v.t[j])) {  // a dropped pixel is skipped: nothing under it reaches a sum
+      if (keep(mask_byte(v.m, j), v.t[j])) {  // a dropped pixel is skipped: nothing under it reaches a sum
         const float t32 = v.t[j], p32 = RESAMPLE ? sample(y, x) : v.p[j];
         const float q = max_nan(__fdiv_rn(t32, p32), __fdiv_rn(p32, t32));
         c.v[0] += 1;
@@ -138,6 +142,8 @@ __global__ __launch_bounds__(256) void metric_partial_kernel(const float* __rest
       if (RESAMPLE && ++x == W) x = 0, ++y;  // the next element of the lane begins the next row
     }
   });
+  // The block's row, spelled out: a partial keeps its counts behind its own sums, in EV_SLOTS slots, and the finish kernel
+  // reads it whole. Keep it equal to block_row of frame_sums.hpp (profiles/criteria_refactor.md).
   __shared__ WaveSlots<Tuple<double, EV_D>> rd;
   __shared__ WaveSlots<Tuple<int, EV_C>> rc;
   rd.put(s, SumOp{});
@@ -195,16 +201,17 @@ __global__ __launch_bounds__(256) void silog_partial_kernel(const float* __restr
                                                             double* __restrict__ partial) {
   Tuple<double, 2> s = {{0, 0}};
   int cnt = 0;
-  sweep<PPL, true>(pred, target, mask, (int)blockIdx.x, n, [&](int, Px<PPL>& v) {
+  sweep<PPL, true>(pred, target, mask, (int)blockIdx.x, n, [&](int, Elems<PPL>& v) {
 #pragma unroll
     for (int j = 0; j < PPL; ++j)
-      if (keep((v.m >> (8 * j)) & 0xFFu, v.t[j])) {
+      if (keep(mask_byte(v.m, j), v.t[j])) {
         const double dl = log((double)v.t[j]) - log((double)v.p[j]);
         s.v[0] += dl;
         s.v[1] += dl * dl;
         cnt += 1;
       }
   });
+  // the block's row, spelled out as in metric_partial_kernel: the count behind the block's own sums
   __shared__ WaveSlots<Tuple<double, 2>> rd;
   __shared__ WaveSlots<int> rc;
   rd.put(s, SumOp{});
@@ -246,19 +253,18 @@ __global__ __launch_bounds__(256) void silog_backward_kernel(const float* __rest
                                                              float* __restrict__ grad) {
   const double loss = state[0], cnt = state[1];
   const double shift = lambd * (state[2] / cnt), den = cnt * loss, co = (double)coeff[0];
-  sweep<PPL, true>(pred, target, mask, (int)blockIdx.x, n, [&](int i, Px<PPL>& v) {
+  sweep<PPL, true>(pred, target, mask, (int)blockIdx.x, n, [&](int i, Elems<PPL>& v) {
     float g[PPL];
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
       g[j] = 0.f;
-      if (keep((v.m >> (8 * j)) & 0xFFu, v.t[j])) {
+      if (keep(mask_byte(v.m, j), v.t[j])) {
         const double p = (double)v.p[j];
         const double dl = log((double)v.t[j]) - log(p);
         g[j] = (float)(co * (-(dl - shift) / (den * p)));
       }
     }
-    if (PPL == 4) *(f32x4*)(grad + i) = f32x4{g[0], g[1 % PPL], g[2 % PPL], g[3 % PPL]};
-    else grad[i] = g[0];
+    store_px<PPL>(grad + i, g);
   });
 }
 
@@ -272,7 +278,7 @@ inline bool make_keep(int bounded, double min_depth, double max_depth, Keep& k) 
 static_assert(MT_BPI == 256, "the finishing kernels read one partial per lane of a 256-lane block");
 static_assert(EV_C % 2 == 0, "the counts of a partial fill whole 8-byte slots");
 
-extern "C" int vdn_metric_trip(int wide) { return MT_BPI * 256 * (wide ? 4 : 1); }
+extern "C" int vdn_metric_trip(int wide) { return (int)(wide ? sweep_stride<MT_BPI, 4>() : sweep_stride<MT_BPI, 1>()); }
 
 extern "C" size_t vdn_metric_workspace_bytes(int items) {
   if (items <= 0) return 0;
@@ -288,21 +294,19 @@ extern "C" int vdn_metric_eval(const float* pred, const float* depth, const uint
   if (!pred || !depth || !workspace || !out) return VDN_EINVAL;
   if (items <= 0 || ph <= 0 || pw <= 0 || H <= 0 || W <= 0 || !make_keep(bounded, min_depth, max_depth, keep)) return VDN_EINVAL;
   if ((int64_t)H * W > INT32_MAX || (int64_t)ph * pw > INT32_MAX || items > 65535) return VDN_EUNSUPPORTED;
-  if (((uintptr_t)pred & 3) || ((uintptr_t)depth & 3) || ((uintptr_t)workspace & 7) || ((uintptr_t)out & 7)) return VDN_EALIGN;
+  if (misaligned(4, pred, depth) || misaligned(8, workspace, out)) return VDN_EALIGN;
   hipStream_t s = (hipStream_t)stream;
   const bool resample = ph != H || pw != W;
   const int n = H * W;
-  // four floats per lane when every item starts on 16 bytes (its mask on 4) and holds whole quads
-  const bool wide = n % 4 == 0 && !((uintptr_t)depth & 15) && !((uintptr_t)valid & 3) && (resample || !((uintptr_t)pred & 15));
   const dim3 grid((unsigned)items * MT_BPI), block(256);
   double* partial = (double*)workspace;
-#define VDN_METRIC_GO(P, R) \
-  hipLaunchKernelGGL((metric_partial_kernel<P, R>), grid, block, 0, s, pred, depth, valid, ph, pw, H, W, keep, partial)
-  if (wide && resample) VDN_METRIC_GO(4, true);
-  else if (wide) VDN_METRIC_GO(4, false);
-  else if (resample) VDN_METRIC_GO(1, true);
-  else VDN_METRIC_GO(1, false);
-#undef VDN_METRIC_GO
+  // a prediction of another size is sampled, never read by quads
+  with_ppl(wide_ok((size_t)n, {depth, resample ? nullptr : pred}, {valid}), [&](auto ppl) {
+    with_bool(resample, [&](auto resampled) {
+      hipLaunchKernelGGL((metric_partial_kernel<decltype(ppl)::value, decltype(resampled)::value>), grid, block, 0, s, pred, depth, valid,
+                         ph, pw, H, W, keep, partial);
+    });
+  });
   hipLaunchKernelGGL(metric_finish_kernel, dim3((unsigned)items), block, 0, s, (const double*)partial, out);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
@@ -315,13 +319,13 @@ extern "C" int vdn_silog_loss(const float* pred, const float* target, const uint
   if (!pred || !target || !workspace || !out) return VDN_EINVAL;
   if (count <= 0 || !make_keep(bounded, min_depth, max_depth, keep)) return VDN_EINVAL;
   if (count > INT32_MAX) return VDN_EUNSUPPORTED;
-  if (((uintptr_t)pred & 3) || ((uintptr_t)target & 3) || ((uintptr_t)workspace & 7) || ((uintptr_t)out & 7)) return VDN_EALIGN;
+  if (misaligned(4, pred, target) || misaligned(8, workspace, out)) return VDN_EALIGN;
   hipStream_t s = (hipStream_t)stream;
-  const bool wide = count % 4 == 0 && !((uintptr_t)pred & 15) && !((uintptr_t)target & 15) && !((uintptr_t)mask & 3);
   const dim3 grid(MT_BPI), block(256);
   double* partial = (double*)workspace;
-  if (wide) hipLaunchKernelGGL(silog_partial_kernel<4>, grid, block, 0, s, pred, target, mask, (int)count, keep, partial);
-  else hipLaunchKernelGGL(silog_partial_kernel<1>, grid, block, 0, s, pred, target, mask, (int)count, keep, partial);
+  with_ppl(wide_ok((size_t)count, {pred, target}, {mask}), [&](auto ppl) {
+    hipLaunchKernelGGL(silog_partial_kernel<decltype(ppl)::value>, grid, block, 0, s, pred, target, mask, (int)count, keep, partial);
+  });
   hipLaunchKernelGGL(silog_finish_kernel, dim3(1), block, 0, s, (const double*)partial, lambd, out);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
@@ -334,16 +338,13 @@ extern "C" int vdn_silog_loss_backward(const float* pred, const float* target, c
   if (!pred || !target || !state || !coeff || !grad) return VDN_EINVAL;
   if (count <= 0 || !make_keep(bounded, min_depth, max_depth, keep)) return VDN_EINVAL;
   if (count > INT32_MAX) return VDN_EUNSUPPORTED;
-  if (((uintptr_t)pred & 3) || ((uintptr_t)target & 3) || ((uintptr_t)grad & 3) || ((uintptr_t)coeff & 3) || ((uintptr_t)state & 7))
-    return VDN_EALIGN;
+  if (misaligned(4, pred, target, grad, coeff) || misaligned(8, state)) return VDN_EALIGN;
   hipStream_t s = (hipStream_t)stream;
-  const bool wide = count % 4 == 0 && !((uintptr_t)pred & 15) && !((uintptr_t)target & 15) && !((uintptr_t)grad & 15) &&
-                    !((uintptr_t)mask & 3);
   const dim3 grid(MT_BPI), block(256);
-  if (wide)
-    hipLaunchKernelGGL(silog_backward_kernel<4>, grid, block, 0, s, pred, target, mask, (int)count, keep, lambd, state, coeff, grad);
-  else
-    hipLaunchKernelGGL(silog_backward_kernel<1>, grid, block, 0, s, pred, target, mask, (int)count, keep, lambd, state, coeff, grad);
+  with_ppl(wide_ok((size_t)count, {pred, target, grad}, {mask}), [&](auto ppl) {
+    hipLaunchKernelGGL(silog_backward_kernel<decltype(ppl)::value>, grid, block, 0, s, pred, target, mask, (int)count, keep, lambd, state,
+                       coeff, grad);
+  });
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

@@ -1,9 +1,10 @@
-// What the passes of the normal criterion share (normals.hip forward, normals_grad.hip backward): the block layout of a
-// frame, the Sobel stencil and the unit normal made from it, the 3 x 3 erosion, the clamped norm of F.cosine_similarity, and
+// What the passes of the normal criterion share (normals.hip forward, normals_grad.hip backward): the blocks per frame
+// (swept and summed as frame_sums.hpp states), the Sobel stencil and the unit normal made from it, the 3 x 3 erosion, the clamped norm of F.cosine_similarity, and
 // the neighbourhood of a lane's pixels. Include it AFTER the unit's `#pragma clang fp contract(off)`: every product here feeds
 // a sum, and both units must round them apart.
 #pragma once
 #include "common.hpp"
+#include "frame_sums.hpp"
 #include <math.h>
 
 namespace {
@@ -115,19 +116,16 @@ struct Hood {
   }
 };
 
-// A lane's PPL consecutive pixels of the three planes of a frame: one 16-byte load per plane (PPL == 4) or one float.
+// A lane's PPL consecutive pixels of the three planes of a frame, loaded and stored as frame_sums.hpp does.
 template <int PPL>
 __device__ __forceinline__ void load3(const float* __restrict__ f, int hw, int p0, float (&v)[3][PPL]) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    if (PPL == 4) {
-      const f32x4 w = *(const f32x4*)(f + (size_t)c * hw + p0);
+  for (int c = 0; c < 3; ++c) load_px<PPL>(f + (size_t)c * hw + p0, v[c]);
+}
+template <int PPL>
+__device__ __forceinline__ void store3(float* __restrict__ f, int hw, int p0, const float (&v)[3][PPL]) {
 #pragma unroll
-      for (int j = 0; j < PPL; ++j) v[c][j] = w[j];
-    } else {
-      v[c][0] = f[(size_t)c * hw + p0];
-    }
-  }
+  for (int c = 0; c < 3; ++c) store_px<PPL>(f + (size_t)c * hw + p0, v[c]);
 }
 
 }  // namespace

@@ -5,13 +5,12 @@
 //   vdn_normal_eval                     one pass: erode, (make the target normal from depth,) cosine, per-block partial
 //                                       sums; then a one-block finalise
 // The stencil, the normalisation and the cosine are fp64 computed from the f32 samples, with separate multiply and add
-// roundings (contraction is off for this file). Sums have a fixed order: a lane's stride through its block's share, the
-// wave and the block as reduce.hpp states them, a frame's NE_BPF blocks in index order, the frames in index order. No
+// roundings (contraction is off for this file). Sums have the fixed order of frame_sums.hpp, with NE_BPF blocks per frame. No
 // atomics: two runs give the same bits. Any 4-byte-aligned pointer is accepted; vdn_normal_eval reads pred (and a stored
 // target) four floats per lane where the planes are 16-byte aligned, one per lane otherwise. Stencil and erosion neighbours
 // that belong to other lanes or blocks are read through the cache, as refine_pack_kernel does; the four pixels of a lane share theirs.
 #include "common.hpp"
-#include "reduce.hpp"
+#include "frame_sums.hpp"
 
 #pragma clang fp contract(off)
 #include "normal_px.hpp"
@@ -92,63 +91,48 @@ __global__ __launch_bounds__(256) void normal_eval_partial_kernel(const float* _
   const float* pf = pred + (size_t)f * 3 * hw;
   const float* tf = target + (size_t)f * (DEPTH ? 1 : 3) * hw;
   const uint8_t* mf = mask ? mask + (size_t)f * hw : nullptr;
-  double sum = 0.0;
-  int cnt = 0;
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)NE_BPF * 256 * PPL) {
+  Tuple<double, 1> sum = {{0.0}};
+  Tuple<int, 1> cnt = {{0}};
+  for (int64_t q0 = sweep_first<PPL>(b); q0 < hw; q0 += sweep_stride<NE_BPF, PPL>()) {
     const int p0 = (int)q0;
     float pv[3][PPL], tv[3][PPL];
     load3<PPL>(pf, hw, p0, pv);
     if (!DEPTH) load3<PPL>(tf, hw, p0, tv);
-    int y = p0 / W, x = p0 - y * W;
-    const Hood<PPL, DEPTH> hood(tf, mf, y, x, H, W);
+    RowWalk at(p0, W);
+    const Hood<PPL, DEPTH> hood(tf, mf, at.y, at.x, H, W);
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
-      if (hood.keep(mf, j, y, x, H, W)) {  // a dropped pixel is skipped: nothing under it is read into the sums
+      if (hood.keep(mf, j, at.y, at.x, H, W)) {  // a dropped pixel is skipped: nothing under it is read into the sums
         const double a[3] = {(double)pv[0][j], (double)pv[1][j], (double)pv[2][j]};
         double t[3];
-        if (DEPTH) hood.normal(tf, j, y, x, H, W, t);
+        if (DEPTH) hood.normal(tf, j, at.y, at.x, H, W, t);
         else t[0] = (double)tv[0][j], t[1] = (double)tv[1][j], t[2] = (double)tv[2][j];
-        sum += cosine3(a, t);
-        cnt += 1;
+        sum.v[0] += cosine3(a, t);
+        cnt.v[0] += 1;
       }
-      if (++x == W) x = 0, ++y;
+      at.step(W);
     }
   }
-  __shared__ WaveSlots<double> rs;
-  __shared__ WaveSlots<int> rc;
-  rs.put(sum, SumOp{});
-  rc.put(cnt, SumOp{});
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    ws.bsum[blockIdx.x] = rs.get(SumOp{});
-    ws.bcnt[blockIdx.x] = (int64_t)rc.get(SumOp{});
-  }
+  block_row<1, 1>(sum, cnt, ws.bsum, ws.bcnt);
 }
 
-// One block: every frame's blocks in index order, then the frames in index order.
+// One block: the fold of frame_sums.hpp.
 __global__ __launch_bounds__(256) void normal_eval_finalise_kernel(void* __restrict__ workspace, int T, double* __restrict__ frame_sums,
                                                                    int64_t* __restrict__ frame_counts, double* __restrict__ out) {
   const Ws ws(workspace, T);
   for (int f = threadIdx.x; f < T; f += 256) {
-    double s = 0.0;
-    int64_t n = 0;
-    for (int b = 0; b < NE_BPF; ++b) {
-      s += ws.bsum[(size_t)f * NE_BPF + b];
-      n += ws.bcnt[(size_t)f * NE_BPF + b];
-    }
-    ws.fsum[f] = s;
-    ws.fcnt[f] = n;
+    double s;
+    int64_t n;
+    fold_blocks<1, 1, NE_BPF>(ws.bsum, ws.bcnt, f, &s, &n);
+    store_row<1, 1>(ws.fsum, ws.fcnt, (size_t)f, &s, &n);
     if (frame_sums) frame_sums[f] = s;
     if (frame_counts) frame_counts[f] = n;
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
-  double s = 0.0;
-  int64_t n = 0;
-  for (int f = 0; f < T; ++f) {
-    s += ws.fsum[f];
-    n += ws.fcnt[f];
-  }
+  double s;
+  int64_t n;
+  fold_frames<1, 1>(ws.fsum, ws.fcnt, 0, T, &s, &n);
   out[0] = n > 0 ? 1.0 - s / (double)n : 1.0;  // reduction_batch_based: sum * 0 when nothing is kept
   out[1] = (double)n;
 }
@@ -171,7 +155,7 @@ extern "C" int vdn_sobel_ix_iy(const float* depth, float* ix, float* iy, int fra
                                vdn_stream stream) {
   if (!depth || !ix || !iy) return VDN_EINVAL;
   if (const int rc = check_frames(frames, H, W)) return rc;
-  if (((uintptr_t)depth & 3) || ((uintptr_t)ix & 3) || ((uintptr_t)iy & 3)) return VDN_EALIGN;
+  if (misaligned(4, depth, ix, iy)) return VDN_EALIGN;
   hipLaunchKernelGGL(normal_vector_kernel<0>, dim3(grid_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream,
                      depth, ix, iy, frames, H, W, normalize_kernel ? 0.125 : 1.0, 1.0, 1.0, 0.0);
   VDN_CHECK_LAUNCH();
@@ -182,7 +166,7 @@ extern "C" int vdn_normal_vector(const float* depth, float* out, int frames, int
                                  float scale_z, float eps, vdn_stream stream) {
   if (!depth || !out) return VDN_EINVAL;
   if (const int rc = check_frames(frames, H, W)) return rc;
-  if (((uintptr_t)depth & 3) || ((uintptr_t)out & 3)) return VDN_EALIGN;
+  if (misaligned(4, depth, out)) return VDN_EALIGN;
   hipLaunchKernelGGL(normal_vector_kernel<1>, dim3(grid_for((size_t)frames * H * W, 16384)), dim3(256), 0, (hipStream_t)stream,
                      depth, out, (float*)nullptr, frames, H, W, normalize_kernel ? 0.125 : 1.0, (double)scale_xy, (double)scale_z,
                      (double)eps);
@@ -204,20 +188,16 @@ extern "C" int vdn_normal_eval(const float* pred, const float* target, int targe
   if (!pred || !target || !workspace || !out) return VDN_EINVAL;
   if (const int rc = check_frames(frames, H, W)) return rc;
   if (frames > INT32_MAX / NE_BPF) return VDN_EINVAL;
-  if (((uintptr_t)pred & 3) || ((uintptr_t)target & 3)) return VDN_EALIGN;
-  if (((uintptr_t)workspace & 7) || ((uintptr_t)frame_sums & 7) || ((uintptr_t)frame_counts & 7) || ((uintptr_t)out & 7))
-    return VDN_EALIGN;
+  if (misaligned(4, pred, target) || misaligned(8, workspace, frame_sums, frame_counts, out)) return VDN_EALIGN;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)frames * NE_BPF), block(256);
-  // four floats per lane when every plane of every frame starts on 16 bytes and holds whole quads
-  const bool wide = ((size_t)H * W) % 4 == 0 && !((uintptr_t)pred & 15) && (target_is_depth || !((uintptr_t)target & 15));
-  if (target_is_depth) {
-    if (wide) hipLaunchKernelGGL((normal_eval_partial_kernel<4, true>), grid, block, 0, s, pred, target, mask, frames, H, W, workspace);
-    else hipLaunchKernelGGL((normal_eval_partial_kernel<1, true>), grid, block, 0, s, pred, target, mask, frames, H, W, workspace);
-  } else {
-    if (wide) hipLaunchKernelGGL((normal_eval_partial_kernel<4, false>), grid, block, 0, s, pred, target, mask, frames, H, W, workspace);
-    else hipLaunchKernelGGL((normal_eval_partial_kernel<1, false>), grid, block, 0, s, pred, target, mask, frames, H, W, workspace);
-  }
+  // a depth target is read through its stencil, never by quads
+  with_ppl(wide_ok((size_t)H * W, {pred, target_is_depth ? nullptr : target}), [&](auto ppl) {
+    with_bool(target_is_depth != 0, [&](auto depth) {
+      hipLaunchKernelGGL((normal_eval_partial_kernel<decltype(ppl)::value, decltype(depth)::value>), grid, block, 0, s, pred, target,
+                         mask, frames, H, W, workspace);
+    });
+  });
   hipLaunchKernelGGL(normal_eval_finalise_kernel, dim3(1), dim3(256), 0, s, workspace, frames, frame_sums, frame_counts, out);
   VDN_CHECK_LAUNCH();
   return VDN_OK;

@@ -5,7 +5,7 @@
 //     dL/dp_c = -(g / N) * (that_c - ((p . that) / n) * (p_c / |p|)) / n          (p_c / |p| := 0 where |p| = 0)
 // on both sides of the clamp, a dropped pixel +0.0, and everything +0.0 when N = 0.
 // One pass: a lane owns the pixels the forward gives it (four consecutive ones with 16-byte loads and stores where the planes
-// allow, one otherwise), reads the forward's count and the incoming coefficient from device memory and writes its pixels'
+// allow, one otherwise: frame_sums.hpp), reads the forward's count and the incoming coefficient from device memory and writes its pixels'
 // three components once. No sums, no atomics, no workspace: a component depends on its own pixel (and, for a depth target,
 // on the pixel's stencil) alone, so the two load shapes and two runs give the same bits. fp64 from the f32 samples,
 // contraction off, one rounding to float32 at the store.
@@ -33,20 +33,20 @@ __global__ __launch_bounds__(256) void normal_grad_kernel(const float* __restric
   const double N = count[0];
   const bool live = N > 0.0;                     // nothing kept: the loss is sum * 0 and its gradient +0.0 everywhere
   const double k = live ? -(coeff[0] / N) : 0.0;
-  for (int64_t q0 = (int64_t)(b * 256 + (int)threadIdx.x) * PPL; q0 < hw; q0 += (int64_t)NE_BPF * 256 * PPL) {
+  for (int64_t q0 = sweep_first<PPL>(b); q0 < hw; q0 += sweep_stride<NE_BPF, PPL>()) {
     const int p0 = (int)q0;
     float pv[3][PPL], tv[3][PPL], r[3][PPL];
     load3<PPL>(pf, hw, p0, pv);
     if (!DEPTH) load3<PPL>(tf, hw, p0, tv);
-    int y = p0 / W, x = p0 - y * W;
-    const Hood<PPL, DEPTH> hood(tf, mf, y, x, H, W);
+    RowWalk at(p0, W);
+    const Hood<PPL, DEPTH> hood(tf, mf, at.y, at.x, H, W);
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
       r[0][j] = r[1][j] = r[2][j] = 0.f;
-      if (live && hood.keep(mf, j, y, x, H, W)) {  // a dropped pixel is skipped: nothing under it is read
+      if (live && hood.keep(mf, j, at.y, at.x, H, W)) {  // a dropped pixel is skipped: nothing under it is read
         const double a[3] = {(double)pv[0][j], (double)pv[1][j], (double)pv[2][j]};
         double t[3];
-        if (DEPTH) hood.normal(tf, j, y, x, H, W, t);
+        if (DEPTH) hood.normal(tf, j, at.y, at.x, H, W, t);
         else t[0] = (double)tv[0][j], t[1] = (double)tv[1][j], t[2] = (double)tv[2][j];
         const double na = norm3(a);
         const double inv_n = 1.0 / clamp_norm(na), inv_nt = 1.0 / clamp_norm(norm3(t));
@@ -56,19 +56,15 @@ __global__ __launch_bounds__(256) void normal_grad_kernel(const float* __restric
 #pragma unroll
         for (int c = 0; c < 3; ++c) r[c][j] = (float)(k * ((th[c] - d * (a[c] * inv_na)) * inv_n));
       }
-      if (++x == W) x = 0, ++y;
+      at.step(W);
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if (PPL == 4) *(f32x4*)(gf + (size_t)c * hw + p0) = f32x4{r[c][0], r[c][1], r[c][2], r[c][3]};
-      else gf[(size_t)c * hw + p0] = r[c][0];
-    }
+    store3<PPL>(gf, hw, p0, r);
   }
 }
 
 }  // namespace
 
-extern "C" int vdn_normal_loss_backward_trip(int wide) { return NE_BPF * 256 * (wide ? 4 : 1); }
+extern "C" int vdn_normal_loss_backward_trip(int wide) { return (int)(wide ? sweep_stride<NE_BPF, 4>() : sweep_stride<NE_BPF, 1>()); }
 
 extern "C" int vdn_normal_loss_backward(const float* pred, const float* target, int target_is_depth, const uint8_t* mask, int frames,
                                         int H, int W, const double* count, const double* coeff, float* grad_pred, vdn_stream stream) {
@@ -76,20 +72,16 @@ extern "C" int vdn_normal_loss_backward(const float* pred, const float* target, 
   if (frames <= 0 || H < 2 || W < 2) return VDN_EINVAL;
   if ((int64_t)H * W > INT32_MAX) return VDN_EUNSUPPORTED;
   if (frames > INT32_MAX / NE_BPF) return VDN_EINVAL;
-  if (((uintptr_t)pred & 3) || ((uintptr_t)target & 3) || ((uintptr_t)grad_pred & 3)) return VDN_EALIGN;
-  if (((uintptr_t)count & 7) || ((uintptr_t)coeff & 7)) return VDN_EALIGN;
+  if (misaligned(4, pred, target, grad_pred) || misaligned(8, count, coeff)) return VDN_EALIGN;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)frames * NE_BPF), block(256);
-  // four floats per lane when every plane of every frame starts on 16 bytes and holds whole quads
-  const bool wide = ((size_t)H * W) % 4 == 0 && !((uintptr_t)pred & 15) && !((uintptr_t)grad_pred & 15) &&
-                    (target_is_depth || !((uintptr_t)target & 15));
-  if (target_is_depth) {
-    if (wide) hipLaunchKernelGGL((normal_grad_kernel<4, true>), grid, block, 0, s, pred, target, mask, H, W, count, coeff, grad_pred);
-    else hipLaunchKernelGGL((normal_grad_kernel<1, true>), grid, block, 0, s, pred, target, mask, H, W, count, coeff, grad_pred);
-  } else {
-    if (wide) hipLaunchKernelGGL((normal_grad_kernel<4, false>), grid, block, 0, s, pred, target, mask, H, W, count, coeff, grad_pred);
-    else hipLaunchKernelGGL((normal_grad_kernel<1, false>), grid, block, 0, s, pred, target, mask, H, W, count, coeff, grad_pred);
-  }
+  // a depth target is read through its stencil, never by quads
+  with_ppl(wide_ok((size_t)H * W, {pred, grad_pred, target_is_depth ? nullptr : target}), [&](auto ppl) {
+    with_bool(target_is_depth != 0, [&](auto depth) {
+      hipLaunchKernelGGL((normal_grad_kernel<decltype(ppl)::value, decltype(depth)::value>), grid, block, 0, s, pred, target, mask,
+                         H, W, count, coeff, grad_pred);
+    });
+  });
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

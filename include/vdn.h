@@ -736,8 +736,10 @@ int vdn_colorize(const float* depth, const float* minmax, int per_frame, const u
 
 /* Depth-refiner wrappers v2 .. v5 (models/video_depth_model_v5.py:63-87,160-192, models/video_depth_model_v4.py:117-148,
  * utils/normal_utils.py:4-51). f32 throughout, frames are [frames, n = H*W] row-major.
- * vdn_frame_median  — median[f] = torch.quantile(x[f], 0.5) (linear interpolation), exact radix select;
- *                     workspace = vdn_frame_median_workspace_bytes(frames).
+ * vdn_frame_median  — median[f] = torch.quantile(x[f], 0.5) (linear interpolation), exact radix select; a frame that
+ *                     holds a NaN of either sign gets a NaN, as torch.quantile gives it, and leaves the other frames'
+ *                     medians alone. workspace = vdn_frame_median_workspace_bytes(frames): the select's bins and state
+ *                     and one 4-byte NaN flag per frame, which the entry zeroes itself (one memset on `stream`).
  * vdn_refine_scale  — out = x / max_depth * s_f, s_f = exp(tanh(w * median[f] / max_depth + b) * max_log_scale)
  *                     (GlobalScaleHead: quantile pool -> 1x1 conv -> TanhToExp); scale_out[f] = s_f (may be NULL).
  * vdn_refine_pack   — encoder input [frames,3,H,W] = (d, nx, ny); normals != 0: Sobel/8 on a reflect-padded map,
@@ -848,7 +850,9 @@ int vdn_dn_tail(const float* x, int F, int IH, int IW, int Cin, const float* w, 
  *                    Shares lane_attn_kernel with vdn_dn_attn: in that entry's terms L = Lkv, estride = W, n0 = W, s0 = 1,
  *                    n1 = frames, s1 = W*Lkv, with output stride W*Lq and q_stride elements pooled into a query.
  * vdn_hiera_pool   — y[f, j, :] = max over g < 4 of x[f, g*n + j, :]; x f32 [frames, 4n, C], y f32 [frames, n, C]
- *                    (the max-pool of a width-changing block's projected residual). C % 4 == 0.
+ *                    (the max-pool of a width-changing block's projected residual). C % 4 == 0. Departure from the
+ *                    reference, whose pool is torch.max / MaxPool and hands a NaN on: the max is C's fmaxf, where a NaN
+ *                    loses against a number, so a token's NaN reaches y only when all four groups hold one there.
  * vdn_hiera_reroll — the model's `reroll` + undo_windowing: unrolled tokens f32 [frames, (56 >> stage)^2, C] of stage
  *                    0..3 -> f32 NHWC map [frames, 56 >> stage, 56 >> stage, C] (what vdn_dn_prologue reads). C % 4 == 0. */
 int vdn_hiera_embed(int dt, const float* img, void* rows, void* rows_lo, int frames, int ldk, vdn_stream stream);

@@ -3,7 +3,10 @@
 // utils/normal_utils.py:4-51):
 //   vdn_frame_median  — torch.quantile(x, 0.5) per frame (linear interpolation between the two middle order
 //                       statistics) as the exact 3-pass radix select of select.hpp (integer atomics: deterministic),
-//                       both ranks in the same passes;
+//                       both ranks in the same passes. A frame that holds a NaN of either sign gets a NaN, as
+//                       torch.quantile gives it: the select orders keys by bit pattern, where a NaN sits beyond the
+//                       infinity of its sign and would be passed over, so the key functor raises a per-frame flag (a
+//                       plain store of 1: every writer stores the same word) that the last kernel reads;
 //   vdn_refine_scale  — x / max_depth * exp(tanh(w * median / max_depth + b) * max_log_scale)  (GlobalScaleHead);
 //   vdn_refine_pack   — network input [F,3,H,W] = (d, nx, ny) with n = (-Ix, -Iy, 1)/|.|, Sobel/8 on a reflect pad;
 //   vdn_refine_finish — (scaled + (w * depth + b)) * max_depth  (scalar 1x1 'ZeroConv' shift + residual; v3: max_depth 1);
@@ -16,9 +19,32 @@
 
 namespace {
 
-__global__ void median_final_kernel(const SelState* st, int F, size_t n, float* median) {
+// the plain sample: both slots select among the same keys; nan[f] = 1 when frame f holds a NaN (zeroed before the select)
+struct MedianKey {
+  static constexpr int SLOTS = 2, PER = 1;
+  const float* x;
+  size_t n;
+  uint32_t* nan;
+  __device__ __forceinline__ uint32_t operator()(int f, size_t i, uint32_t (&key)[1][2]) const {
+    const float v = x[(size_t)f * n + i];
+    if (v != v) nan[f] = 1u;
+    key[0][0] = key[0][1] = ordered_key(v);
+    return 3u;
+  }
+};
+
+// the flags sit behind the select's state
+inline uint32_t* median_nan_flags(void* workspace, int frames) {
+  return (uint32_t*)(select_state(workspace, frames, 2) + (size_t)frames * 2);
+}
+
+__global__ void median_final_kernel(const SelState* st, const uint32_t* nan, int F, size_t n, float* median) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= F) return;
+  if (nan[f]) {
+    median[f] = __builtin_nanf("");
+    return;
+  }
   const float a = key_value(st[f * 2].prefix), b = key_value(st[f * 2 + 1].prefix);
   const float w = (n & 1) ? 0.f : 0.5f;  // fractional part of 0.5 (n - 1)
   median[f] = w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.f - w);  // at::lerp's two-sided form
@@ -135,15 +161,19 @@ int launch_elementwise(const float* a, const float* b, float* out, size_t n, Op 
 }  // namespace
 
 extern "C" size_t vdn_frame_median_workspace_bytes(int frames) {
-  return frames <= 0 ? 0 : select_workspace_bytes(frames, 2);
+  return frames <= 0 ? 0 : select_workspace_bytes(frames, 2) + (size_t)frames * sizeof(uint32_t);   // + the NaN flags
 }
 
 extern "C" int vdn_frame_median(const float* x, int frames, size_t n, float* median, void* workspace, vdn_stream stream) {
   if (!x || !median || !workspace || frames <= 0 || n == 0) return VDN_EINVAL;
   if (n >= ((size_t)1 << 32)) return VDN_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  select_launch(SampleKey{x, n}, frames, 1, n, SelRanks<2>{{(uint32_t)((n - 1) / 2), (uint32_t)(n / 2)}, nullptr}, workspace, s);  // floor / ceil of 0.5 (n - 1)
-  hipLaunchKernelGGL(median_final_kernel, dim3((frames + 63) / 64), dim3(64), 0, s, select_state(workspace, frames, 2), frames, n, median);
+  uint32_t* nan = median_nan_flags(workspace, frames);
+  const hipError_t e = hipMemsetAsync(nan, 0, (size_t)frames * sizeof(uint32_t), s);
+  if (e != hipSuccess) return -(1000 + (int)e);
+  select_launch(MedianKey{x, n, nan}, frames, 1, n, SelRanks<2>{{(uint32_t)((n - 1) / 2), (uint32_t)(n / 2)}, nullptr}, workspace, s);  // floor / ceil of 0.5 (n - 1)
+  hipLaunchKernelGGL(median_final_kernel, dim3((frames + 63) / 64), dim3(64), 0, s, select_state(workspace, frames, 2), nan, frames, n,
+                     median);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

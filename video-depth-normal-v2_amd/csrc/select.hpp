@@ -42,17 +42,6 @@ struct SelRanks {
   const uint32_t* dev;   // [SLOTS] in device memory, read by the select's first kernel
 };
 
-// the plain sample: both slots select among the same keys
-struct SampleKey {
-  static constexpr int SLOTS = 2, PER = 1;
-  const float* x;
-  size_t n;
-  __device__ __forceinline__ uint32_t operator()(int f, size_t i, uint32_t (&key)[1][2]) const {
-    key[0][0] = key[0][1] = ordered_key(x[(size_t)f * n + i]);
-    return 3u;
-  }
-};
-
 template <int SLOTS>
 __global__ void select_init_kernel(SelState* st, uint32_t* hist, int sets, SelRanks<SLOTS> ranks) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

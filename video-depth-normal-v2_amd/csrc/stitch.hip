@@ -64,11 +64,14 @@ __global__ void align_solve_kernel(const double* __restrict__ partial, int nbloc
 //   frames align_len .. overlap-1      : out_tail[i] = out_tail[i] * (1 - w_i) + fit(frame) * w_i   (i = 0 .. interp-1)
 //   frames overlap .. T-1              : out_new[j]  = fit(frame)
 //   frame ref_frame (the 2nd keyframe) : ref1        = fit(frame)                                    (extra write)
-// fit(d) = max(d * scale + shift, 0) with separate multiply and add roundings, as numpy evaluates it.
+// fit(d) = max(d * scale + shift, 0) with separate multiply and add roundings, as numpy evaluates it: plain products and
+// sums with contraction switched off in this function. (__fmul_rn and __fadd_rn are a plain product and sum compiled under
+// their header's mode, not this one: nested, they came out as one fma.)
 __global__ __launch_bounds__(256) void align_apply_kernel(const float* __restrict__ win, const float* __restrict__ coef,
                                                           float* __restrict__ out_tail, float* __restrict__ out_new,
                                                           float* __restrict__ ref1, size_t hw, int T, int align_len,
                                                           int overlap, int ref_frame) {
+#pragma clang fp contract(off)
   const float scale = coef[0], shift = coef[1];
   const int interp = overlap - align_len;
   const float step = 1.0f / (float)(interp - 1);
@@ -76,12 +79,12 @@ __global__ __launch_bounds__(256) void align_apply_kernel(const float* __restric
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int f = align_len + (int)(i / hw);
     const size_t px = i - (size_t)(f - align_len) * hw;
-    const float d = fmaxf(__fadd_rn(__fmul_rn(win[(size_t)f * hw + px], scale), shift), 0.f);
+    const float d = fmaxf(win[(size_t)f * hw + px] * scale + shift, 0.f);
     if (f < overlap) {
       const int k = f - align_len;
       const float w = k == 0 ? 0.f : (k == interp - 1 ? 1.f : (float)k * step);
       float* o = out_tail + (size_t)k * hw + px;
-      *o = __fadd_rn(__fmul_rn(*o, 1.f - w), __fmul_rn(d, w));
+      *o = *o * (1.f - w) + d * w;
     } else {
       out_new[(size_t)(f - overlap) * hw + px] = d;
     }

@@ -78,6 +78,65 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in _abi.lib.vdn_version()
 
 
+_C_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+              "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint8_t": ctypes.c_uint8}
+
+
+def _header_prototypes():
+    """{name: (result type, [parameter types])} of include/vdn.h as C text, comments and parameter names dropped."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vdn.h")).read(), flags=re.S)
+    protos = {}
+    for res, name, params in re.findall(r"^((?:const\s+)?\w+\s*\*?)\s*(vdn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M):
+        params = [re.sub(r"\s+", " ", p).strip() for p in params.split(",")]
+        types = [] if params == ["void"] else [re.sub(r"\s*\b\w+$", "", p).replace(" *", "*") for p in params]
+        protos[name] = (re.sub(r"\s+", " ", res).strip().replace(" *", "*"), types)
+    return protos
+
+
+def _ctype_agrees(c_type: str, entry, pointers: dict) -> bool:
+    """Does the ctypes `entry` of vdn/_abi.py stand for the C type? A scalar has one ctypes type; vdn_stream and a pointer take
+    c_void_p, or the POINTER(...) of their pointee; the three pointers of `pointers` take that POINTER(...) only."""
+    if c_type in pointers:
+        return entry is pointers[c_type]
+    if c_type == "vdn_stream" or c_type.endswith("*"):
+        pointee = _C_SCALARS.get(c_type.replace("const ", "").rstrip("*"))
+        return entry is ctypes.c_void_p or (pointee is not None and entry is ctypes.POINTER(pointee))
+    return entry is _C_SCALARS[c_type]
+
+
+def _signature_mismatches(exports) -> list:
+    from vdn import _abi
+    pointers = {"const vdn_gemm_desc*": ctypes.POINTER(_abi.GemmDesc), "vdn_gemm_tuning*": ctypes.POINTER(_abi.GemmTuning),
+                "const int32_t*": ctypes.POINTER(ctypes.c_int32)}
+    bad = []
+    for name, (res, params) in _header_prototypes().items():
+        e_res, e_params = exports[name]
+        if not (e_res is ctypes.c_char_p if res == "const char*" else _ctype_agrees(res, e_res, pointers)):
+            bad.append(f"{name}: result {res} is {e_res.__name__} in _abi.EXPORTS")
+        if len(params) != len(e_params):
+            bad.append(f"{name}: {len(params)} parameters in vdn.h, {len(e_params)} in _abi.EXPORTS")
+            continue
+        bad += [f"{name}: parameter {i} {p} is {e.__name__} in _abi.EXPORTS" for i, (p, e) in enumerate(zip(params, e_params))
+                if not _ctype_agrees(p, e, pointers)]
+    return bad
+
+
+def test_every_prototype_has_the_types_of_the_abi_table():
+    """The result and every parameter type of each prototype of include/vdn.h equal vdn/_abi.py's EXPORTS: ctypes converts
+    silently, so an int where a size_t is declared would go unnoticed. An edited table entry is reported."""
+    from vdn import _abi
+    protos = _header_prototypes()
+    assert set(protos) == set(_abi.EXPORTS) and len(protos) >= 87, set(protos) ^ set(_abi.EXPORTS)
+    assert _signature_mismatches(_abi.EXPORTS) == []
+    res, params = _abi.EXPORTS["vdn_stitch_fit"]                     # size_t n -> int: one entry edited
+    edited = dict(_abi.EXPORTS, vdn_stitch_fit=(res, params[:2] + [ctypes.c_int] + params[3:]))
+    assert _signature_mismatches(edited) == ["vdn_stitch_fit: parameter 2 size_t is c_int in _abi.EXPORTS"]
+    edited = dict(_abi.EXPORTS, vdn_eval_workspace_bytes=(ctypes.c_int, [ctypes.c_int]))
+    assert _signature_mismatches(edited) == ["vdn_eval_workspace_bytes: result size_t is c_int in _abi.EXPORTS"]
+    edited = dict(_abi.EXPORTS, vdn_refine_pack=(ctypes.c_int, _abi.EXPORTS["vdn_refine_pack"][1][:-1]))
+    assert _signature_mismatches(edited) == ["vdn_refine_pack: 7 parameters in vdn.h, 6 in _abi.EXPORTS"]
+
+
 def test_gemm_argument_validation_without_gpu():
     """vdn_gemm rejects malformed descriptors before touching the device."""
     from vdn import _abi

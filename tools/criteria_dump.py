@@ -97,10 +97,10 @@ def main():
         fresh().depth_loss_backward(pred, target, mask, 0.5, 4, 10.0, ss, fs, fc, out, coeff, grad)
         dump(f"depth_loss_backward_{case}", grad=grad)
         out, ss, fs, fc = state(40)
-        fresh().depth_loss_trimmed(pred, target, mask, out, 0.8, scale_shift=ss, frame_stats=fs, frame_counts=fc, **args)
+        fresh().depth_loss(pred, target, mask, out, scale_shift=ss, frame_stats=fs, frame_counts=fc, keep=0.8, **args)
         dump(f"depth_loss_trimmed_{case}", out=out, scale_shift=ss, frame_stats=fs, frame_counts=fc)
         grad = empty(B, T, H, W, off=off)
-        fresh().depth_loss_trimmed_backward(pred, target, mask, 0.5, 4, 10.0, ss, fs, fc, out, coeff, grad)
+        fresh().depth_loss_backward(pred, target, mask, 0.5, 4, 10.0, ss, fs, fc, out, coeff, grad, keep=0.8)
         dump(f"depth_loss_trimmed_backward_{case}", grad=grad)
 
     depth("2x3x5x7", 2, 3, 5, 7)

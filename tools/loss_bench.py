@@ -100,7 +100,7 @@ def time_shape(shape, a, dev):
     for s in pool:
         s["fit"] = tuple(s[k].view(B, T * H, W) for k in ("pred", "target", "mask"))
     crit = L.VideoDepthLoss()
-    rt = L._runtime_for(dev, base["pred"])
+    rt = L.runtime_for(dev, base["pred"])
     med = torch.empty(B * T, dtype=torch.float32, device=dev)
     at = lambda i: pool[i % sets]
     t = dict(

@@ -74,7 +74,7 @@ def torch_composition(pred, depth, mask):
 def time_shape(T, H, W, a, dev):
     import normal_ref as R
     from vdn import normals as N
-    rt = N._runtime(dev)
+    rt = N._runtime_for(dev)
     c = R.make_case(9, (1, T, H, W), "bool", "unit")
     px = T * H * W
     fused_bytes, stored_bytes = 17 * px, 25 * px

@@ -86,7 +86,7 @@ def saved_counts(rt, pool, dev):
 
 def trace(a, dev):
     from vdn import normals as N
-    rt = N._runtime(dev)
+    rt = N._runtime_for(dev)
     pool, _ = make_pool(a.frames, a.size, a.size, dev)
     counts, one = saved_counts(rt, pool, dev), torch.ones(1, dtype=torch.float64, device=dev)
     out = torch.zeros(2, dtype=torch.float64, device=dev)
@@ -142,7 +142,7 @@ def main():
     if a.trace:
         return trace(a, dev)
     from vdn import normals as N
-    rt = N._runtime(dev)
+    rt = N._runtime_for(dev)
     T, H, W = a.frames, a.size, a.size
     pool, px = make_pool(T, H, W, dev)
     sets = len(pool)

@@ -8,13 +8,12 @@ by
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import List
 
-import numpy as np
 import torch
 
 from . import _abi as abi
-from .runtime import Runtime
+from ._device import runtime as _runtime, runtime_for, stage   # _runtime: the name the GPU tests and tools fetch the runtime by
 
 eval_metrics = [
     "abs_relative_difference",
@@ -27,29 +26,6 @@ eval_metrics = [
 ]
 
 _DOMAINS = {"depth": abi.EVAL_DEPTH, "disp": abi.EVAL_DISP}
-_RUNTIMES: Dict[torch.device, Runtime] = {}
-
-
-def _runtime(device: torch.device) -> Runtime:
-    if device.type != "cuda":
-        raise abi.VdnError("vdn.eval runs on an MI355X ('cuda' device under ROCm); there is no CPU path")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if device not in _RUNTIMES:
-        _RUNTIMES[device] = Runtime(device)
-    return _RUNTIMES[device]
-
-
-def _on_device(x, device: torch.device, dtype: torch.dtype) -> torch.Tensor:
-    """A CUDA tensor of the right type is used in place; anything else is copied once."""
-    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"expected a numpy array or a torch tensor, got {type(x).__name__}")
-    if t.dtype == torch.bool and dtype == torch.uint8 and t.is_cuda:
-        return t.contiguous().view(torch.uint8)
-    if dtype == torch.uint8 and t.dtype != torch.uint8:
-        t = t != 0
-    return t.to(device=device if not t.is_cuda else t.device, dtype=dtype).contiguous()
 
 
 def _check_clip(pred_disp, gt_disp, seq_len, domain, mask) -> int:
@@ -70,9 +46,9 @@ def _check_clip(pred_disp, gt_disp, seq_len, domain, mask) -> int:
 def _clip_launches(rt, pred_disp, gt_disp, mask, seq_len: int, domain, lo: float, hi: float, tgm_over_time: bool, res):
     """The launches of one clip: res float64 [9] on the device <- coef[2] | the seven metrics."""
     dev = rt.device
-    pred = _on_device(pred_disp[:seq_len], dev, torch.float32)
-    gt = _on_device(gt_disp[:seq_len], dev, torch.float32)
-    m = None if mask is None else _on_device(mask[:seq_len], dev, torch.uint8)
+    pred = stage(pred_disp[:seq_len], dev, torch.float32)
+    gt = stage(gt_disp[:seq_len], dev, torch.float32)
+    m = None if mask is None else stage(mask[:seq_len], dev, torch.uint8)
     if pred.shape[1:] != gt.shape[1:]:
         resized = torch.empty_like(gt)
         rt.resize_bilinear_hp(pred, resized)
@@ -96,8 +72,7 @@ def eval_batch_by_data(pred, gt, device="cuda", seq_len=98, domain="depth", data
         raise ValueError(f"mask shape {tuple(mask.shape)} is not gt's {tuple(gt.shape)}")
     B = pred.shape[0]
     n = _check_clip(pred[0], gt[0], seq_len, domain, None if mask is None else mask[0])
-    dev = next((t.device for t in (pred, gt) if isinstance(t, torch.Tensor) and t.is_cuda), torch.device(device))
-    rt = _runtime(dev)
+    rt = runtime_for(device, pred, gt)
     with torch.cuda.device(rt.device):
         res = torch.empty((B, 9), dtype=torch.float64, device=rt.device)   # per item coef[2] | out[7]
         for b in range(B):
@@ -132,31 +107,10 @@ def eval_single_by_data(pred_disp, gt_disp, device="cuda", seq_len=98, domain="d
     * A kept frame whose TGM mask is empty makes TGM NaN, as in the reference.
 
     The result is read back with one synchronising copy of the seven values."""
-    if domain not in _DOMAINS:
-        raise ValueError(f"domain must be 'depth' or 'disp', got {domain!r}")
-    if pred_disp.ndim != 3 or gt_disp.ndim != 3:
-        raise ValueError(f"pred and gt must be [T, H, W], got {tuple(pred_disp.shape)} and {tuple(gt_disp.shape)}")
-    seq_len = min(int(seq_len), pred_disp.shape[0])
-    if gt_disp.shape[0] < seq_len:
-        raise ValueError(f"gt has {gt_disp.shape[0]} frames, the prediction {seq_len} after truncation")
-    if mask is not None and tuple(mask.shape) != tuple(gt_disp.shape):
-        raise ValueError(f"mask shape {tuple(mask.shape)} is not gt's {tuple(gt_disp.shape)}")
-    if seq_len == 0 or 0 in tuple(pred_disp.shape) or 0 in tuple(gt_disp.shape):
-        raise ValueError("empty clip")
-    dev = next((t.device for t in (pred_disp, gt_disp) if isinstance(t, torch.Tensor) and t.is_cuda), torch.device(device))
-    rt = _runtime(dev)
-    dev = rt.device
-    pred = _on_device(pred_disp[:seq_len], dev, torch.float32)
-    gt = _on_device(gt_disp[:seq_len], dev, torch.float32)
-    m = None if mask is None else _on_device(mask[:seq_len], dev, torch.uint8)
-    with torch.cuda.device(dev):
-        if pred.shape[1:] != gt.shape[1:]:
-            resized = torch.empty_like(gt)
-            rt.resize_bilinear_hp(pred, resized)
-            pred = resized
+    seq_len = _check_clip(pred_disp, gt_disp, seq_len, domain, mask)
+    rt = runtime_for(device, pred_disp, gt_disp)
+    with torch.cuda.device(rt.device):
         res = rt.buf("eval_out", (9,), torch.float64)   # coef[2] | out[7]
-        lo, hi = float(dataset_min_depth), float(dataset_max_depth)
-        rt.eval_fit(pred, gt, m, lo, hi, _DOMAINS[domain], res[:2])
-        rt.eval_metrics(pred, gt, m, lo, hi, _DOMAINS[domain], abi.EVAL_TGM_FRAMES if tgm_over_time else abi.EVAL_TGM_ROWS,
-                        res[:2], res[2:])
+        _clip_launches(rt, pred_disp, gt_disp, mask, seq_len, domain, float(dataset_min_depth), float(dataset_max_depth),
+                       tgm_over_time, res)
         return res[2:].cpu().tolist()

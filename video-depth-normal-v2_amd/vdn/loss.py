@@ -39,7 +39,7 @@ from typing import Dict, Tuple
 
 import torch
 
-from .normals import _on_device, _runtime_for
+from ._device import runtime_for, stage, wants_grad
 
 OUT_SLOTS = 20   # include/vdn.h: the layout of vdn_depth_loss's out
 TRIM_SLOTS = 40  # ... and of vdn_depth_loss_trimmed's: 20 + 5 * term: k | n_less | n_tied | threshold | weight
@@ -88,10 +88,10 @@ def _launch(prediction, target, mask, alpha, scales, stable_scale, device, per_f
     B, T, H, W = _check(prediction, target, mask, 4)
     if stable_scale > 0 and T < 2:
         raise ValueError("stable_scale > 0 needs T >= 2: the temporal term of a single frame divides by a count of zero")
-    rt = _runtime_for(device, prediction, target, mask)
-    p = _on_device(prediction, rt.device, torch.float32)
-    t = _on_device(target, rt.device, torch.float32)
-    m = _on_device(mask, rt.device, torch.uint8)
+    rt = runtime_for(device, prediction, target, mask)
+    p = stage(prediction, rt.device, torch.float32)
+    t = stage(target, rt.device, torch.float32)
+    m = stage(mask, rt.device, torch.uint8)
     F = B * T
     with torch.cuda.device(rt.device):
         N = TRIM_SLOTS if keep < 1.0 else OUT_SLOTS
@@ -99,10 +99,7 @@ def _launch(prediction, target, mask, alpha, scales, stable_scale, device, per_f
         stats = res[N:N + 4 * F] if per_frame else None
         counts = res[N + 4 * F:].view(torch.int64) if per_frame else None
         ss = torch.empty((B, 2), dtype=torch.float32, device=rt.device) if state else None
-        if keep < 1.0:
-            rt.depth_loss_trimmed(p, t, m, res[:N], keep, alpha, int(scales), stable_scale, ss, stats, counts)
-        else:
-            rt.depth_loss(p, t, m, res[:N], alpha, int(scales), stable_scale, ss, stats, counts)
+        rt.depth_loss(p, t, m, res[:N], alpha, int(scales), stable_scale, ss, stats, counts, keep=keep)
     return (rt, res, ss, p, t, m) if state else (rt, res)
 
 
@@ -114,8 +111,8 @@ def _backward(rt, p, t, m, alpha, scales, stable_scale, ss, res, coeff, keep: fl
     N = TRIM_SLOTS if keep < 1.0 else OUT_SLOTS
     with torch.cuda.device(rt.device):
         grad = torch.empty_like(p)
-        fn = rt.depth_loss_trimmed_backward if keep < 1.0 else rt.depth_loss_backward
-        fn(p, t, m, alpha, int(scales), stable_scale, ss, res[N:N + 4 * F], res[N + 4 * F:].view(torch.int64), res[:N], coeff, grad)
+        rt.depth_loss_backward(p, t, m, alpha, int(scales), stable_scale, ss, res[N:N + 4 * F], res[N + 4 * F:].view(torch.int64),
+                               res[:N], coeff, grad, keep=keep)
     return grad
 
 
@@ -173,9 +170,7 @@ class VideoDepthLoss(torch.nn.Module):
         values carry a grad_fn whose backward gives prediction.grad in the prediction's dtype and shape."""
         if self.ssim_loss_scale > 0:      # the attribute is public, as in the reference
             raise NotImplementedError("ssim_loss_scale > 0 is not computed")
-        if torch.is_grad_enabled() and isinstance(target, torch.Tensor) and target.requires_grad:
-            raise NotImplementedError("the gradient with respect to target is not computed; detach the target")
-        if torch.is_grad_enabled() and isinstance(prediction, torch.Tensor) and prediction.requires_grad:
+        if wants_grad(prediction, target):
             v = _DepthLossFn.apply(prediction, target, mask, self._alpha, self.scales, float(self.stable_scale), self.device,
                                    self._keep)
             return {k: v[_SLOT[k]] for k in self.keys}
@@ -205,15 +200,15 @@ def compute_scale_and_shift(prediction, target, mask, *, device="cuda"):
     """loss/loss.py:74-96 for [B, H, W] tensors -> float32 (scale [B], shift [B]) on the device: the masked least-squares
     fit of scale * prediction + shift to target per item, sums in fp64, rounded once (the fit pass of vdn_depth_loss alone)."""
     B, H, W = _check(prediction, target, mask, 3)
-    rt = _runtime_for(device, prediction, target, mask)
+    rt = runtime_for(device, prediction, target, mask)
     # An item's H * W pixels are handed to the kernel as `parts` frames of equal length (the most, up to 64, that leave 32768
     # pixels each, four for every lane of a frame's blocks): the fit sums an item's frames, and a frame is what the kernel
     # spreads over blocks.
     n = H * W
     parts = next((c for c in range(64, 1, -1) if n % c == 0 and n // c >= 32768 and B * c <= 65535), 1)
-    p = _on_device(prediction, rt.device, torch.float32).view(B, parts, 1, n // parts)
-    t = _on_device(target, rt.device, torch.float32).view(B, parts, 1, n // parts)
-    m = _on_device(mask, rt.device, torch.uint8).view(B, parts, 1, n // parts)
+    p = stage(prediction, rt.device, torch.float32).view(B, parts, 1, n // parts)
+    t = stage(target, rt.device, torch.float32).view(B, parts, 1, n // parts)
+    m = stage(mask, rt.device, torch.uint8).view(B, parts, 1, n // parts)
     with torch.cuda.device(rt.device):
         ss = torch.empty((B, 2), dtype=torch.float32, device=rt.device)
         rt.depth_loss(p, t, m, None, scale_shift=ss)

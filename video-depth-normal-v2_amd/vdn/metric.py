@@ -35,7 +35,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .normals import _on_device, _runtime_for
+from ._device import runtime_for, stage, wants_grad
 
 KEYS = ("d1", "d2", "d3", "abs_rel", "sq_rel", "rmse", "rmse_log", "log10", "silog")   # eval_depth's, in its order
 ROW = 1 + len(KEYS)   # a row of eval_depth_batch: n, then the nine
@@ -79,7 +79,7 @@ def _mask_u8(mask: torch.Tensor, device: torch.device) -> torch.Tensor:
     """uint8 whose bytes equal 1 exactly where `mask == 1`: bool and uint8 tensors on the device in place."""
     if mask.dtype not in (torch.bool, torch.uint8):
         mask = mask == 1
-    return _on_device(mask, device, torch.uint8)
+    return stage(mask, device, torch.uint8)
 
 
 def eval_depth_batch(pred, depth, valid_mask, *, min_depth, max_depth, device="cuda") -> torch.Tensor:
@@ -97,9 +97,9 @@ def eval_depth_batch(pred, depth, valid_mask, *, min_depth, max_depth, device="c
     bounds = _bounds(min_depth, max_depth)
     if bounds is None:
         raise ValueError("min_depth and max_depth are required")
-    rt = _runtime_for(device, pred, depth, valid_mask)
-    p = _on_device(pred, rt.device, torch.float32)
-    d = _on_device(depth, rt.device, torch.float32)
+    rt = runtime_for(device, pred, depth, valid_mask)
+    p = stage(pred, rt.device, torch.float32)
+    d = stage(depth, rt.device, torch.float32)
     m = _mask_u8(valid_mask, rt.device)
     with torch.cuda.device(rt.device):
         out = torch.empty((d.shape[0], ROW), dtype=torch.float64, device=rt.device)
@@ -112,9 +112,9 @@ def eval_depth(pred, target, *, device="cuda") -> Dict[str, float]:
     depth[valid_mask]), every element kept -> {'d1', 'd2', 'd3', 'abs_rel', 'sq_rel', 'rmse', 'rmse_log', 'log10', 'silog'} as
     Python floats, read with one synchronising copy."""
     _same(pred, target)
-    rt = _runtime_for(device, pred, target)
-    p = _on_device(pred, rt.device, torch.float32).view(1, 1, -1)
-    t = _on_device(target, rt.device, torch.float32).view(1, 1, -1)
+    rt = runtime_for(device, pred, target)
+    p = stage(pred, rt.device, torch.float32).view(1, 1, -1)
+    t = stage(target, rt.device, torch.float32).view(1, 1, -1)
     with torch.cuda.device(rt.device):
         out = torch.empty((1, ROW), dtype=torch.float64, device=rt.device)
         rt.metric_eval(p, t, None, out)
@@ -125,9 +125,9 @@ def _forward(pred, target, mask, lambd, bounds, device):
     """-> (runtime, state float64 [4] = loss | n | sum dl | sum dl^2 in a tensor of its own, and the float32 prediction, target
     and uint8 mask the kernels read)."""
     _same(pred, target, mask)
-    rt = _runtime_for(device, pred, target, mask)
-    p = _on_device(pred, rt.device, torch.float32)
-    t = _on_device(target, rt.device, torch.float32)
+    rt = runtime_for(device, pred, target, mask)
+    p = stage(pred, rt.device, torch.float32)
+    t = stage(target, rt.device, torch.float32)
     m = _mask_u8(mask, rt.device)
     with torch.cuda.device(rt.device):
         state = torch.empty(4, dtype=torch.float64, device=rt.device)
@@ -179,9 +179,7 @@ class SiLogLoss(torch.nn.Module):
 
     def _run(self, pred, target, mask, bounds) -> torch.Tensor:
         lambd = _lambd(self.lambd)   # the attribute is public, as in the reference
-        if torch.is_grad_enabled() and isinstance(target, torch.Tensor) and target.requires_grad:
-            raise NotImplementedError("the gradient with respect to target is not computed; detach the target")
-        if torch.is_grad_enabled() and isinstance(pred, torch.Tensor) and pred.requires_grad:
+        if wants_grad(pred, target):
             return _SiLogFn.apply(pred, target, mask, lambd, bounds, self.device)
         rt, state, *_ = _forward(pred, target, mask, lambd, bounds, self.device)
         with torch.cuda.device(rt.device):

@@ -27,38 +27,10 @@ cosine and its gradient are fp64 on the device, where the reference computes in 
 order, so two runs give the same bits."""
 from __future__ import annotations
 
-from typing import Dict, Optional
-
 import torch
 
 from . import _abi as abi
-from .runtime import Runtime
-
-_RUNTIMES: Dict[torch.device, Runtime] = {}
-
-
-def _runtime(device: torch.device) -> Runtime:
-    if device.type != "cuda":
-        raise abi.VdnError("vdn.normals runs on an MI355X ('cuda' device under ROCm); there is no CPU path")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if device not in _RUNTIMES:
-        _RUNTIMES[device] = Runtime(device)
-    return _RUNTIMES[device]
-
-
-def _runtime_for(device, *tensors) -> Runtime:
-    return _runtime(next((t.device for t in tensors if t is not None and t.is_cuda), torch.device(device)))
-
-
-def _on_device(t: torch.Tensor, device: torch.device, dtype: torch.dtype) -> torch.Tensor:
-    """A CUDA tensor of the right type is used in place (made contiguous if it is a view); anything else is copied once."""
-    if dtype == torch.uint8:
-        if t.dtype == torch.bool and t.is_cuda:
-            return t.contiguous().view(torch.uint8)
-        if t.dtype != torch.uint8:
-            t = t != 0
-    return t.to(device=t.device if t.is_cuda else device, dtype=dtype).contiguous()
+from ._device import runtime_for as _runtime_for, stage, wants_grad
 
 
 def _check_size(H: int, W: int):
@@ -82,7 +54,7 @@ def sobel_ix_iy(img: torch.Tensor, normalize_kernel: bool = True, *, device="cud
     reference's pad raises."""
     B, S, Y, X = _check_img(img)
     rt = _runtime_for(device, img)
-    d = _on_device(img, rt.device, torch.float32).view(B * S, Y, X)
+    d = stage(img, rt.device, torch.float32).view(B * S, Y, X)
     with torch.cuda.device(rt.device):
         ix, iy = torch.empty_like(d), torch.empty_like(d)
         rt.sobel_ix_iy(d, ix, iy, normalize_kernel)
@@ -96,7 +68,7 @@ def normal_vector(img: torch.Tensor, normalize_kernel: bool = True, scale_xy: fl
     arithmetic does."""
     B, S, Y, X = _check_img(img)
     rt = _runtime_for(device, img)
-    d = _on_device(img, rt.device, torch.float32).view(B * S, Y, X)
+    d = stage(img, rt.device, torch.float32).view(B * S, Y, X)
     with torch.cuda.device(rt.device):
         out = torch.empty((B * S, 3, Y, X), dtype=torch.float32, device=rt.device)
         rt.normal_vector(d, out, normalize_kernel, float(scale_xy), float(scale_z), float(eps))
@@ -132,9 +104,9 @@ def _launch(prediction, target, mask, target_is_depth: bool, device):
     B, T, H, W = _check_loss_shapes(prediction, target, mask, target_is_depth)
     rt = _runtime_for(device, prediction, target, mask)
     F = B * T
-    p = _on_device(prediction, rt.device, torch.float32).view(F, 3, H, W)
-    t = _on_device(target, rt.device, torch.float32).view((F, H, W) if target_is_depth else (F, 3, H, W))
-    m = None if mask is None else _on_device(mask, rt.device, torch.uint8).view(F, H, W)
+    p = stage(prediction, rt.device, torch.float32).view(F, 3, H, W)
+    t = stage(target, rt.device, torch.float32).view((F, H, W) if target_is_depth else (F, 3, H, W))
+    m = None if mask is None else stage(mask, rt.device, torch.uint8).view(F, H, W)
     with torch.cuda.device(rt.device):
         out = rt.buf("normal_out", (2,), torch.float64)
         rt.normal_eval(p, t, m, out)
@@ -199,16 +171,14 @@ class VideoNormalLoss(torch.nn.Module):
             raise ValueError("empty input")
         _check_size(H, W)
         rt = _runtime_for(self.device, mask)
-        m = _on_device(mask, rt.device, torch.uint8).view(B * T, H, W)
+        m = stage(mask, rt.device, torch.uint8).view(B * T, H, W)
         with torch.cuda.device(rt.device):
             out = torch.empty_like(m)
             rt.erode_mask3(m, out)
         return out.view(B, T, H, W).view(torch.bool)
 
     def _value(self, prediction, target, mask, target_is_depth: bool, name: str):
-        if torch.is_grad_enabled() and isinstance(target, torch.Tensor) and target.requires_grad:
-            raise NotImplementedError(f"the gradient with respect to {name} is not computed; detach the {name}")
-        if torch.is_grad_enabled() and isinstance(prediction, torch.Tensor) and prediction.requires_grad:
+        if wants_grad(prediction, target, name):
             return {"normal_loss": _NormalLossFn.apply(prediction, target, mask, target_is_depth, self.device)}
         rt, out, _, _, _ = _launch(prediction, target, mask, target_is_depth, self.device)
         with torch.cuda.device(rt.device):
@@ -234,9 +204,9 @@ def _loss(prediction, target, mask, target_is_depth: bool, per_frame: bool, devi
     B, T, H, W = _check_loss_shapes(prediction, target, mask, target_is_depth)
     rt = _runtime_for(device, prediction, target, mask)
     F = B * T
-    p = _on_device(prediction, rt.device, torch.float32).view(F, 3, H, W)
-    t = _on_device(target, rt.device, torch.float32).view((F, H, W) if target_is_depth else (F, 3, H, W))
-    m = None if mask is None else _on_device(mask, rt.device, torch.uint8).view(F, H, W)
+    p = stage(prediction, rt.device, torch.float32).view(F, 3, H, W)
+    t = stage(target, rt.device, torch.float32).view((F, H, W) if target_is_depth else (F, 3, H, W))
+    m = None if mask is None else stage(mask, rt.device, torch.uint8).view(F, H, W)
     with torch.cuda.device(rt.device):
         res = rt.buf("normal_res", (2 + 2 * F,), torch.float64)   # out[2] | frame sums [F] | frame counts [F] (int64)
         sums, counts = res[2:2 + F], res[2 + F:].view(torch.int64)

@@ -16,7 +16,7 @@ from typing import Tuple
 
 import torch
 
-from .normals import _on_device, _runtime_for
+from ._device import runtime_for, stage
 
 
 def depth_to_points(depth, rgb_u8, fx: float, fy: float, device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
@@ -32,9 +32,9 @@ def depth_to_points(depth, rgb_u8, fx: float, fy: float, device="cuda") -> Tuple
     fx, fy = float(fx), float(fy)
     if not (fx > 0 or fx < 0) or not (fy > 0 or fy < 0):
         raise ValueError(f"fx={fx!r}, fy={fy!r}: a focal length is zero or NaN")
-    rt = _runtime_for(device, depth, rgb_u8)
-    depth = _on_device(depth, rt.device, torch.float32)
-    rgb_u8 = _on_device(rgb_u8, rt.device, torch.uint8)
+    rt = runtime_for(device, depth, rgb_u8)
+    depth = stage(depth, rt.device, torch.float32)
+    rgb_u8 = stage(rgb_u8, rt.device, torch.uint8)
     points = torch.empty((h * w, 3), dtype=torch.float64, device=rt.device)
     colors = torch.empty((h * w, 3), dtype=torch.float64, device=rt.device)
     with torch.cuda.device(rt.device):

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _abi as abi
-from .normals import _on_device, _runtime_for
+from ._device import runtime_for, stage
 
 _EPS = float(np.float32(1e-8))
 
@@ -44,8 +44,8 @@ def _shape(t, name: str, rank: int, channels: Optional[int] = None) -> tuple:
 
 def _rgb(rgb_batch, normalize: bool, device) -> torch.Tensor:
     B, S, _, H, W = _shape(rgb_batch, "rgb_batch", 5, 3)
-    rt = _runtime_for(device, rgb_batch)
-    x = _on_device(rgb_batch, rt.device, torch.float32).view(B * S, 3, H, W)
+    rt = runtime_for(device, rgb_batch)
+    x = stage(rgb_batch, rt.device, torch.float32).view(B * S, 3, H, W)
     with torch.cuda.device(rt.device):
         out = torch.empty_like(x)
         rt.prep_rgb(x, out, normalize)
@@ -66,9 +66,9 @@ def preprocess_rgb_viz_sequences(rgb_batch, *, device="cuda") -> torch.Tensor:
 def _depth(x, masks, shape4: tuple, reciprocal: bool, clamp0: bool, normalize: bool, device, minmax: bool = False):
     """x and masks (or None) hold B * S * H * W elements in [B, S, H, W] order -> float32 [B, S, H, W] (and lo / hi [B, 2])."""
     B = shape4[0]
-    rt = _runtime_for(device, x, masks)
-    d = _on_device(x, rt.device, torch.float32).view(B, -1)
-    m = None if masks is None or not normalize else _on_device(masks, rt.device, torch.uint8).view(B, -1)
+    rt = runtime_for(device, x, masks)
+    d = stage(x, rt.device, torch.float32).view(B, -1)
+    m = None if masks is None or not normalize else stage(masks, rt.device, torch.uint8).view(B, -1)
     with torch.cuda.device(rt.device):
         out = torch.empty_like(d)
         mm = torch.empty((B, 2), dtype=torch.float32, device=rt.device) if minmax else None

@@ -81,6 +81,45 @@ def _hl(t):
     return (t.hi, None) if isinstance(t, KT) else (t, None)
 
 
+_f32, _f64, _u8, _i64 = torch.float32, torch.float64, torch.uint8, torch.int64
+
+
+def _fits(got, shape) -> bool:
+    """Is `got` the `shape`, a None entry of which leaves that dimension free?"""
+    if len(got) != len(shape):
+        return False
+    for w, g in zip(shape, got):
+        if w is not None and w != g:
+            return False
+    return True
+
+
+def checked_ptr(what: str, t, device: torch.device, dtype, shape=None, count=None, optional: bool = False) -> Optional[int]:
+    """The contract of one tensor operand, stated where it becomes a pointer: `t` is a contiguous tensor on `device` of `dtype`
+    (one dtype, or a tuple of admissible ones), with exactly `shape` (a None entry leaves that dimension free; an int is a rank,
+    every dimension free) and / or `count` elements -> t.data_ptr(). None passes for an `optional` operand. Anything else raises
+    VdnError before a pointer is taken; `what` names the wrapper and the operand. The C side sees only the pointer and the
+    caller's counts, so this is the last check between a wrong tensor and an out-of-bounds access, and it raises rather than
+    asserts: python -O keeps it."""
+    if t is None and optional:
+        return None
+    if (isinstance(t, torch.Tensor) and (t.dtype == dtype or (type(dtype) is tuple and t.dtype in dtype)) and t.is_contiguous()
+            and (t.device == device or (device.index is None and t.device.type == device.type))
+            and (shape is None or (t.dim() == shape if type(shape) is int else t.shape == shape or _fits(t.shape, shape)))
+            and (count is None or t.numel() == count)):
+        return t.data_ptr()
+    want = " or ".join(str(d) for d in (dtype if type(dtype) is tuple else (dtype,))) + " tensor"
+    if shape is not None:
+        want += " [" + ", ".join("*" if s is None else str(int(s)) for s in ((None,) * shape if type(shape) is int else shape)) + "]"
+    if count is not None:
+        want += f" of {int(count)} elements"
+    if isinstance(t, torch.Tensor):
+        got = f"{t.dtype} {list(t.shape)} on {t.device}" + ("" if t.is_contiguous() else ", not contiguous")
+    else:
+        got = type(t).__name__
+    raise abi.VdnError(f"{what}: expected a contiguous {want} on {device}, got {got}")
+
+
 class Runtime:
     def __init__(self, device: torch.device, half: torch.dtype = torch.float16, split: bool = False):
         if device.type != "cuda":
@@ -171,6 +210,10 @@ class Runtime:
 
     def workspace_bytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self._bufs.values())
+
+    def _ws(self, name: str, nbytes: int) -> torch.Tensor:
+        """The arena's workspace `name`: at least nbytes, rounded up to whole 8-byte words."""
+        return self.buf(name, ((nbytes + 7) // 8,), torch.float64)
 
     # ------------------------------------------------------------------ launch
     def _launch(self, fn, *args, tag: Optional[str] = None, flop: float = 0.0):
@@ -340,206 +383,178 @@ class Runtime:
         self._launch(abi.lib.vdn_upsample_bilinear, self.dt, x.data_ptr(), xl, y.data_ptr(), yl, B, IH, IW, OH, OW, Cn)
 
     def upsample_f32(self, x, y, B: int, IH: int, IW: int, OH: int, OW: int, relu: bool = False):
-        self._launch(abi.lib.vdn_upsample_bilinear_f32, x.data_ptr(), y.data_ptr(), B, IH, IW, OH, OW, int(relu))
+        dev = self.device
+        self._launch(abi.lib.vdn_upsample_bilinear_f32, checked_ptr("upsample_f32: x", x, dev, _f32, count=B * IH * IW),
+                     checked_ptr("upsample_f32: y", y, dev, _f32, count=B * OH * OW), B, IH, IW, OH, OW, int(relu))
 
     def stitch_fit(self, pred: torch.Tensor, target: torch.Tensor, coef: torch.Tensor):
         """coef[0:2] <- least-squares (scale, shift) of pred onto target (utils/util.py:40-62), on the device."""
-        ws = self.buf("stitch_ws", (abi.lib.vdn_stitch_workspace_bytes() // 8,), torch.float64)
-        assert pred.is_contiguous() and target.is_contiguous() and pred.numel() == target.numel()
-        self._launch(abi.lib.vdn_stitch_fit, pred.data_ptr(), target.data_ptr(), pred.numel(), ws.data_ptr(), coef.data_ptr())
+        dev = self.device
+        p = checked_ptr("stitch_fit: pred", pred, dev, _f32)
+        n = pred.numel()
+        self._launch(abi.lib.vdn_stitch_fit, p, checked_ptr("stitch_fit: target", target, dev, _f32, count=n), n,
+                     self._ws("stitch_ws", abi.lib.vdn_stitch_workspace_bytes()).data_ptr(),
+                     checked_ptr("stitch_fit: coef", coef, dev, _f32, count=2))
 
     def stitch_apply(self, window: torch.Tensor, coef: torch.Tensor, out_tail: torch.Tensor, out_new: torch.Tensor,
                      ref1: torch.Tensor, align_len: int, overlap: int, ref_frame: int):
-        T, hw = window.shape[0], window[0].numel()
-        assert window.is_contiguous() and out_tail.is_contiguous() and out_new.is_contiguous() and ref1.is_contiguous()
-        assert out_tail.shape[0] == overlap - align_len and out_new.shape[0] == T - overlap
-        self._launch(abi.lib.vdn_stitch_apply, window.data_ptr(), coef.data_ptr(), out_tail.data_ptr(), out_new.data_ptr(),
-                     ref1.data_ptr(), hw, T, align_len, overlap, ref_frame)
+        """window f32 [T, ...] -> out_tail [overlap - align_len, ...], out_new [T - overlap, ...] and ref1 [...], the frame
+        `ref_frame` (include/vdn.h vdn_stitch_apply); coef f32 [2] is what stitch_fit wrote."""
+        dev = self.device
+        w = checked_ptr("stitch_apply: window", window, dev, _f32)
+        T, frame = window.shape[0], tuple(window.shape[1:])
+        self._launch(abi.lib.vdn_stitch_apply, w, checked_ptr("stitch_apply: coef", coef, dev, _f32, count=2),
+                     checked_ptr("stitch_apply: out_tail", out_tail, dev, _f32, (overlap - align_len,) + frame),
+                     checked_ptr("stitch_apply: out_new", out_new, dev, _f32, (T - overlap,) + frame),
+                     checked_ptr("stitch_apply: ref1", ref1, dev, _f32, frame),
+                     window[0].numel(), T, align_len, overlap, ref_frame)
 
-    def _eval_args(self, pred, gt, mask):
-        T = pred.shape[0]
-        for t in (pred, gt):
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.dim() == 3 and t.shape == pred.shape
-        if mask is not None:
-            assert mask.is_contiguous() and mask.dtype in (torch.uint8, torch.bool) and mask.shape == pred.shape
-        ws = self.buf("eval_ws", (abi.lib.vdn_eval_workspace_bytes(T) // 8,), torch.float64)
-        return T, ws
+    def _eval_args(self, what: str, pred, gt, mask):
+        """-> the pointers of f32 pred, gt [T, H, W], the u8 or bool mask [T, H, W] (or None) and the clip's workspace."""
+        p = checked_ptr(what + ": pred", pred, self.device, _f32, 3)
+        return (p, checked_ptr(what + ": gt", gt, self.device, _f32, pred.shape),
+                checked_ptr(what + ": mask", mask, self.device, (_u8, torch.bool), pred.shape, optional=True),
+                self._ws("eval_ws", abi.lib.vdn_eval_workspace_bytes(pred.shape[0])).data_ptr())
 
     def eval_fit(self, pred, gt, mask, dmin: float, dmax: float, domain: int, coef: torch.Tensor):
         """coef[0:2] (float64) <- masked least-squares (scale, shift) of the clip evaluation (include/vdn.h vdn_eval_fit)."""
-        T, ws = self._eval_args(pred, gt, mask)
-        assert coef.dtype == torch.float64 and coef.numel() >= 2
-        self._launch(abi.lib.vdn_eval_fit, pred.data_ptr(), gt.data_ptr(), self._p(mask), T, pred[0].numel(), dmin, dmax,
-                     domain, ws.data_ptr(), coef.data_ptr())
+        p, g, m, ws = self._eval_args("eval_fit", pred, gt, mask)
+        self._launch(abi.lib.vdn_eval_fit, p, g, m, pred.shape[0], pred[0].numel(), dmin, dmax, domain, ws,
+                     checked_ptr("eval_fit: coef", coef, self.device, _f64, count=2))
 
     def eval_metrics(self, pred, gt, mask, dmin: float, dmax: float, domain: int, tgm: int, coef: torch.Tensor,
                      out: torch.Tensor):
         """out[0:7] (float64) <- the seven clip metrics; follows eval_fit on the same arguments (vdn_eval_metrics)."""
-        T, ws = self._eval_args(pred, gt, mask)
-        assert coef.dtype == torch.float64 and out.dtype == torch.float64 and out.numel() >= 7
-        self._launch(abi.lib.vdn_eval_metrics, pred.data_ptr(), gt.data_ptr(), self._p(mask), T, pred.shape[1], pred.shape[2],
-                     dmin, dmax, domain, tgm, coef.data_ptr(), ws.data_ptr(), out.data_ptr())
+        p, g, m, ws = self._eval_args("eval_metrics", pred, gt, mask)
+        self._launch(abi.lib.vdn_eval_metrics, p, g, m, pred.shape[0], pred.shape[1], pred.shape[2], dmin, dmax, domain, tgm,
+                     checked_ptr("eval_metrics: coef", coef, self.device, _f64, count=2), ws,
+                     checked_ptr("eval_metrics: out", out, self.device, _f64, count=7))
 
     def resize_bilinear_hp(self, x: torch.Tensor, out: torch.Tensor):
         """out [T, OH, OW] <- half-pixel (align_corners=False) bilinear resize of f32 x [T, IH, IW]."""
-        assert x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype == torch.float32
-        assert x.dim() == 3 and out.dim() == 3 and x.shape[0] == out.shape[0]
-        self._launch(abi.lib.vdn_resize_bilinear_hp, x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], x.shape[2],
-                     out.shape[1], out.shape[2])
-
-    @staticmethod
-    def _frames3(t: torch.Tensor, dtype=torch.float32):
-        assert t.is_contiguous() and t.dtype == dtype and t.dim() == 3, (t.shape, t.dtype)
-        return t.shape
+        px = checked_ptr("resize_bilinear_hp: x", x, self.device, _f32, 3)
+        po = checked_ptr("resize_bilinear_hp: out", out, self.device, _f32, (x.shape[0], None, None))
+        self._launch(abi.lib.vdn_resize_bilinear_hp, px, po, x.shape[0], x.shape[1], x.shape[2], out.shape[1], out.shape[2])
 
     def sobel_ix_iy(self, depth: torch.Tensor, ix: torch.Tensor, iy: torch.Tensor, normalize_kernel: bool = True):
         """ix, iy f32 [F, H, W] <- Sobel (/ 8) of the reflect-padded f32 depth [F, H, W] (include/vdn.h vdn_sobel_ix_iy)."""
-        F, H, W = self._frames3(depth)
-        assert self._frames3(ix) == depth.shape and self._frames3(iy) == depth.shape
-        self._launch(abi.lib.vdn_sobel_ix_iy, depth.data_ptr(), ix.data_ptr(), iy.data_ptr(), F, H, W, int(normalize_kernel))
+        dev = self.device
+        d = checked_ptr("sobel_ix_iy: depth", depth, dev, _f32, 3)
+        F, H, W = depth.shape
+        self._launch(abi.lib.vdn_sobel_ix_iy, d, checked_ptr("sobel_ix_iy: ix", ix, dev, _f32, depth.shape),
+                     checked_ptr("sobel_ix_iy: iy", iy, dev, _f32, depth.shape),
+                     F, H, W, int(normalize_kernel))
 
     def normal_vector(self, depth: torch.Tensor, out: torch.Tensor, normalize_kernel: bool = True, scale_xy: float = 1.0,
                       scale_z: float = 1.0, eps: float = 1e-8):
         """out f32 [F, 3, H, W] <- unit normals of f32 depth [F, H, W] (vdn_normal_vector)."""
-        F, H, W = self._frames3(depth)
-        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (F, 3, H, W)
-        self._launch(abi.lib.vdn_normal_vector, depth.data_ptr(), out.data_ptr(), F, H, W, int(normalize_kernel), scale_xy,
-                     scale_z, eps)
+        d = checked_ptr("normal_vector: depth", depth, self.device, _f32, 3)
+        F, H, W = depth.shape
+        self._launch(abi.lib.vdn_normal_vector, d, checked_ptr("normal_vector: out", out, self.device, _f32, (F, 3, H, W)), F, H, W,
+                     int(normalize_kernel), scale_xy, scale_z, eps)
 
     def erode_mask3(self, mask: torch.Tensor, out: torch.Tensor):
         """out u8 [F, H, W] <- 1 where u8 mask and its 3 x 3 neighbours inside the image are non-zero (vdn_erode_mask3)."""
-        F, H, W = self._frames3(mask, torch.uint8)
-        assert self._frames3(out, torch.uint8) == mask.shape
-        self._launch(abi.lib.vdn_erode_mask3, mask.data_ptr(), out.data_ptr(), F, H, W)
+        m = checked_ptr("erode_mask3: mask", mask, self.device, _u8, 3)
+        F, H, W = mask.shape
+        self._launch(abi.lib.vdn_erode_mask3, m, checked_ptr("erode_mask3: out", out, self.device, _u8, mask.shape), F, H, W)
+
+    def _normal_args(self, what: str, pred, target, mask):
+        """-> F, H, W and the pointers of f32 pred [F, 3, H, W], the f32 target, normals [F, 3, H, W] or a depth map [F, H, W],
+        and the u8 mask [F, H, W] (or None)."""
+        p = checked_ptr(what + ": pred", pred, self.device, _f32, (None, 3, None, None))
+        F, _, H, W = pred.shape
+        t = checked_ptr(what + ": target", target, self.device, _f32, (F, H, W) if getattr(target, "ndim", 4) == 3 else (F, 3, H, W))
+        return F, H, W, p, t, checked_ptr(what + ": mask", mask, self.device, _u8, (F, H, W), optional=True)
 
     def normal_eval(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Tensor,
                     frame_sums: Optional[torch.Tensor] = None, frame_counts: Optional[torch.Tensor] = None):
         """out[0:2] (float64) <- (1 - masked mean cosine, kept pixels) of pred f32 [F, 3, H, W] against target: normals
         [F, 3, H, W] or a depth map [F, H, W], whose normals are made on the fly (vdn_normal_eval)."""
-        F, _, H, W = pred.shape
-        assert pred.is_contiguous() and pred.dtype == torch.float32 and pred.shape[1] == 3
-        assert target.is_contiguous() and target.dtype == torch.float32
-        assert tuple(target.shape) in ((F, 3, H, W), (F, H, W)), (pred.shape, target.shape)
-        if mask is not None:
-            assert self._frames3(mask, torch.uint8) == (F, H, W)
-        assert out.dtype == torch.float64 and out.numel() >= 2
-        assert frame_sums is None or (frame_sums.dtype == torch.float64 and frame_sums.numel() == F)
-        assert frame_counts is None or (frame_counts.dtype == torch.int64 and frame_counts.numel() == F)
-        ws = self.buf("normal_eval_ws", (abi.lib.vdn_normal_eval_workspace_bytes(F) // 8,), torch.float64)
-        self._launch(abi.lib.vdn_normal_eval, pred.data_ptr(), target.data_ptr(), int(target.dim() == 3), self._p(mask), F, H, W,
-                     ws.data_ptr(), self._p(frame_sums), self._p(frame_counts), out.data_ptr())
+        dev = self.device
+        F, H, W, p, t, m = self._normal_args("normal_eval", pred, target, mask)
+        o = checked_ptr("normal_eval: out", out, dev, _f64, count=2)
+        fs = checked_ptr("normal_eval: frame_sums", frame_sums, dev, _f64, count=F, optional=True)
+        fc = checked_ptr("normal_eval: frame_counts", frame_counts, dev, _i64, count=F, optional=True)
+        ws = self._ws("normal_eval_ws", abi.lib.vdn_normal_eval_workspace_bytes(F))
+        self._launch(abi.lib.vdn_normal_eval, p, t, int(target.dim() == 3), m, F, H, W, ws.data_ptr(), fs, fc, o)
 
     def normal_loss_backward(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], count: torch.Tensor,
                              coeff: torch.Tensor, grad: torch.Tensor):
         """grad f32 [F, 3, H, W] <- coeff * d normal_loss / d pred (vdn_normal_loss_backward). pred, target and mask as for
         normal_eval; count float64 [1] is the out[1] normal_eval wrote for them and coeff float64 [1], both on the device."""
-        F, _, H, W = pred.shape
-        for t in (pred, grad):
-            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (F, 3, H, W), t.shape
-        assert target.is_contiguous() and target.dtype == torch.float32
-        assert tuple(target.shape) in ((F, 3, H, W), (F, H, W)), (pred.shape, target.shape)
-        if mask is not None:
-            assert self._frames3(mask, torch.uint8) == (F, H, W)
-        for t in (count, coeff):
-            assert t.dtype == torch.float64 and t.numel() == 1 and t.is_cuda
-        self._launch(abi.lib.vdn_normal_loss_backward, pred.data_ptr(), target.data_ptr(), int(target.dim() == 3), self._p(mask),
-                     F, H, W, count.data_ptr(), coeff.data_ptr(), grad.data_ptr())
+        dev = self.device
+        F, H, W, p, t, m = self._normal_args("normal_loss_backward", pred, target, mask)
+        self._launch(abi.lib.vdn_normal_loss_backward, p, t, int(target.dim() == 3), m, F, H, W,
+                     checked_ptr("normal_loss_backward: count", count, dev, _f64, count=1),
+                     checked_ptr("normal_loss_backward: coeff", coeff, dev, _f64, count=1),
+                     checked_ptr("normal_loss_backward: grad", grad, dev, _f32, pred.shape))
+
+    def _depth_loss_args(self, what: str, keep: float, prediction, target, mask, out, scale_shift, frame_stats, frame_counts,
+                         optional: bool):
+        """-> B, T, H, W, whether keep < 1 selects the trimmed criterion, and the pointers of f32 prediction and target and the u8
+        mask [B, T, H, W], out f64 [20] (trimmed: [40]), scale_shift f32 [B, 2], frame_stats f64 [B T, 4] and frame_counts
+        i64 [B T]; `optional`: the last four may be None (the forward)."""
+        dev = self.device
+        p = checked_ptr(what + ": prediction", prediction, dev, _f32, 4)
+        B, T, H, W = shape = prediction.shape
+        trimmed = keep < 1.0
+        return (B, T, H, W, trimmed, p, checked_ptr(what + ": target", target, dev, _f32, shape), checked_ptr(what + ": mask", mask, dev, _u8, shape),
+                checked_ptr(what + ": out", out, dev, _f64, count=40 if trimmed else 20, optional=optional),
+                checked_ptr(what + ": scale_shift", scale_shift, dev, _f32, count=2 * B, optional=optional),
+                checked_ptr(what + ": frame_stats", frame_stats, dev, _f64, count=4 * B * T, optional=optional),
+                checked_ptr(what + ": frame_counts", frame_counts, dev, _i64, count=B * T, optional=optional))
 
     def depth_loss(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor],
                    alpha: float = 0.5, scales: int = 4, stable_scale: float = 10.0, scale_shift: Optional[torch.Tensor] = None,
-                   frame_stats: Optional[torch.Tensor] = None, frame_counts: Optional[torch.Tensor] = None):
+                   frame_stats: Optional[torch.Tensor] = None, frame_counts: Optional[torch.Tensor] = None, keep: float = 1.0):
         """out[0:20] (float64) <- VideoDepthLoss of f32 prediction, target [B, T, H, W] under the u8 mask (vdn_depth_loss;
-        include/vdn.h has the layout). out None: the fit alone, into scale_shift f32 [B, 2]."""
-        B, T, H, W = prediction.shape
-        for t in (prediction, target):
-            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, T, H, W), t.shape
-        assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, T, H, W)
-        assert out is not None or scale_shift is not None
-        assert out is None or (out.dtype == torch.float64 and out.numel() >= 20 and out.is_contiguous())
-        assert scale_shift is None or (scale_shift.dtype == torch.float32 and scale_shift.numel() == 2 * B and scale_shift.is_contiguous())
-        assert frame_stats is None or (frame_stats.dtype == torch.float64 and frame_stats.numel() == 4 * B * T and frame_stats.is_contiguous())
-        assert frame_counts is None or (frame_counts.dtype == torch.int64 and frame_counts.numel() == B * T and frame_counts.is_contiguous())
-        ws = self.buf("depth_loss_ws", (abi.lib.vdn_depth_loss_workspace_bytes(B, T) // 8,), torch.float64)
-        self._launch(abi.lib.vdn_depth_loss, prediction.data_ptr(), target.data_ptr(), mask.data_ptr(), B, T, H, W, float(alpha),
-                     int(scales), float(stable_scale), ws.data_ptr(), self._p(scale_shift), self._p(frame_stats),
-                     self._p(frame_counts), self._p(out))
+        include/vdn.h has the layout). out None: the fit alone, into scale_shift f32 [B, 2]. keep = 1 - trim in (0, 1): the
+        trimmed criterion and its out[0:40] (vdn_depth_loss_trimmed)."""
+        B, T, H, W, trimmed, p, t, m, o, ss, fs, fc = self._depth_loss_args("depth_loss", keep, prediction, target, mask, out,
+                                                                            scale_shift, frame_stats, frame_counts, True)
+        if out is None and (trimmed or scale_shift is None):
+            raise abi.VdnError("depth_loss: out may be None only for the untrimmed fit alone, which writes scale_shift")
+        if trimmed:
+            ws = self._ws("depth_loss_trimmed_ws", abi.lib.vdn_depth_loss_trimmed_workspace_bytes(B, T))
+            entry, extra = abi.lib.vdn_depth_loss_trimmed, (float(keep),)
+        else:
+            ws = self._ws("depth_loss_ws", abi.lib.vdn_depth_loss_workspace_bytes(B, T))
+            entry, extra = abi.lib.vdn_depth_loss, ()
+        self._launch(entry, p, t, m, B, T, H, W, float(alpha), int(scales), float(stable_scale), *extra, ws.data_ptr(), ss, fs, fc, o)
 
     def depth_loss_backward(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, alpha: float, scales: int,
                             stable_scale: float, scale_shift: torch.Tensor, frame_stats: torch.Tensor, frame_counts: torch.Tensor,
-                            out: torch.Tensor, coeff: torch.Tensor, grad: torch.Tensor):
+                            out: torch.Tensor, coeff: torch.Tensor, grad: torch.Tensor, keep: float = 1.0):
         """grad f32 [B, T, H, W] <- the gradient of c_sp * spatial + c_st * stable + c_ar * absRel with respect to the f32
-        prediction (vdn_depth_loss_backward), coeff f32 [3] = {c_sp, c_st, c_ar} on the device. scale_shift, frame_stats,
-        frame_counts and out are what depth_loss wrote for the same inputs and arguments."""
-        B, T, H, W = prediction.shape
-        for t in (prediction, target, grad):
-            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, T, H, W), t.shape
-        assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, T, H, W)
-        assert scale_shift.dtype == torch.float32 and scale_shift.numel() == 2 * B and scale_shift.is_contiguous()
-        assert frame_stats.dtype == torch.float64 and frame_stats.numel() == 4 * B * T and frame_stats.is_contiguous()
-        assert frame_counts.dtype == torch.int64 and frame_counts.numel() == B * T and frame_counts.is_contiguous()
-        assert out.dtype == torch.float64 and out.numel() >= 20 and out.is_contiguous()
-        assert coeff.dtype == torch.float32 and coeff.numel() == 3 and coeff.is_contiguous()
-        ws = self.buf("depth_loss_backward_ws", (abi.lib.vdn_depth_loss_backward_workspace_bytes(B, T, H, W) // 8,), torch.float64)
-        self._launch(abi.lib.vdn_depth_loss_backward, prediction.data_ptr(), target.data_ptr(), mask.data_ptr(), B, T, H, W,
-                     float(alpha), int(scales), float(stable_scale), scale_shift.data_ptr(), frame_stats.data_ptr(),
-                     frame_counts.data_ptr(), out.data_ptr(), coeff.data_ptr(), ws.data_ptr(), grad.data_ptr())
-
-    def depth_loss_trimmed(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, out: torch.Tensor, keep: float,
-                           alpha: float = 0.5, scales: int = 4, stable_scale: float = 10.0, scale_shift: Optional[torch.Tensor] = None,
-                           frame_stats: Optional[torch.Tensor] = None, frame_counts: Optional[torch.Tensor] = None):
-        """out[0:40] (float64) <- the trimmed VideoDepthLoss, keep = 1 - trim in (0, 1] (vdn_depth_loss_trimmed; include/vdn.h
-        has the layout)."""
-        B, T, H, W = prediction.shape
-        for t in (prediction, target):
-            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, T, H, W), t.shape
-        assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, T, H, W)
-        assert out.dtype == torch.float64 and out.numel() >= 40 and out.is_contiguous()
-        assert scale_shift is None or (scale_shift.dtype == torch.float32 and scale_shift.numel() == 2 * B and scale_shift.is_contiguous())
-        assert frame_stats is None or (frame_stats.dtype == torch.float64 and frame_stats.numel() == 4 * B * T and frame_stats.is_contiguous())
-        assert frame_counts is None or (frame_counts.dtype == torch.int64 and frame_counts.numel() == B * T and frame_counts.is_contiguous())
-        ws = self.buf("depth_loss_trimmed_ws", (abi.lib.vdn_depth_loss_trimmed_workspace_bytes(B, T) // 8,), torch.float64)
-        self._launch(abi.lib.vdn_depth_loss_trimmed, prediction.data_ptr(), target.data_ptr(), mask.data_ptr(), B, T, H, W, float(alpha),
-                     int(scales), float(stable_scale), float(keep), ws.data_ptr(), self._p(scale_shift), self._p(frame_stats),
-                     self._p(frame_counts), out.data_ptr())
-
-    def depth_loss_trimmed_backward(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, alpha: float, scales: int,
-                                    stable_scale: float, scale_shift: torch.Tensor, frame_stats: torch.Tensor,
-                                    frame_counts: torch.Tensor, out: torch.Tensor, coeff: torch.Tensor, grad: torch.Tensor):
-        """As depth_loss_backward for the trimmed criterion (vdn_depth_loss_trimmed_backward): out is the float64 [40] that
-        depth_loss_trimmed wrote for the same inputs and arguments."""
-        B, T, H, W = prediction.shape
-        for t in (prediction, target, grad):
-            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, T, H, W), t.shape
-        assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, T, H, W)
-        assert scale_shift.dtype == torch.float32 and scale_shift.numel() == 2 * B and scale_shift.is_contiguous()
-        assert frame_stats.dtype == torch.float64 and frame_stats.numel() == 4 * B * T and frame_stats.is_contiguous()
-        assert frame_counts.dtype == torch.int64 and frame_counts.numel() == B * T and frame_counts.is_contiguous()
-        assert out.dtype == torch.float64 and out.numel() >= 40 and out.is_contiguous()
-        assert coeff.dtype == torch.float32 and coeff.numel() == 3 and coeff.is_contiguous()
-        ws = self.buf("depth_loss_backward_ws", (abi.lib.vdn_depth_loss_trimmed_backward_workspace_bytes(B, T, H, W) // 8,), torch.float64)
-        self._launch(abi.lib.vdn_depth_loss_trimmed_backward, prediction.data_ptr(), target.data_ptr(), mask.data_ptr(), B, T, H, W,
-                     float(alpha), int(scales), float(stable_scale), scale_shift.data_ptr(), frame_stats.data_ptr(),
-                     frame_counts.data_ptr(), out.data_ptr(), coeff.data_ptr(), ws.data_ptr(), grad.data_ptr())
+        prediction (vdn_depth_loss_backward; keep < 1: vdn_depth_loss_trimmed_backward), coeff f32 [3] = {c_sp, c_st, c_ar} on
+        the device. scale_shift, frame_stats, frame_counts and out are what depth_loss wrote for the same inputs and arguments."""
+        B, T, H, W, trimmed, p, t, m, o, ss, fs, fc = self._depth_loss_args("depth_loss_backward", keep, prediction, target, mask, out,
+                                                                            scale_shift, frame_stats, frame_counts, False)
+        c = checked_ptr("depth_loss_backward: coeff", coeff, self.device, _f32, count=3)
+        g = checked_ptr("depth_loss_backward: grad", grad, self.device, _f32, prediction.shape)
+        size, entry = ((abi.lib.vdn_depth_loss_trimmed_backward_workspace_bytes, abi.lib.vdn_depth_loss_trimmed_backward) if trimmed
+                       else (abi.lib.vdn_depth_loss_backward_workspace_bytes, abi.lib.vdn_depth_loss_backward))
+        ws = self._ws("depth_loss_backward_ws", size(B, T, H, W))
+        self._launch(entry, p, t, m, B, T, H, W, float(alpha), int(scales), float(stable_scale), ss, fs, fc, o, c, ws.data_ptr(), g)
 
     def prep_rgb(self, x: torch.Tensor, out: torch.Tensor, normalize: bool):
         """out f32 [F, 3, H, W] <- clamp(x, 0, 1), then the ImageNet mean / std when `normalize` (vdn_prep_rgb); out may be x."""
+        px = checked_ptr("prep_rgb: x", x, self.device, _f32, (None, 3, None, None))
         F, _, H, W = x.shape
-        for t in (x, out):
-            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (F, 3, H, W), t.shape
-        self._launch(abi.lib.vdn_prep_rgb, x.data_ptr(), out.data_ptr(), F, H, W, int(normalize))
+        self._launch(abi.lib.vdn_prep_rgb, px, checked_ptr("prep_rgb: out", out, self.device, _f32, x.shape), F, H, W, int(normalize))
 
     def prep_depth(self, x: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Tensor, reciprocal: bool, clamp0: bool,
                    normalize: bool, minmax: Optional[torch.Tensor] = None):
         """out f32 [B, n] <- the stages of vdn_prep_depth on f32 x [B, n] under the u8 mask [B, n] (None: all kept);
         minmax f32 [B, 2] receives the (lo, hi) of the normalisation."""
+        dev = self.device
+        px = checked_ptr("prep_depth: x", x, dev, _f32, 2)
         B, n = x.shape
-        for t in (x, out):
-            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, n), t.shape
-        assert mask is None or (mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (B, n))
-        assert minmax is None or (minmax.is_contiguous() and minmax.dtype == torch.float32 and minmax.numel() == 2 * B)
-        ws = self.buf("prep_depth_ws", (abi.lib.vdn_prep_depth_workspace_bytes(B) // 8,), torch.float64) if normalize else None
-        self._launch(abi.lib.vdn_prep_depth, x.data_ptr(), self._p(mask), out.data_ptr(), B, n, int(reciprocal), int(clamp0),
-                     int(normalize), self._p(ws), self._p(minmax))
+        ws = self._ws("prep_depth_ws", abi.lib.vdn_prep_depth_workspace_bytes(B)).data_ptr() if normalize else None
+        self._launch(abi.lib.vdn_prep_depth, px, checked_ptr("prep_depth: mask", mask, dev, _u8, x.shape, optional=True),
+                     checked_ptr("prep_depth: out", out, dev, _f32, x.shape), B, n, int(reciprocal), int(clamp0), int(normalize), ws,
+                     checked_ptr("prep_depth: minmax", minmax, dev, _f32, count=2 * B, optional=True))
 
     @staticmethod
     def _bounds(bounds):
@@ -548,95 +563,110 @@ class Runtime:
     def metric_eval(self, pred: torch.Tensor, depth: torch.Tensor, valid: Optional[torch.Tensor], out: torch.Tensor, bounds=None):
         """out f64 [B, 10] <- n and eval_depth's nine metrics of f32 pred [B, h, w] against f32 depth [B, H, W] under the u8
         mask [B, H, W] (byte == 1 keeps; None: all kept) and, with bounds = (min_depth, max_depth), those (vdn_metric_eval)."""
+        dev = self.device
+        d = checked_ptr("metric_eval: depth", depth, dev, _f32, 3)
         B, H, W = depth.shape
-        assert pred.is_contiguous() and pred.dtype == torch.float32 and pred.dim() == 3 and pred.shape[0] == B, pred.shape
-        assert depth.is_contiguous() and depth.dtype == torch.float32
-        assert valid is None or (valid.is_contiguous() and valid.dtype == torch.uint8 and tuple(valid.shape) == (B, H, W))
-        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (B, 10)
-        ws = self.buf("metric_ws", (abi.lib.vdn_metric_workspace_bytes(B) // 8,), torch.float64)
-        self._launch(abi.lib.vdn_metric_eval, pred.data_ptr(), depth.data_ptr(), self._p(valid), B, pred.shape[1], pred.shape[2],
-                     H, W, *self._bounds(bounds), ws.data_ptr(), out.data_ptr())
+        p = checked_ptr("metric_eval: pred", pred, dev, _f32, (B, None, None))
+        self._launch(abi.lib.vdn_metric_eval, p, d, checked_ptr("metric_eval: valid", valid, dev, _u8, depth.shape, optional=True), B, pred.shape[1],
+                     pred.shape[2], H, W, *self._bounds(bounds), self._ws("metric_ws", abi.lib.vdn_metric_workspace_bytes(B)).data_ptr(),
+                     checked_ptr("metric_eval: out", out, dev, _f64, (B, 10)))
+
+    def _silog_args(self, what: str, pred, target, mask):
+        """-> the element count and the pointers of f32 pred and target and the u8 mask (or None) of that many elements."""
+        p = checked_ptr(what + ": pred", pred, self.device, _f32)
+        n = pred.numel()
+        return (n, p, checked_ptr(what + ": target", target, self.device, _f32, count=n),
+                checked_ptr(what + ": mask", mask, self.device, _u8, count=n, optional=True))
 
     def silog_loss(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Tensor, lambd: float,
                    bounds=None):
         """out f64 [4] <- loss | n | sum dl | sum dl^2 of SiLogLoss over f32 pred, target and the u8 mask of equal size
         (vdn_silog_loss)."""
-        n = pred.numel()
-        for t in (pred, target):
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == n, t.shape
-        assert mask is None or (mask.is_contiguous() and mask.dtype == torch.uint8 and mask.numel() == n)
-        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == 4
-        ws = self.buf("silog_ws", (abi.lib.vdn_silog_loss_workspace_bytes() // 8,), torch.float64)
-        self._launch(abi.lib.vdn_silog_loss, pred.data_ptr(), target.data_ptr(), self._p(mask), n, float(lambd),
-                     *self._bounds(bounds), ws.data_ptr(), out.data_ptr())
+        n, p, t, m = self._silog_args("silog_loss", pred, target, mask)
+        self._launch(abi.lib.vdn_silog_loss, p, t, m, n, float(lambd), *self._bounds(bounds),
+                     self._ws("silog_ws", abi.lib.vdn_silog_loss_workspace_bytes()).data_ptr(),
+                     checked_ptr("silog_loss: out", out, self.device, _f64, count=4))
 
     def silog_loss_backward(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], state: torch.Tensor,
                             coeff: torch.Tensor, grad: torch.Tensor, lambd: float, bounds=None):
         """grad f32 <- coeff * d loss / d pred (vdn_silog_loss_backward); state is what silog_loss wrote for the same inputs
         and arguments, coeff f32 [1] on the device."""
-        n = pred.numel()
-        for t in (pred, target, grad):
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == n, t.shape
-        assert mask is None or (mask.is_contiguous() and mask.dtype == torch.uint8 and mask.numel() == n)
-        assert state.is_contiguous() and state.dtype == torch.float64 and state.numel() == 4
-        assert coeff.is_contiguous() and coeff.dtype == torch.float32 and coeff.numel() == 1 and coeff.is_cuda
-        self._launch(abi.lib.vdn_silog_loss_backward, pred.data_ptr(), target.data_ptr(), self._p(mask), n, float(lambd),
-                     *self._bounds(bounds), state.data_ptr(), coeff.data_ptr(), grad.data_ptr())
+        dev = self.device
+        n, p, t, m = self._silog_args("silog_loss_backward", pred, target, mask)
+        self._launch(abi.lib.vdn_silog_loss_backward, p, t, m, n, float(lambd), *self._bounds(bounds),
+                     checked_ptr("silog_loss_backward: state", state, dev, _f64, count=4),
+                     checked_ptr("silog_loss_backward: coeff", coeff, dev, _f32, count=1),
+                     checked_ptr("silog_loss_backward: grad", grad, dev, _f32, count=n))
 
     def minmax(self, x: torch.Tensor, groups: int, out: torch.Tensor):
         """out f32 [groups, 2] <- {min, max} of each of the `groups` equal runs of contiguous f32 x (vdn_minmax_f32)."""
-        assert x.is_contiguous() and x.dtype == torch.float32 and x.numel() % groups == 0
-        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == 2 * groups
-        ws = self.buf("minmax_ws", (abi.lib.vdn_minmax_workspace_bytes(groups) // 4,), torch.float32)
-        self._launch(abi.lib.vdn_minmax_f32, x.data_ptr(), groups, x.numel() // groups, ws.data_ptr(), out.data_ptr())
+        px = checked_ptr("minmax: x", x, self.device, _f32)
+        if groups < 1 or x.numel() % groups:
+            raise abi.VdnError(f"minmax: {x.numel()} elements are not {groups} equal runs")
+        self._launch(abi.lib.vdn_minmax_f32, px, groups, x.numel() // groups,
+                     self._ws("minmax_ws", abi.lib.vdn_minmax_workspace_bytes(groups)).data_ptr(),
+                     checked_ptr("minmax: out", out, self.device, _f32, count=2 * groups))
 
     def colorize(self, depth: torch.Tensor, minmax: torch.Tensor, lut: torch.Tensor, out: torch.Tensor,
                  raw: Optional[torch.Tensor] = None, margin: int = 0):
         """out u8 <- palette pixels of f32 depth [N, H, W] (vdn_colorize): [N, H, W, ch], or with raw u8 [N, H, W, 3]
         [N, H, 2W + margin, 3]. minmax f32 [N, 2] (per frame) or [1, 2]; lut u8 [256, ch]."""
+        dev = self.device
+        d = checked_ptr("colorize: depth", depth, dev, _f32, 3)
         N, H, W = depth.shape
+        table = checked_ptr("colorize: lut", lut, dev, _u8, (256, None))
         ch = lut.shape[1]
-        assert depth.is_contiguous() and depth.dtype == torch.float32
-        assert minmax.is_contiguous() and minmax.dtype == torch.float32 and minmax.numel() in (2, 2 * N)
-        assert lut.is_contiguous() and lut.dtype == torch.uint8 and tuple(lut.shape) == (256, ch)
-        assert out.is_contiguous() and out.dtype == torch.uint8
-        if raw is None:
-            assert out.numel() == N * H * W * ch
-        else:
-            assert raw.is_contiguous() and raw.dtype == torch.uint8 and tuple(raw.shape) == (N, H, W, 3)
-            assert out.numel() == N * H * (2 * W + margin) * 3
-        self._launch(abi.lib.vdn_colorize, depth.data_ptr(), minmax.data_ptr(), int(minmax.numel() == 2 * N and N > 1),
-                     lut.data_ptr(), ch, self._p(raw), margin, out.data_ptr(), N, H, W)
+        per_frame = N > 1 and isinstance(minmax, torch.Tensor) and minmax.numel() == 2 * N
+        self._launch(abi.lib.vdn_colorize, d, checked_ptr("colorize: minmax", minmax, dev, _f32, count=2 * N if per_frame else 2),
+                     int(per_frame), table,
+                     ch, checked_ptr("colorize: raw", raw, dev, _u8, (N, H, W, 3), optional=True), margin,
+                     checked_ptr("colorize: out", out, dev, _u8, count=N * H * W * ch if raw is None else N * H * (2 * W + margin) * 3), N, H, W)
 
     def frame_median(self, x: torch.Tensor, median: torch.Tensor):
         """median[f] = torch.quantile(x[f], 0.5) for f32 x [F, ...] (exact radix select on the device)."""
+        px = checked_ptr("frame_median: x", x, self.device, _f32)
         F = x.shape[0]
-        ws = self.buf("median_ws", ((abi.lib.vdn_frame_median_workspace_bytes(F) + 7) // 8,), torch.int64)
-        assert x.is_contiguous() and x.dtype == torch.float32 and median.numel() == F
-        self._launch(abi.lib.vdn_frame_median, x.data_ptr(), F, x[0].numel(), median.data_ptr(), ws.data_ptr())
+        self._launch(abi.lib.vdn_frame_median, px, F, x[0].numel(), checked_ptr("frame_median: median", median, self.device, _f32, count=F),
+                     self._ws("median_ws", abi.lib.vdn_frame_median_workspace_bytes(F)).data_ptr())
 
     def refine_scale(self, x, median, w: float, b: float, max_log_scale: float, max_depth: float, out, scale_out=None):
-        self._launch(abi.lib.vdn_refine_scale, x.data_ptr(), median.data_ptr(), x.shape[0], x[0].numel(), w, b, max_log_scale,
-                     max_depth, out.data_ptr(), self._p(scale_out))
+        """out f32, of x's size <- x / max_depth * s_f for f32 x [F, ...] with s_f from median f32 [F] (vdn_refine_scale);
+        scale_out f32 [F] receives s_f."""
+        dev = self.device
+        px = checked_ptr("refine_scale: x", x, dev, _f32)
+        F = x.shape[0]
+        self._launch(abi.lib.vdn_refine_scale, px, checked_ptr("refine_scale: median", median, dev, _f32, count=F), F, x[0].numel(), w, b,
+                     max_log_scale, max_depth, checked_ptr("refine_scale: out", out, dev, _f32, count=x.numel()),
+                     checked_ptr("refine_scale: scale_out", scale_out, dev, _f32, count=F, optional=True))
 
     def refine_pack(self, d, out, normals: bool = True):
+        """out f32 [F, 3, H, W] <- (d, nx, ny) of f32 d [F, H, W], or d on all three planes without `normals` (vdn_refine_pack)."""
+        pd = checked_ptr("refine_pack: d", d, self.device, _f32, 3)
         F, H, W = d.shape
-        self._launch(abi.lib.vdn_refine_pack, d.data_ptr(), out.data_ptr(), F, H, W, int(normals))
+        self._launch(abi.lib.vdn_refine_pack, pd, checked_ptr("refine_pack: out", out, self.device, _f32, (F, 3, H, W)), F, H, W, int(normals))
 
     def refine_finish(self, scaled, depth, w: float, b: float, max_depth: float, residual: bool, out):
-        self._launch(abi.lib.vdn_refine_finish, self._p(scaled), depth.data_ptr(), w, b, max_depth, int(residual), out.data_ptr(),
-                     depth.numel())
+        """out <- (scaled + (w * depth + b)) * max_depth, or depth * max_depth without `residual`, over f32 tensors of depth's size
+        (vdn_refine_finish); scaled may be None where it is not read."""
+        dev = self.device
+        pd = checked_ptr("refine_finish: depth", depth, dev, _f32)
+        n = depth.numel()
+        self._launch(abi.lib.vdn_refine_finish, checked_ptr("refine_finish: scaled", scaled, dev, _f32, count=n, optional=not residual), pd, w, b,
+                     max_depth, int(residual), checked_ptr("refine_finish: out", out, dev, _f32, count=n), n)
 
     def refine_normalize(self, x, max_depth: float, out):
         """out = x / max_depth (true fp32 division) for contiguous f32 tensors of equal size."""
-        assert x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype == torch.float32 and out.numel() == x.numel()
-        self._launch(abi.lib.vdn_refine_normalize, x.data_ptr(), max_depth, out.data_ptr(), x.numel())
+        px = checked_ptr("refine_normalize: x", x, self.device, _f32)
+        self._launch(abi.lib.vdn_refine_normalize, px, max_depth,
+                     checked_ptr("refine_normalize: out", out, self.device, _f32, count=x.numel()), x.numel())
 
     def refine_mix(self, depth, x, a0: float, a1: float, c0: float, a2: float, c1: float, out):
         """out = relu(a2 * relu(a0 * depth + a1 * x + c0) + c1): the v2 refiner's final_res, BatchNorms folded (refiner.fold_final_res)."""
-        for t in (depth, x, out):
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == depth.numel()
-        self._launch(abi.lib.vdn_refine_mix, depth.data_ptr(), x.data_ptr(), a0, a1, c0, a2, c1, out.data_ptr(), depth.numel())
+        dev = self.device
+        pd = checked_ptr("refine_mix: depth", depth, dev, _f32)
+        n = depth.numel()
+        self._launch(abi.lib.vdn_refine_mix, pd, checked_ptr("refine_mix: x", x, dev, _f32, count=n), a0, a1, c0, a2, c1,
+                     checked_ptr("refine_mix: out", out, dev, _f32, count=n), n)
 
     def dn_attn(self, qkv, out, rows: int, Cn: int, heads: int, L: int, estride: int, n0: int, s0: int, n1: int, s1: int,
                 scale: float):
@@ -698,13 +728,13 @@ class Runtime:
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """u8 [n,h,w,3] on the device -> normalised f32 [n,3,H,W] (cubic resize + /255 + mean / std), one launch.
         `out`: a contiguous f32 [n,3,H,W] to write instead of a fresh tensor."""
+        src = checked_ptr("preprocess_u8: frames_u8", frames_u8, self.device, _u8, (None, None, None, 3))
         n, h, w, _ = frames_u8.shape
-        assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
         if out is None:
             out = torch.empty((n, 3, H, W), dtype=torch.float32, device=self.device)
-        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3, H, W)
         m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-        self._launch(abi.lib.vdn_preprocess, frames_u8.data_ptr(), n, h, w, int(swap_rb), out.data_ptr(), H, W, m3, s3)
+        self._launch(abi.lib.vdn_preprocess, src, n, h, w, int(swap_rb),
+                     checked_ptr("preprocess_u8: out", out, self.device, _f32, (n, 3, H, W)), H, W, m3, s3)
         return out
 
     def add_vec(self, x, vec, alpha: float, y, rows: int, Cn: int):
@@ -750,13 +780,12 @@ class Runtime:
     def depth_to_points(self, depth: torch.Tensor, rgb: torch.Tensor, fx: float, fy: float, points: torch.Tensor,
                         colors: torch.Tensor):
         """points, colors f64 [h*w, 3] <- the point cloud of depth f32 [h, w] and rgb u8 [h, w, 3] (vdn_depth_to_points)."""
+        dev = self.device
+        d = checked_ptr("depth_to_points: depth", depth, dev, _f32, 2)
         h, w = depth.shape
-        assert depth.dtype == torch.float32 and depth.is_contiguous() and rgb.dtype == torch.uint8 and rgb.is_contiguous()
-        assert tuple(rgb.shape) == (h, w, 3), (rgb.shape, depth.shape)
-        for t in (points, colors):
-            assert t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (h * w, 3), (t.shape, t.dtype)
-        self._launch(abi.lib.vdn_depth_to_points, depth.data_ptr(), rgb.data_ptr(), h, w, float(fx), float(fy), points.data_ptr(),
-                     colors.data_ptr())
+        self._launch(abi.lib.vdn_depth_to_points, d, checked_ptr("depth_to_points: rgb", rgb, dev, _u8, (h, w, 3)), h, w, float(fx), float(fy),
+                     checked_ptr("depth_to_points: points", points, dev, _f64, (h * w, 3)),
+                     checked_ptr("depth_to_points: colors", colors, dev, _f64, (h * w, 3)))
 
     def mask_down1(self, depth, out, B, H, W, OH, OW, w):
         self._launch(abi.lib.vdn_mask_down1, depth.data_ptr(), out.data_ptr(), B, H, W, OH, OW, w.data_ptr())

@@ -14,22 +14,11 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _abi as abi
+from ._device import runtime as _runtime
 from ._palettes import PALETTES
 from .runtime import Runtime
 
-_RUNTIMES: Dict[torch.device, Runtime] = {}
 _LUTS: Dict[tuple, torch.Tensor] = {}
-
-
-def _runtime(device: torch.device) -> Runtime:
-    if device.type != "cuda":
-        raise abi.VdnError("vdn.vis runs on an MI355X ('cuda' device under ROCm); there is no CPU path")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if device not in _RUNTIMES:
-        _RUNTIMES[device] = Runtime(device)
-    return _RUNTIMES[device]
 
 
 def _check(palette: str, order: str, scope: str, grayscale: bool, gray_channels: int):

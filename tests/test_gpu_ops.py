@@ -568,6 +568,57 @@ def test_x3_flash_attention(rt3, nq, nk, gain, pv, tol, qk8):
         rt3.pv_products = PV_DEFAULT
 
 
+# rel-L2 bars of test_bf16_split_flash_attention: 4 x the error measured on these inputs before flash_attn_kernel moved onto
+# csrc/attn_tile.hpp (profiles/attn_refactor.md has the measured values), the margin the fp16 rows use for rounding noise
+BF16_SPLIT_BARS = {(130, 321, 3): 4 * 9.609e-6, (130, 321, 2): 4 * 1.623e-3, (37, 64, 3): 4 * 8.197e-6, (37, 64, 2): 4 * 1.258e-3}
+
+
+def bf16_split_flash_attention(nq, nk, pv):
+    """-> rel-L2 error of one bf16 split-plane vdn_flash_attn call against fp64 attention on the values the planes hold; a
+    second call must give the same bits."""
+    from vdn.runtime import HL, Runtime, ceil_to
+    bf = torch.bfloat16
+    rb = Runtime(torch.device("cuda:0"), bf, split=True)
+    rb.pv_products = pv
+    H, dh = 2, 64
+    q, k, v = rnd(H, nq, dh, seed=250), rnd(H, nk, dh, seed=251), rnd(H, nk, dh, seed=252)
+    qp, kp = ceil_to(nq, 64), ceil_to(nk, 64)
+    Q, K, V = HL.from_float(q, bf, True), HL.from_float(k, bf, True), HL.from_float(v.transpose(1, 2), bf, True)
+    ref = F.scaled_dot_product_attention(Q.float().double(), K.float().double(), V.float().double().transpose(1, 2))
+    ref = ref.float().transpose(0, 1).reshape(nq, H * dh)
+
+    def padded(P, shape, fill):   # planes into a [H, *shape] buffer whose padding is `fill`
+        planes = []
+        for p in (P.hi, P.lo):
+            t = torch.full((H, *shape), fill, dtype=bf)
+            t[:, :p.shape[1], :p.shape[2]] = p
+            planes.append(t.to(DEV))
+        return HL(*planes)
+
+    qd, kd, vd = padded(Q, (qp, dh), 0.0), padded(K, (kp, dh), float("nan")), padded(V, (dh, kp), 0.0)  # pad keys must not matter
+    out = HL(torch.full((nq, H * dh), float("nan"), dtype=bf, device=DEV), torch.full((nq, H * dh), float("nan"), dtype=bf, device=DEV))
+    rb.flash_attn(qd, kd, vd, out, 1, H, nq, qp, nk, kp, 0.125)
+    first = (out.hi.clone(), out.lo.clone())
+    got = out.float().cpu()
+    rb.flash_attn(qd, kd, vd, out, 1, H, nq, qp, nk, kp, 0.125)
+    assert torch.equal(out.hi.view(torch.int16), first[0].view(torch.int16)) and torch.equal(out.lo.view(torch.int16), first[1].view(torch.int16))
+    assert bool(torch.isfinite(got).all())
+    return float((got - ref).norm() / ref.norm())
+
+
+@pytest.mark.parametrize("pv", [3, 2])
+@pytest.mark.parametrize("nq,nk", [(130, 321), (37, 64)])
+def test_bf16_split_flash_attention(nq, nk, pv):
+    """flash_attn_kernel<bf16, SPLIT> with the 3-product and the 2-product P V (bf16 has no 8-bit planes, so pv = 1 runs the
+    2-product kernel as well): six tiles with a ragged last one and two query blocks, and a single tile. The pv = 2 bars are
+    those of a weight rounded once to bf16's 8 bits (2^-9 relative): at that width they would not notice the V_lo product
+    going missing (2^-9 of V as well); what pins that product is the pv = 3 rows here and the byte comparison of
+    tools/attn_dump.py between two builds."""
+    err = bf16_split_flash_attention(nq, nk, pv)
+    print(f"\nbf16 split flash_attn {nq}x{nk} pv={pv}: rel-L2 {err:.3e} (bar {BF16_SPLIT_BARS[(nq, nk, pv)]})")
+    assert err < BF16_SPLIT_BARS[(nq, nk, pv)]
+
+
 @pytest.mark.parametrize("T", [32, 64, 50])
 def test_x3_temporal_attention_up_to_64_frames(rt3, T):
     Bv, D, c = 1, 5, 192

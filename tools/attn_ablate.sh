@@ -1,7 +1,7 @@
 #!/bin/bash
-# Variant libraries of the attention kernel with parts of its loop removed (VDN_ATTN_ABL bits, csrc/attn.hip) for
-# same-box timing: where do the cycles of a 64-key tile go? Usage: [FLAG=VDN_ATTN_OPT VARS="0 1 ..."] tools/attn_ablate.sh build | run
-# (VDN_ATTN_ABL bits: 1 no DMA, 2 no barrier, 4 no softmax VALU, 8 no MFMA; VDN_ATTN_OPT: schedule switches, csrc/attn.hip)
+# Variant libraries of the attention kernel with parts of its loop removed (VDN_ATTN_ABL bits, csrc/attn_tile.hpp) for
+# same-box timing: where do the cycles of a 64-key tile go? Usage: [VARS="0 1 ..."] tools/attn_ablate.sh build | run
+# (VDN_ATTN_ABL bits, csrc/attn_tile.hpp: 1 no DMA, 2 no barrier, 4 no softmax VALU, 8 no MFMA)
 PKG="$(cd "$(dirname "$0")/.." && pwd)/video-depth-normal-v2_amd"
 VARS="${VARS:-0 1 2 3 4 7 8 11}"; FLAG="${FLAG:-VDN_ATTN_ABL}"
 if [ "$1" = build ]; then

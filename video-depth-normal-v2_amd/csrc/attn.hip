@@ -12,17 +12,13 @@
 //   ds_read_b128 fragment reads bank-conflict free.
 //   SPLIT: every operand comes as (hi, lo) 16-bit planes and each product is accumulated as
 //   hi*hi + hi*lo + lo*hi (fp32-faithful "x3" mode, see include/vdn.h).
-//   PV2 (SPLIT only, the default): P, which is born in registers, is rounded ONCE to 16 bits (p~) and O accumulates
+//   PV2 (SPLIT only): P, which is born in registers, is rounded ONCE to 16 bits (p~) and O accumulates
 //   p~ (V_hi + V_lo): 2 products instead of 3 and no lo split of P on the VALU. The row sum l is accumulated from the
 //   SAME rounded p~ (one v_dot2 per pair), so O / l is an exact convex combination of the (21-bit) V rows with
 //   weights p~ / sum p~: the rounding perturbs each weight by <= 2^-11 relative and any part of it common to a
 //   row cancels in the normalisation (DESIGN.md §3 has the measured end-to-end effect).
-//   QK8 (with PV2, fp16 only): the two CROSS terms of S^T = K Q^T run on the block-scaled 8-bit MFMA
-//   (v_mfma_scale_f32_32x32x64_f8f6f4, e5m2 operands, K = 64 = the whole head dimension in one instruction, 2.3x the
-//   fp16 rate measured): S^T = K_hi Q_hi^T [4 fp16 MFMAs] + K8 (Q_lo8)^T 2^-10 + K_lo8 (Q8)^T 2^-10 [2 MFMAs], where
-//   X8 = e5m2(X) and X_lo8 = e5m2((X - X_hi) 2^10) are written by the projection GEMM's epilogue (vdn_gemm_desc.dst8)
-//   and the 2^-10 is the MFMA's E8M0 scale operand. A cross term is 2^-11 of the product, so the 3-bit e5m2 significand
-//   leaves 2^-14 per term: logits good to ~1e-5 (tools/micro/mfma_scale_probe.hip pins layout, scale and rate).
+//   The tile itself (staging, fragment addresses, softmax pieces, output) is attn_tile.hpp, shared with
+//   flash_attn2_kernel (attn2_kernel.hpp), the kernel of the default mode: fp16 split planes with 8-bit Q / K planes.
 //
 // temporal_attn_kernel — <= 32 frames per (pixel, head): one wave per sequence, fragments loaded
 //   straight from global memory (no LDS), same accumulator-as-operand chaining.
@@ -33,41 +29,9 @@
 
 namespace {
 
-__device__ __forceinline__ bool lane_hi() { return (threadIdx.x & 32) != 0; }
-__device__ __forceinline__ int perm23(int i) {  // swap bits 2 and 3
-  return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1);
-}
-// key offset (0..31) held by accumulator register `reg` of lane-half `h` after the row permutation
-__device__ __forceinline__ int acc_key(int reg, int h) {
-  return (reg & 3) + 4 * ((reg >> 2) & 1) + 8 * h + 16 * (reg >> 3);
-}
+#include "attn_tile.hpp"
 
-// value held by the same row's lane in the other 32-lane half (v_permlane32_swap: VALU, no LDS round trip)
-__device__ __forceinline__ float xhalf(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __builtin_bit_cast(float, (lane_hi() ? r[0] : r[1]));
-}
-
-template <class F, int... J>
-__device__ __forceinline__ void for_each_slot_impl(F& f, std::integer_sequence<int, J...>) {
-  (f(std::integral_constant<int, J>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void for_each_slot(F& f) {
-  for_each_slot_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
-// Timing ablations for tools/attn_ablate.sh variant builds only (results are wrong with any bit set; the shipped
-// library is built without the macro): 1 no LDS-DMA in the loop, 2 no workgroup barrier, 4 no softmax VALU, 8 no MFMA, 16 no fragment reads from LDS, 32 one workgroup per CU, 64 s_memtime stamps, 128 softmax without its fma
-// (96 KB of LDS requested: one wave per SIMD).
-#ifndef VDN_ATTN_ABL
-#define VDN_ATTN_ABL 0
-#endif
-
-template <int DT, bool SPLIT, bool PV2, bool QK8>
+template <int DT, bool SPLIT, bool PV2>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void flash_attn_kernel(const typename Half<DT>::T* __restrict__ Q,
                                                          const typename Half<DT>::T* __restrict__ K,
                                                          const typename Half<DT>::T* __restrict__ Vt,
@@ -76,79 +40,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                                          const typename Half<DT>::T* __restrict__ Kl,
                                                          const typename Half<DT>::T* __restrict__ Vtl,
                                                          typename Half<DT>::T* __restrict__ outl,
-                                                         const uint8_t* __restrict__ Q8, const uint8_t* __restrict__ K8,
                                                          int H, int nq, int nq_pad, int nk, int nk_pad, float scale_log2) {
-  static_assert(!QK8 || (SPLIT && PV2 && DT == VDN_F16), "8-bit cross terms: split fp16 planes, 2-product P V");
   using HT = Half<DT>;
   using T = typename HT::T;
   using V8 = typename HT::V8;
-  constexpr int TILE = 8192;         // 64 rows x 128 B
   constexpr int NT = SPLIT ? 4 : 2;  // tiles per stage: K, Vt (, K_lo, Vt_lo)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
+  // the wave's place (attn_tile.hpp states the order)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // 1-D grid, XCD-aware: the q-blocks of one (batch, head) are consecutive logical ids and therefore run
-  // on ONE XCD, so its K / V^T tiles are fetched from HBM once and re-read by the other q-blocks from
-  // that XCD's L2 (rocprofv3 FETCH_SIZE showed 7.6x over-fetch with a round-robin 2-D grid).
   const int nqb = (nq + 127) >> 7;
   const int logical = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = logical / nqb;
   const int q0 = (logical - bh * nqb) * 128 + wave * 32;
   const int r = lane & 31, h = lane >> 5;
-
-  // ---- Q fragments (B operand of S^T = K Q^T): Q[q][16 ks + 8 h + j]
   V8 qf[4], ql[4];
-  i32x8 q8h, q8l;  // QK8: B operands of the 32x32x64 8-bit MFMA: Q8[q][32 h + j], j = 0..31
   {
     int q = q0 + r;
     q = q < nq ? q : nq - 1;
-    const size_t qo = ((size_t)bh * nq_pad + q) * 64 + 8 * h;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      qf[ks] = *(const V8*)(Q + qo + 16 * ks);
-      if constexpr (SPLIT && !QK8) ql[ks] = *(const V8*)(Ql + qo + 16 * ks);
-    }
-    if constexpr (QK8) {
-      const uint8_t* q8 = Q8 + ((size_t)bh * nq_pad + q) * 128 + 32 * h;
-      const u32x4 a0 = *(const u32x4*)q8, a1 = *(const u32x4*)(q8 + 16), b0 = *(const u32x4*)(q8 + 64), b1 = *(const u32x4*)(q8 + 80);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { q8h[e] = (int)a0[e]; q8h[4 + e] = (int)a1[e]; q8l[e] = (int)b0[e]; q8l[4 + e] = (int)b1[e]; }
-    }
+    load_q<HT, SPLIT>(Q, Ql, ((size_t)bh * nq_pad + q) * 64 + 8 * h, qf, ql);
   }
-
-  // ---- staging: 8 pieces (1 KiB = 8 rows) per tile and operand, 2 per wave, as `buffer_load_dwordx4 ... offen lds`:
-  // the (batch, head)'s plane is a buffer resource (4 SGPRs, hardware range check), the lane's place in a piece a
-  // loop-invariant 32-bit VGPR offset and the tile a SCALAR offset — no vector address arithmetic per tile (the flat
-  // global_load_lds form cost 16 v_lshl_add_u64 per tile and 16 VGPRs of per-lane 64-bit pointers).
-  const int lr = lane >> 3;
-  const unsigned k_bytes = (unsigned)nk_pad * 64 * sizeof(T);  // one plane of one (batch, head): K rows, V^T rows, K8 rows
-  const auto rsrc = [&](const void* base, size_t off) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + off), 0, (int)k_bytes, 0x00020000);
-  };
-  const size_t plane_off = (size_t)bh * k_bytes;
-  const __amdgpu_buffer_rsrc_t rK = rsrc(K, plane_off), rV = rsrc(Vt, plane_off);
-  const __amdgpu_buffer_rsrc_t rKl = rsrc(QK8 ? (const void*)K8 : (const void*)(SPLIT ? Kl : K), plane_off);
-  const __amdgpu_buffer_rsrc_t rVl = rsrc(SPLIT ? Vtl : Vt, plane_off);
-  int koff[2], voff[2];  // byte offsets
+  // staging: 2 pieces per wave, tile and plane; the second planes are K_lo and V^T_lo
+  const __amdgpu_buffer_rsrc_t rK = plane_rsrc<T>(K, bh, nk_pad), rV = plane_rsrc<T>(Vt, bh, nk_pad);
+  const __amdgpu_buffer_rsrc_t rKl = plane_rsrc<T>(SPLIT ? Kl : K, bh, nk_pad), rVl = plane_rsrc<T>(SPLIT ? Vtl : Vt, bh, nk_pad);
+  int koff[2], voff[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = (wave + 4 * i) * 8 + lr;
-    const int c = (lane & 7) ^ ((row >> 1) & 7);
-    koff[i] = (row * 64 + c * 8) * (int)sizeof(T);
-    voff[i] = (row * nk_pad + c * 8) * (int)sizeof(T);
-  }
-#define BLDS16(rs, voffset, soffset, dst) \
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst), 16, voffset, soffset, 0, 0)
-  // piece i (0, 1) of a tile of K (hi plane; second plane = K_lo rows or the 8-bit rows: both 128 B per key) / of V^T
-  auto stage_k_piece = [&](int buf, int t, int i, bool second) {
-    char* sK = smem + buf * NT * TILE + (second ? 2 * TILE : 0);
-    BLDS16(second ? rKl : rK, koff[i], t * (64 * 64 * (int)sizeof(T)), sK + (wave + 4 * i) * 1024);
-  };
-  auto stage_v_piece = [&](int buf, int t, int i, bool second) {
-    char* sV = smem + buf * NT * TILE + TILE + (second ? 2 * TILE : 0);
-    BLDS16(second ? rVl : rV, voff[i], t * (64 * (int)sizeof(T)), sV + (wave + 4 * i) * 1024);
-  };
+  for (int i = 0; i < 2; ++i) stage_offsets<T>(wave, lane, i, nk_pad, koff[i], voff[i]);
+  auto stage_k_piece = [&](int buf, int t, int i, bool second) { dma_k_piece<T, NT>(second ? rKl : rK, koff[i], buf, t, wave, i, second); };
+  auto stage_v_piece = [&](int buf, int t, int i, bool second) { dma_v_piece<T, NT>(second ? rVl : rV, voff[i], buf, t, wave, i, second); };
   auto stage_k = [&](int buf, int t) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -163,32 +81,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if constexpr (SPLIT) stage_v_piece(buf, t, i, true);
     }
   };
-
-  // ---- fragment read offsets. Row r (+32 kb) of a tile, 16-byte chunk (2 ks + h) ^ swz(row): the kb / db
-  // term is a compile-time immediate and the ks / c term an XOR with (ks << 5), so ONE register per operand
-  // is kept (not 8) and the address of each fragment pair costs one v_xor (the loop is register-bound).
-  const int k_base = perm23(r) * 128 + ((h ^ ((perm23(r) >> 1) & 7)) << 4);
-  const int v_base = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);
-  auto k_addr = [&](int kb, int ks) { return kb * 4096 + (k_base ^ (ks << 5)); };
-  // 8-bit A operand of key row perm23(r): bytes 32 h .. 32 h + 31 of the e5m2(K) half (16-byte chunks 2h, 2h+1 of the
-  // row) or of the remainder half (chunks 4+2h, 5+2h), same XOR swizzle: one base, the chunk as an XOR immediate
-  const int k8_base = perm23(r) * 128 + (((2 * h) ^ ((perm23(r) >> 1) & 7)) << 4);
-  auto k8_read = [&](const char* sK, int kb, int lo) {
-    const char* p = sK + 2 * TILE + kb * 4096;
-    const u32x4 a0 = *(const u32x4*)(p + (k8_base ^ ((4 * lo) << 4))), a1 = *(const u32x4*)(p + (k8_base ^ ((4 * lo + 1) << 4)));
-    i32x8 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[e] = (int)a0[e]; v[4 + e] = (int)a1[e]; }
-    return v;
-  };
-  // cross terms of one 32-key block on the scaled 8-bit MFMA (e5m2 x e5m2; the remainder planes carry 2^10)
-  auto cross_hl = [&](const i32x8& k8, f32x16 c) {  // K8 (Q_lo8)^T
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k8, q8l, c, 1, 1, 0, 127, 0, VDN_LO8_E8M0);
-  };
-  auto cross_lh = [&](const i32x8& k8l, f32x16 c) {  // K_lo8 (Q8)^T
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k8l, q8h, c, 1, 1, 0, VDN_LO8_E8M0, 0, 127);
-  };
-  auto v_addr = [&](int db, int c) { return db * 4096 + (v_base ^ (c << 5)); };
+  const FragAddr fa(r, h);
 
   f32x16 o[2];
 #pragma unroll
@@ -197,42 +90,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   // S^T of one 64-key tile from K buffer `buf`
   auto qk = [&](int buf, f32x16 (&sc)[2]) {
-    const char* sK = smem + buf * NT * TILE;
+    const char* sK = attn_smem + buf * NT * ATTN_TILE;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) sc[kb][i] = 0.f;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const V8 a = *(const V8*)(sK + k_addr(kb, ks));
+        const V8 a = *(const V8*)(sK + fa.k(kb, ks));
         sc[kb] = HT::mfma32(a, qf[ks], sc[kb]);
-        if constexpr (SPLIT && !QK8) {
-          const V8 al = *(const V8*)(sK + 2 * TILE + k_addr(kb, ks));
+        if constexpr (SPLIT) {
+          const V8 al = *(const V8*)(sK + 2 * ATTN_TILE + fa.k(kb, ks));
           sc[kb] = HT::mfma32(a, ql[ks], sc[kb]);
           sc[kb] = HT::mfma32(al, qf[ks], sc[kb]);
         }
       }
-      if constexpr (QK8) {
-        sc[kb] = cross_hl(k8_read(sK, kb, 0), sc[kb]);
-        sc[kb] = cross_lh(k8_read(sK, kb, 1), sc[kb]);
-      }
     }
-  };
-  // O^T += V^T P^T of one tile from V buffer `buf`
-  auto pv = [&](int buf, const V8 (&pf)[2][2], const V8 (&pl)[2][2]) {
-    const char* sV = smem + buf * NT * TILE + TILE;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)  // c outer: a P fragment is dead after its 6 MFMAs (registers for the next tile's P)
-#pragma unroll
-      for (int db = 0; db < 2; ++db) {
-        const V8 a = *(const V8*)(sV + v_addr(db, c));
-        o[db] = HT::mfma32(a, pf[c >> 1][c & 1], o[db]);
-        if constexpr (SPLIT) {
-          const V8 al = *(const V8*)(sV + 2 * TILE + v_addr(db, c));
-          if constexpr (!PV2) o[db] = HT::mfma32(a, pl[c >> 1][c & 1], o[db]);
-          o[db] = HT::mfma32(al, pf[c >> 1][c & 1], o[db]);
-        }
-      }
   };
 
   // Three-stage software pipeline, all in ONE basic block per iteration so the scheduler can slot the
@@ -241,10 +114,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   //     iteration t:   S(t+1) = K_{t+1} Q^T   ||   P(t) = softmax-numerator(S(t))   ||   O += V_{t-1} P(t-1)
   // LDS ring (2 buffers each): iteration t reads K_{t+1} and V_{t-1}; its DMA fills K_{t+2} (buffer of K_t,
   // consumed in iteration t-1) and V_t (buffer of V_{t-2}, consumed in iteration t-1).
-  // Lazy rescale: the reference point m_run moves only when some row's tile maximum exceeds it by more than
-  // 2^LAZY (P stays <= 2^LAZY: exact in fp32 / split fp16; the 1/l normalisation makes the result
-  // independent of the reference), so in steady state the O accumulators are never touched by the VALU.
-  constexpr float LAZY = 6.0f;
   const int nt = (nk + 63) >> 6;
   f32x16 s[2];
   V8 pf[2][2], pl[2][2];
@@ -257,17 +126,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (t + 2 < nt) stage_k(cur, t + 2);
       }
     }
-    if constexpr (!HAS_NEXT) {  // only the last tile can be ragged
-      if ((t + 1) * 64 > nk) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int i = 0; i < 16; ++i)
-            if (t * 64 + kb * 32 + acc_key(i, h) >= nk) s[kb][i] = -INFINITY;
-      }
-    }
-    const char* sKn = smem + (cur ^ 1) * NT * TILE;         // K_{t+1}
-    const char* sVp = smem + (cur ^ 1) * NT * TILE + TILE;  // V_{t-1}
+    if constexpr (!HAS_NEXT) mask_ragged(s, t, nk, h);  // only the last tile can be ragged
+    const char* sKn = attn_smem + (cur ^ 1) * NT * ATTN_TILE;         // K_{t+1}
+    const char* sVp = attn_smem + (cur ^ 1) * NT * ATTN_TILE + ATTN_TILE;  // V_{t-1}
 
     // ---- hand-placed stream: 48 slots = 16 MFMA triples (8 of PV(t-1), c outer; then 8 of QK(t+1)), each
     // slot = one small piece of softmax(t) + one MFMA, fenced by sched_barrier so the order survives the
@@ -278,25 +139,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     //   P fragment f is read by PV(t-1) in slots 6f..6f+5 and rewritten by softmax(t) in slots >= 7+8f;
     //   S[0] is last read in slot 20 and overwritten by QK(t+1) from slot 24, S[1] read in 36 (softmax piece
     //   first in the slot), overwritten from slot 36's MFMA on.
-    V8 fa[2], fl[2];
-    i32x8 f8[2];  // QK8: the 8-bit K fragment of triples (kb, ks = 0) [e5m2(K)] and (kb, ks = 1) [remainder plane]
+    V8 fr[2], fl[2];
     auto frag = [&](auto jc, V8& a, V8& al) {
       constexpr int j = decltype(jc)::value;
       if constexpr (VDN_ATTN_ABL & 16) {
         asm volatile("" : "+v"(a), "+v"(al));  // timing ablation: no fragment reads (operands stay what they were)
       } else if constexpr (j < 8) {
         if constexpr (HAS_PREV) {
-          a = *(const V8*)(sVp + v_addr(j & 1, j >> 1));
-          if constexpr (SPLIT) al = *(const V8*)(sVp + 2 * TILE + v_addr(j & 1, j >> 1));
+          a = *(const V8*)(sVp + fa.v(j & 1, j >> 1));
+          if constexpr (SPLIT) al = *(const V8*)(sVp + 2 * ATTN_TILE + fa.v(j & 1, j >> 1));
         }
       } else if constexpr (HAS_NEXT) {
-        a = *(const V8*)(sKn + k_addr((j - 8) >> 2, (j - 8) & 3));
-        if constexpr (QK8) {
-          constexpr int ks = (j - 8) & 3;
-          if constexpr (ks < 2) f8[ks] = k8_read(sKn, (j - 8) >> 2, ks);
-        } else if constexpr (SPLIT) {
-          al = *(const V8*)(sKn + 2 * TILE + k_addr((j - 8) >> 2, (j - 8) & 3));
-        }
+        a = *(const V8*)(sKn + fa.k((j - 8) >> 2, (j - 8) & 3));
+        if constexpr (SPLIT) al = *(const V8*)(sKn + 2 * ATTN_TILE + fa.k((j - 8) >> 2, (j - 8) & 3));
       }
     };
     auto mma = [&](auto jc, auto qc, const V8& a, const V8& al) {
@@ -316,12 +171,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int i = 0; i < 16; ++i) z[i] = 0.f;
           s[kb] = HT::mfma32(a, qf[ks], z);
-        } else if constexpr (QK8) {
-          // 6 MFMAs per 32-key block in its 12 slots: 4 fp16 (q == 0) + the two 8-bit cross terms in the q == 1 slots
-          // of ks = 0, 1 (twice as long as a fp16 MFMA: they hide two softmax pieces); the other slots are VALU-only
-          if constexpr (q == 0) s[kb] = HT::mfma32(a, qf[ks], s[kb]);
-          if constexpr (q == 1 && ks == 0) s[kb] = cross_hl(f8[0], s[kb]);
-          if constexpr (q == 1 && ks == 1) s[kb] = cross_lh(f8[1], s[kb]);
         } else {
           if constexpr (q == 0) s[kb] = HT::mfma32(a, qf[ks], s[kb]);
           if constexpr (q == 1) s[kb] = HT::mfma32(a, ql[ks], s[kb]);
@@ -333,20 +182,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     bool bump = false;
     auto vstep = [&](auto kc) {
       constexpr int k = decltype(kc)::value;
-      if constexpr (k < 4) {  // tile maximum, 8 scores per slot
-        constexpr int kb = k >> 1, i = (k & 1) * 8;
-        mx = fmaxf(fmaxf(mx, s[kb][i]), s[kb][i + 1]);
-        mx = fmaxf(fmaxf(mx, s[kb][i + 2]), s[kb][i + 3]);
-        mx = fmaxf(fmaxf(mx, s[kb][i + 4]), s[kb][i + 5]);
-        mx = fmaxf(fmaxf(mx, s[kb][i + 6]), s[kb][i + 7]);
+      if constexpr (k < 4) {
+        max8<(k & 1) * 8>(mx, s[k >> 1]);
       } else if constexpr (k == 4) {
-        mx = fmaxf(mx, xhalf(mx));
+        max_halves(mx);
       } else if constexpr (k == 5) {
-        bump = __builtin_amdgcn_ballot_w64((mx - m_run) * scale_log2 > LAZY) != 0;  // wave-uniform
-        const float m_new = bump ? fmaxf(m_run, mx) : m_run;
-        alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2);  // == 1 when not bumped
-        m_run = m_new;
-        mb = -m_new * scale_log2;
+        lazy_reference(mx, scale_log2, m_run, bump, alpha, mb);
       } else if constexpr (k < 38) {
         constexpr int pi = (k - 6) >> 1, kb = pi >> 3, i = (pi & 7) * 2;
         if constexpr (((k - 6) & 1) == 0) {
@@ -380,26 +221,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
     auto slot = [&](auto jc) {
       constexpr int j = decltype(jc)::value, tj = j / 3, q = j % 3;
-      if constexpr (q == 0 && tj + 1 < 16) frag(std::integral_constant<int, tj + 1>{}, fa[(tj + 1) & 1], fl[(tj + 1) & 1]);
+      if constexpr (q == 0 && tj + 1 < 16) frag(std::integral_constant<int, tj + 1>{}, fr[(tj + 1) & 1], fl[(tj + 1) & 1]);
       if constexpr (!(VDN_ATTN_ABL & 4)) vstep(jc);
-      if constexpr (!(VDN_ATTN_ABL & 8)) mma(std::integral_constant<int, tj>{}, std::integral_constant<int, q>{}, fa[tj & 1], fl[tj & 1]);
+      if constexpr (!(VDN_ATTN_ABL & 8)) mma(std::integral_constant<int, tj>{}, std::integral_constant<int, q>{}, fr[tj & 1], fl[tj & 1]);
       __builtin_amdgcn_sched_barrier(0);
     };
-    frag(std::integral_constant<int, 0>{}, fa[0], fl[0]);
+    frag(std::integral_constant<int, 0>{}, fr[0], fl[0]);
     for_each_slot<48>(slot);
 
     // P(t) is only consumed by the next iteration's MFMAs: keep LLVM from sinking its computation there.
     asm volatile("" : "+v"(pf[0][0]), "+v"(pf[0][1]), "+v"(pf[1][0]), "+v"(pf[1][1]));
     if constexpr (SPLIT && !PV2) asm volatile("" : "+v"(pl[0][0]), "+v"(pl[0][1]), "+v"(pl[1][0]), "+v"(pl[1][1]));
-    if (bump) {  // O is in the old reference (it just received tile t-1): move it to the new one
-      asm volatile("" ::: "memory");  // keep this a real (rarely taken) branch: if-converted it costs 16 v_pk_mul per tile
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { o[0][i] *= alpha; o[1][i] *= alpha; }
-    }
-    if constexpr (VDN_ATTN_ABL & 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else stage_barrier();
+    close_iteration(bump, alpha, o);
   };
 
+  // The run, in the order attn_tile.hpp states it (spelled out in both kernels: as a shared function taking the
+  // iteration it changed the tile loop's scalar code, profiles/attn_refactor.md).
   stage_k(0, 0);
   if (nt > 1) stage_k(1, 1);
   stage_barrier();
@@ -414,23 +251,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int t = 1; t + 1 < nt; ++t) iter(t, Y, Y);
     iter(nt - 1, Y, N);
   }
-  pv((nt - 1) & 1, pf, pl);
+  // O^T += V^T P^T of the last tile (as a shared function it renamed the fragment registers of the bf16 3-product tile loop)
+  {
+    const char* sV = attn_smem + ((nt - 1) & 1) * NT * ATTN_TILE + ATTN_TILE;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int db = 0; db < 2; ++db) {
+        const V8 a = *(const V8*)(sV + fa.v(db, c));
+        o[db] = HT::mfma32(a, pf[c >> 1][c & 1], o[db]);
+        if constexpr (SPLIT) {
+          const V8 al = *(const V8*)(sV + 2 * ATTN_TILE + fa.v(db, c));
+          if constexpr (!PV2) o[db] = HT::mfma32(a, pl[c >> 1][c & 1], o[db]);
+          o[db] = HT::mfma32(al, pf[c >> 1][c & 1], o[db]);
+        }
+      }
+  }
 
-  const float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = 1.0f / l_tot;
+  const float inv = inv_row_sum(l_run);
   const int q = q0 + r;
   if (q < nq) {
-    const int b = bh / H, hd = bh - b * H;
-    const size_t oo = (((size_t)b * nq + q) * H + hd) * 64;
+    const size_t oo = out_row(bh, H, nq, q).oo;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
+        // Must stay equal to out_quad (attn_tile.hpp), spelled out here: called with the quads by reference, the bf16
+        // kernels kept them in scratch (24 bytes per lane, profiles/attn_refactor.md).
         typename HT::V4 v, vl;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float x = o[db][4 * g + e] * inv;
-          if (outl) {  // the output is written as planes whenever the caller passes a lo plane (also in 1-product mode)
+          if (outl) {  // planes whenever the caller passes a lo plane (also in 1-product mode)
             T a, b2;
             split_rtz(x, a, b2);
             v[e] = a;
@@ -697,36 +549,37 @@ int flash_launch(const void* Q, const void* K, const void* Vt, void* out, const 
                  void* outl, const void* Q8, const void* K8, void* out8, int out_kt, int B, int H, int nq, int nq_pad, int nk, int nk_pad,
                  float sl2, int pv, hipStream_t s) {
   using T = typename Half<DT>::T;
-  const dim3 grid(((nq + 127) / 128) * B * H);
   const bool pv3 = pv == 3;  // the 3-product P V with P split into hi / lo planes
   const uint8_t* q8 = (const uint8_t*)Q8;
   const uint8_t* k8 = (const uint8_t*)K8;
   // the 8-bit / K-tile-major output planes and a lo-less output exist in the default kernel only (fp16 split planes + Q8 / K8)
   if ((out8 || out_kt || (Ql && !outl)) && !(Ql && !pv3 && q8 && k8 && DT == VDN_F16)) return VDN_EUNSUPPORTED;
+  // flash_attn_kernel: 4 waves = 128 queries per workgroup, lds bytes of its two ring stages
+  const auto grid = [&](int qb) { return dim3(((nq + qb - 1) / qb) * B * H); };  // 1-D: q-blocks of qb queries x (batch, head)
+  auto launch = [&](auto kernel, int lds) {
+    hipLaunchKernelGGL(kernel, grid(128), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, (const T*)Ql,
+                       (const T*)Kl, (const T*)Vtl, (T*)outl, H, nq, nq_pad, nk, nk_pad, sl2);
+  };
   if (Ql && pv3)
-    hipLaunchKernelGGL((flash_attn_kernel<DT, true, false, false>), grid, dim3(256), 65536, s, (const T*)Q, (const T*)K, (const T*)Vt,
-                       (T*)out, (const T*)Ql, (const T*)Kl, (const T*)Vtl, (T*)outl, q8, k8, H, nq, nq_pad, nk, nk_pad, sl2);
+    launch(flash_attn_kernel<DT, true, false>, 65536);
   else if (Ql && q8 && k8 && DT == VDN_F16) {
     if constexpr (DT == VDN_F16) {
 #ifndef VDN_ATTN2_NW
 #define VDN_ATTN2_NW 4
 #endif
       constexpr int NW = VDN_ATTN2_NW;
-      const dim3 grid2(((nq + 32 * NW - 1) / (32 * NW)) * B * H);
-      if (pv == 1)
-        hipLaunchKernelGGL((flash_attn2_kernel<1, NW>), grid2, dim3(64 * NW), (VDN_ATTN_ABL & 32) ? 98304 : 65536, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out,
-                           (const T*)Kl, (const T*)Vtl, (T*)outl, q8, k8, H, nq, nq_pad, nk, nk_pad, sl2, (uint8_t*)out8, out_kt, B * nq);
-      else
-        hipLaunchKernelGGL((flash_attn2_kernel<2, NW>), grid2, dim3(64 * NW), (VDN_ATTN_ABL & 32) ? 98304 : 65536, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out,
-                           (const T*)Kl, (const T*)Vtl, (T*)outl, q8, k8, H, nq, nq_pad, nk, nk_pad, sl2, (uint8_t*)out8, out_kt, B * nq);
+      auto launch2 = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid(32 * NW), dim3(64 * NW), (VDN_ATTN_ABL & 32) ? 98304 : 65536, s, (const T*)Q,
+                           (const T*)K, (const T*)Vt, (T*)out, (const T*)Kl, (const T*)Vtl, (T*)outl, q8, k8, H, nq, nq_pad, nk, nk_pad, sl2,
+                           (uint8_t*)out8, out_kt, B * nq);
+      };
+      if (pv == 1) launch2(flash_attn2_kernel<1, NW>);
+      else launch2(flash_attn2_kernel<2, NW>);
     }
   } else if (Ql)
-    hipLaunchKernelGGL((flash_attn_kernel<DT, true, true, false>), grid, dim3(256), 65536, s, (const T*)Q, (const T*)K, (const T*)Vt,
-                       (T*)out, (const T*)Ql, (const T*)Kl, (const T*)Vtl, (T*)outl, q8, k8, H, nq, nq_pad, nk, nk_pad, sl2);
+    launch(flash_attn_kernel<DT, true, true>, 65536);
   else
-    hipLaunchKernelGGL((flash_attn_kernel<DT, false, false, false>), grid, dim3(256), 32768, s, (const T*)Q, (const T*)K, (const T*)Vt,
-                       (T*)out, (const T*)nullptr, (const T*)nullptr, (const T*)nullptr, (T*)outl, q8, k8, H, nq, nq_pad, nk,
-                       nk_pad, sl2);
+    launch(flash_attn_kernel<DT, false, false>, 32768);
   VDN_CHECK_LAUNCH();
   return VDN_OK;
 }

@@ -1,7 +1,14 @@
 // flash_attn2_kernel — the attention of the default precision mode (fp16 split planes, 2-product P V, score cross terms
-// on the block-scaled 8-bit MFMA), head_dim 64. Same data layout, same arithmetic per element and the same MFMA
-// products as flash_attn_kernel<F16, SPLIT, PV2, QK8> (attn.hip, whose header describes the S^T = K Q^T / O^T = V^T P^T
-// formulation, the row permutation and the LDS image); what differs is the instruction stream of a tile iteration:
+// on the block-scaled 8-bit MFMA), head_dim 64. Same data layout and the same tile (attn_tile.hpp) as flash_attn_kernel
+// (attn.hip, whose header describes the S^T = K Q^T / O^T = V^T P^T formulation, the row permutation, the LDS image and the
+// once-rounded P~ of the 2-product P V), with the 8-bit K plane in the place of K_lo:
+//   QK8: the two CROSS terms of S^T = K Q^T run on the block-scaled 8-bit MFMA
+//   (v_mfma_scale_f32_32x32x64_f8f6f4, e5m2 operands, K = 64 = the whole head dimension in one instruction, 2.3x the
+//   fp16 rate measured): S^T = K_hi Q_hi^T [4 fp16 MFMAs] + K8 (Q_lo8)^T 2^-10 + K_lo8 (Q8)^T 2^-10 [2 MFMAs], where
+//   X8 = e5m2(X) and X_lo8 = e5m2((X - X_hi) 2^10) are written by the projection GEMM's epilogue (vdn_gemm_desc.dst8)
+//   and the 2^-10 is the MFMA's E8M0 scale operand. A cross term is 2^-11 of the product, so the 3-bit e5m2 significand
+//   leaves 2^-14 per term: logits good to ~1e-5 (tools/micro/mfma_scale_probe.hip pins layout, scale and rate).
+// and its own instruction stream of a tile iteration:
 //
 //   * S and P are double-buffered by tile parity (iterations are instantiated for even and odd tiles), so QK(t+1),
 //     softmax(t) and PV(t-1) share no registers and may interleave freely;
@@ -13,7 +20,7 @@
 //   * operand fragments are read LOOKAHEAD MFMAs ahead into a register ring, the 8 LDS-DMA pieces of the iteration are
 //     spread over the gaps, LDS addresses are immediates (the buffer parity is a template parameter).
 //
-// Included by attn.hip (helpers perm23 / acc_key / xhalf / stage_barrier and the Half<> traits come from there).
+// Included by attn.hip after attn_tile.hpp (stage_barrier and the Half<> traits come from common.hpp).
 
 // PV: MFMA products per P V term: 2 = P~ (V_hi + V_lo), 1 = P~ V_hi with V_hi rounded to nearest by the producer
 // (vdn_gemm rounds the hi plane of transposed head splits that way): 8 MFMAs, 8 fragment reads and 2 LDS-DMA pieces fewer per tile.
@@ -21,6 +28,8 @@
 // and plane. 8 (A/B build -DVDN_ATTN2_NW=8): one workgroup per CU, one piece per wave — the same 2 waves per SIMD and half the
 // DMA instructions per wave (an LDS-DMA piece costs its wave 60-180 cycles of issue: s_memtime stamps put ~500 of a tile's
 // 3000 cycles there), but one barrier over 8 waves instead of two independent 4-wave groups: measured 134 vs 125 us. Stays 4.
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
 template <int PV, int NW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void flash_attn2_kernel(
     const _Float16* __restrict__ Q, const _Float16* __restrict__ K, const _Float16* __restrict__ Vt, _Float16* __restrict__ out,
@@ -30,16 +39,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   using HT = Half<VDN_F16>;
   using T = _Float16;
   using V8 = typename HT::V8;
-  constexpr int TILE = 8192;  // 64 rows x 128 B
   constexpr int NT = 4;       // tiles per stage: K, V^T, K8, V^T_lo
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
+  constexpr int NPC = 8 / NW;      // LDS-DMA pieces (of the 8 of a 64-row tile plane) per wave
+  // the wave's place (attn_tile.hpp states the order)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int QB = 32 * NW;      // queries per workgroup
-  constexpr int NPC = 8 / NW;      // LDS-DMA pieces (of the 8 of a 64-row tile plane) per wave
   const int nqb = (nq + QB - 1) / QB;
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);  // the q-blocks of one (batch, head) share an XCD's L2
+  const int logical = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = logical / nqb;
   const int q0 = (logical - bh * nqb) * QB + wave * 32;
   const int r = lane & 31, h = lane >> 5;
@@ -50,48 +57,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   {
     int q = q0 + r;
     q = q < nq ? q : nq - 1;
-    const size_t qo = ((size_t)bh * nq_pad + q) * 64 + 8 * h;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const V8*)(Q + qo + 16 * ks);
+    load_q<HT, false>(Q, nullptr, ((size_t)bh * nq_pad + q) * 64 + 8 * h, qf, qf);
     const uint8_t* q8 = Q8 + ((size_t)bh * nq_pad + q) * 128 + 32 * h;
     const u32x4 a0 = *(const u32x4*)q8, a1 = *(const u32x4*)(q8 + 16), b0 = *(const u32x4*)(q8 + 64), b1 = *(const u32x4*)(q8 + 80);
 #pragma unroll
     for (int e = 0; e < 4; ++e) { q8h[e] = (int)a0[e]; q8h[4 + e] = (int)a1[e]; q8l[e] = (int)b0[e]; q8l[4 + e] = (int)b1[e]; }
   }
-
-  // ---- staging (buffer_load_dwordx4 ... offen lds): plane of this (batch, head) as a buffer resource, loop-invariant
-  // 32-bit lane offsets, the tile as a scalar offset; 8 pieces of 1 KiB per tile and plane, 2 per wave
-  const int lr = lane >> 3;
-  const unsigned k_bytes = (unsigned)nk_pad * 64 * sizeof(T);
-  const auto rsrc = [&](const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + (size_t)bh * k_bytes), 0, (int)k_bytes, 0x00020000);
-  };
-  const __amdgpu_buffer_rsrc_t rK = rsrc(K), rV = rsrc(Vt), rK8 = rsrc(K8), rVl = rsrc(Vtl);
+  // staging: NPC pieces per wave, tile and plane; the second planes are the 8-bit K rows (128 B per key as well) and V^T_lo
+  const __amdgpu_buffer_rsrc_t rK = plane_rsrc<T>(K, bh, nk_pad), rV = plane_rsrc<T>(Vt, bh, nk_pad);
+  const __amdgpu_buffer_rsrc_t rK8 = plane_rsrc<T>(K8, bh, nk_pad), rVl = plane_rsrc<T>(Vtl, bh, nk_pad);
   int koff[2], voff[2];
 #pragma unroll
-  for (int i = 0; i < NPC; ++i) {
-    const int row = (wave + 4 * i) * 8 + lr;
-    const int c = (lane & 7) ^ ((row >> 1) & 7);
-    koff[i] = (row * 64 + c * 8) * (int)sizeof(T);
-    voff[i] = (row * nk_pad + c * 8) * (int)sizeof(T);
-  }
-#define A2_BLDS16(rs, voffset, soffset, dst) \
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst), 16, voffset, soffset, 0, 0)
-  auto stage_k_piece = [&](int buf, int t, int i, bool second) {
-    A2_BLDS16(second ? rK8 : rK, koff[i], t * (64 * 64 * (int)sizeof(T)), smem + buf * NT * TILE + (second ? 2 * TILE : 0) + (wave + 4 * i) * 1024);
-  };
-  auto stage_v_piece = [&](int buf, int t, int i, bool second) {
-    A2_BLDS16(second ? rVl : rV, voff[i], t * (64 * (int)sizeof(T)), smem + buf * NT * TILE + TILE + (second ? 2 * TILE : 0) + (wave + 4 * i) * 1024);
-  };
-
-  // ---- fragment addresses: row r (+32 kb) of a tile, 16-byte chunk (2 ks + h) ^ swz(row)
-  const int k_base = perm23(r) * 128 + ((h ^ ((perm23(r) >> 1) & 7)) << 4);
-  const int v_base = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);
-  const int k8_base = perm23(r) * 128 + (((2 * h) ^ ((perm23(r) >> 1) & 7)) << 4);
-  auto k_addr = [&](int kb, int ks) { return kb * 4096 + (k_base ^ (ks << 5)); };
-  auto v_addr = [&](int db, int c) { return db * 4096 + (v_base ^ (c << 5)); };
+  for (int i = 0; i < NPC; ++i) stage_offsets<T>(wave, lane, i, nk_pad, koff[i], voff[i]);
+  auto stage_k_piece = [&](int buf, int t, int i, bool second) { dma_k_piece<T, NT>(second ? rK8 : rK, koff[i], buf, t, wave, i, second); };
+  auto stage_v_piece = [&](int buf, int t, int i, bool second) { dma_v_piece<T, NT>(second ? rVl : rV, voff[i], buf, t, wave, i, second); };
+  const FragAddr fa(r, h);
+  // 8-bit A operand of key row perm23(r): bytes 32 h .. 32 h + 31 of the e5m2(K) half (16-byte chunks 2h, 2h+1 of the
+  // row) or of the remainder half (chunks 4+2h, 5+2h), same XOR swizzle: one base, the chunk as an XOR immediate
+  const int k8_base = frag_base(perm23(r), 2 * h);
   auto k8_read = [&](const char* sK, int kb, int lo) {
-    const char* p = sK + 2 * TILE + kb * 4096;
+    const char* p = sK + 2 * ATTN_TILE + kb * 4096;
     const u32x4 a0 = *(const u32x4*)(p + (k8_base ^ ((4 * lo) << 4))), a1 = *(const u32x4*)(p + (k8_base ^ ((4 * lo + 1) << 4)));
     i32x8 v;
 #pragma unroll
@@ -110,7 +95,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
   for (int i = 0; i < 16; ++i) { o[0][i] = 0.f; o[1][i] = 0.f; }
   float m_run = -1e30f, l_run = 0.f;
-  constexpr float LAZY = 6.0f;  // the reference maximum moves only when a tile exceeds it by 2^LAZY (flash_attn_kernel)
   const int nt = (nk + 63) >> 6;
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
@@ -124,19 +108,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   auto iter = [&](int t, auto has_prev_c, auto has_next_c, auto par_c) {
     constexpr bool HAS_PREV = decltype(has_prev_c)::value, HAS_NEXT = decltype(has_next_c)::value;
     constexpr int PAR = decltype(par_c)::value;
-    const char* sKn = smem + (PAR ^ 1) * NT * TILE;         // K_{t+1}, K8_{t+1}
-    const char* sVp = smem + (PAR ^ 1) * NT * TILE + TILE;  // V_{t-1}, V_lo_{t-1}
+    const char* sKn = attn_smem + (PAR ^ 1) * NT * ATTN_TILE;         // K_{t+1}, K8_{t+1}
+    const char* sVp = attn_smem + (PAR ^ 1) * NT * ATTN_TILE + ATTN_TILE;  // V_{t-1}, V_lo_{t-1}
     f32x16(&sc)[2] = s[PAR];
     f32x16(&sn)[2] = s[PAR ^ 1];
-    if constexpr (!HAS_NEXT) {  // only the last tile can be ragged
-      if ((t + 1) * 64 > nk) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int i = 0; i < 16; ++i)
-            if (t * 64 + kb * 32 + acc_key(i, h) >= nk) sc[kb][i] = -INFINITY;
-      }
-    }
+    if constexpr (!HAS_NEXT) mask_ragged(sc, t, nk, h);  // only the last tile can be ragged
     V8 fr[8];  // fragment ring (the generated stream uses lookahead + 1 of them)
     i32x8 f8[2];
     float mx = -1e30f, alpha = 1.f, mb = 0.f, ls0 = 0.f, ls1 = 0.f;
@@ -146,10 +122,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int tk = t + 2 < nt ? t + 2 : nt - 1;  // past the end the last K tile is fetched again, into the buffer nobody reads
 
     auto ldv = [&](auto cc, auto dbc, auto wc, auto bc) {
-      if constexpr (HAS_PREV) fr[decltype(bc)::value] = *(const V8*)(sVp + decltype(wc)::value * 2 * TILE + v_addr(decltype(dbc)::value, decltype(cc)::value));
+      if constexpr (HAS_PREV) fr[decltype(bc)::value] = *(const V8*)(sVp + decltype(wc)::value * 2 * ATTN_TILE + fa.v(decltype(dbc)::value, decltype(cc)::value));
     };
     auto ldk = [&](auto kbc, auto ksc, auto bc) {
-      if constexpr (HAS_NEXT) fr[decltype(bc)::value] = *(const V8*)(sKn + k_addr(decltype(kbc)::value, decltype(ksc)::value));
+      if constexpr (HAS_NEXT) fr[decltype(bc)::value] = *(const V8*)(sKn + fa.k(decltype(kbc)::value, decltype(ksc)::value));
     };
     auto ldk8 = [&](auto kbc, auto loc, auto bc) {
       if constexpr (HAS_NEXT) f8[decltype(bc)::value] = k8_read(sKn, decltype(kbc)::value, decltype(loc)::value);
@@ -169,21 +145,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         else sn[kb] = cross_lh(f8[decltype(bc)::value], decltype(firstc)::value ? zero16 : sn[kb]);
       }
     };
-    auto vmax = [&](auto qc) {
-      constexpr int kb = decltype(qc)::value >> 1, i = (decltype(qc)::value & 1) * 8;
-      mx = fmaxf(fmaxf(mx, sc[kb][i]), sc[kb][i + 1]);
-      mx = fmaxf(fmaxf(mx, sc[kb][i + 2]), sc[kb][i + 3]);
-      mx = fmaxf(fmaxf(mx, sc[kb][i + 4]), sc[kb][i + 5]);
-      mx = fmaxf(fmaxf(mx, sc[kb][i + 6]), sc[kb][i + 7]);
-    };
-    auto vxh = [&]() { mx = fmaxf(mx, xhalf(mx)); };
-    auto vbp = [&]() {
-      bump = __builtin_amdgcn_ballot_w64((mx - m_run) * scale_log2 > LAZY) != 0;  // wave-uniform
-      const float m_new = bump ? fmaxf(m_run, mx) : m_run;
-      alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2);  // == 1 when not bumped
-      m_run = m_new;
-      mb = -m_new * scale_log2;
-    };
+    auto vmax = [&](auto qc) { max8<(decltype(qc)::value & 1) * 8>(mx, sc[decltype(qc)::value >> 1]); };
+    auto vxh = [&]() { max_halves(mx); };
+    auto vbp = [&]() { lazy_reference(mx, scale_log2, m_run, bump, alpha, mb); };
     auto vf = [&](auto pc) {  // pair p: scores sc[p >> 3][2 (p & 7)], +1
       constexpr int p = decltype(pc)::value, kb = p >> 3, i = (p & 7) * 2;
       if constexpr (VDN_ATTN_ABL & 128) {  // timing ablation: what a pre-scaled Q + the maximum as accumulator init would save (no fma)
@@ -221,7 +185,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
       }
     };
-#if VDN_ATTN_ABL & 16  // timing ablations (attn.hip): no fragment reads / no MFMA / no softmax VALU / no LDS-DMA
+#if VDN_ATTN_ABL & 16  // timing ablations (attn_tile.hpp): no fragment reads / no MFMA / no softmax VALU / no LDS-DMA
 #define A2_LDV(c, db, w, b) A2_PIN(fr[b]);
 #define A2_LDK(kb, ks, b) A2_PIN(fr[b]);
 #define A2_LDK8(kb, lo, b) A2_PIN(f8[b]);
@@ -297,33 +261,34 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
     // S(t+1) is consumed by the next iteration only: keep its computation in this one (P(t) and the sums are pinned piecewise)
     if constexpr (HAS_NEXT) { A2_PIN(sn[0]); A2_PIN(sn[1]); }
-    if (bump) {  // O is in the old reference (it just received tile t-1): move it to the new one
-      asm volatile("" ::: "memory");  // a real (rarely taken) branch
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { o[0][i] *= alpha; o[1][i] *= alpha; }
-    }
-    if constexpr (VDN_ATTN_ABL & 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else stage_barrier();
+    close_iteration(bump, alpha, o);
 #if VDN_ATTN_ABL & 64
     { const unsigned long long now = __builtin_amdgcn_s_memtime(); stamp_sum[4] += now - stamp_last; stamp_last = now; }
 #endif
   };
 
-  // ---- prologue: K_0 (and K_1) in flight, S(0) from buffer 0
-  auto stage_k_all = [&](int buf, int t) {
+  auto s0 = [&] {  // S(0) from buffer 0
 #pragma unroll
-    for (int i = 0; i < NPC; ++i) { stage_k_piece(buf, t, i, false); stage_k_piece(buf, t, i, true); }
+    for (int kb = 0; kb < 2; ++kb) {
+      s[0][kb] = cross_hl(k8_read(attn_smem, kb, 0), zero16);
+      s[0][kb] = cross_lh(k8_read(attn_smem, kb, 1), s[0][kb]);
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) s[0][kb] = HT::mfma32(*(const V8*)(attn_smem + fa.k(kb, ks)), qf[ks], s[0][kb]);
+    }
   };
-  stage_k_all(0, 0);
-  if (nt > 1) stage_k_all(1, 1);
+  // The run, in the order attn_tile.hpp states it, with the middle iterations alternating between the two parities
+  // (spelled out in both kernels, see flash_attn_kernel).
+  auto stage_k = [&](int buf, int t) {
+#pragma unroll
+    for (int i = 0; i < NPC; ++i) {
+      stage_k_piece(buf, t, i, false);
+      stage_k_piece(buf, t, i, true);
+    }
+  };
+  stage_k(0, 0);
+  if (nt > 1) stage_k(1, 1);
   stage_barrier();
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb) {
-    s[0][kb] = cross_hl(k8_read(smem, kb, 0), zero16);
-    s[0][kb] = cross_lh(k8_read(smem, kb, 1), s[0][kb]);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) s[0][kb] = HT::mfma32(*(const V8*)(smem + k_addr(kb, ks)), qf[ks], s[0][kb]);
-  }
+  s0();
   stage_barrier();  // every wave has read K_0 before iteration 0 lets K_2 overwrite it
   constexpr std::true_type Y{};
   constexpr std::false_type N{};
@@ -342,14 +307,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
   // ---- O += V_{nt-1} P(nt-1)
   {
-    const char* sV = smem + ((nt - 1) & 1) * NT * TILE + TILE;
+    const char* sV = attn_smem + ((nt - 1) & 1) * NT * ATTN_TILE + ATTN_TILE;
     auto pv_last = [&](const V8(&p)[2][2]) {
 #pragma unroll
       for (int c = 0; c < 4; ++c)
 #pragma unroll
         for (int db = 0; db < 2; ++db) {
-          o[db] = HT::mfma32(*(const V8*)(sV + v_addr(db, c)), p[c >> 1][c & 1], o[db]);
-          if constexpr (PV == 2) o[db] = HT::mfma32(*(const V8*)(sV + 2 * TILE + v_addr(db, c)), p[c >> 1][c & 1], o[db]);
+          o[db] = HT::mfma32(*(const V8*)(sV + fa.v(db, c)), p[c >> 1][c & 1], o[db]);
+          if constexpr (PV == 2) o[db] = HT::mfma32(*(const V8*)(sV + 2 * ATTN_TILE + fa.v(db, c)), p[c >> 1][c & 1], o[db]);
         }
     };
     if ((nt - 1) & 1) pv_last(pf[1]);
@@ -360,28 +325,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   if (blockIdx.x == 300 && tid == 0)  // one wave of a mid-grid workgroup reports (the output is garbage in this build anyway)
     for (int i = 0; i < 5; ++i) ((unsigned long long*)out)[i] = stamp_sum[i];
 #endif
-  const float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = 1.0f / l_tot;
+  const float inv = inv_row_sum(l_run);
   const int q = q0 + r;
   if (q < nq) {
-    const int b = bh / H, hd = bh - b * H;
-    const size_t row = (size_t)b * nq + q;
-    const size_t oo = (row * H + hd) * 64;
+    const auto [hd, row, oo] = out_row(bh, H, nq, q);
     [[maybe_unused]] f16x32 hv6, lv6;   // out8: the lane's 32 channels (stream position 16 db + 4 g + e) = one half of the head's slab
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         typename HT::V4 v, vl;
-        float f[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          T a, b2;
-          f[e] = o[db][4 * g + e] * inv;
-          split_rtz(f[e], a, b2);
-          v[e] = a;
-          vl[e] = b2;
-        }
+        out_quad<HT>(o[db], g, inv, true, v, vl);
         const int c = db * 32 + 8 * g + 4 * h;  // channel inside the head
         // out_kt: K-tile-major planes for the 8-bit cross-term GEMM that consumes the attention output (vdn_gemm_desc.a_kt):
         // halves [C/32][rows][32] (the head's two 32-channel tiles are 2 hd + db), bytes [C/64][rows][64] (tile hd)
@@ -404,5 +358,4 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
 #undef A2_IC
 #undef A2_PIN
-#undef A2_BLDS16
 }

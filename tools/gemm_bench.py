@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""GPU micro-benchmark of vdn_gemm on the path's shapes (HIP events, interleaved rounds)."""
+"""GPU micro-benchmark of vdn_gemm on the path's shapes (HIP events, interleaved rounds); prints the median and every repeat.
+VDN_LIB=<other tree>/lib/libvdn_hip.so measures another build of the library with the same script."""
 import os, sys, math
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "video-depth-normal-v2_amd"))
@@ -54,4 +55,4 @@ for name, m, n, k, opt in shapes:
     ts.sort()
     med = ts[len(ts) // 2]
     fl = 2.0 * m * n * k
-    print(f"{name:18s} M={m:7d} N={n:5d} K={k:5d}  {med*1e3:8.1f} us  alg {fl/med/1e9:7.1f} TF/s  executed {(3 if split else 1)*fl/med/1e9:7.1f} TF/s  (BM={os.environ.get('VDN_GEMM_BM','auto')})", flush=True)
+    print(f"{name:18s} M={m:7d} N={n:5d} K={k:5d}  {med*1e3:8.1f} us  alg {fl/med/1e9:7.1f} TF/s  executed {(3 if split else 1)*fl/med/1e9:7.1f} TF/s  (BM={os.environ.get('VDN_GEMM_BM','auto')})  all us {' '.join(f'{t*1e3:.1f}' for t in ts)}", flush=True)

@@ -8,7 +8,7 @@
 // Both kernels are register-bound (occupancy 2 at 183..241 VGPRs) and their register allocation follows the order in which
 // the prologue creates its values: these are plain inlined functions on values the kernels keep in locals, in the shapes
 // with which every loop of every kernel compiles to the text it had before this header existed
-// (profiles/attn_refactor.md, tools/attn_asm_diff.py). Included by attn.hip after common.hpp, inside its anonymous namespace.
+// (profiles/attn_refactor.md, tools/asm_diff.py). Included by attn.hip after common.hpp, inside its anonymous namespace.
 
 // Timing ablations for tools/attn_ablate.sh variant builds only (results are wrong with any bit set; the shipped
 // library is built without the macro): 1 no LDS-DMA in the loop, 2 no workgroup barrier, 4 no softmax VALU, 8 no MFMA, 16 no fragment reads from LDS, 32 one workgroup per CU, 64 s_memtime stamps, 128 softmax without its fma

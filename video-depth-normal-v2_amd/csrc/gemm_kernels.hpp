@@ -21,7 +21,7 @@
 //
 // Roofline: MFMA-bound (>= 170 flop per HBM byte on every shape of the path).
 #pragma once
-#include "common.hpp"
+#include "planes.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -221,28 +221,21 @@ __host__ __device__ inline int epi_flavour(const vdn_gemm_desc& d) {
 template <int DT, int STORE>
 __device__ __forceinline__ void emit4(const vdn_gemm_desc& p, int m, int n, f32x4 a, f32x4 b, f32x4 bias_a, f32x4 bias_b,
                                       f32x4 gam) {
+  // the generic stores, and the straight-line flavours of the 4-wave kernels and of splitk_reduce_kernel. FC1, the head split
+  // without RoPE and SUBPIX are paired-column flavours: emit8 / epilogue_subpix (epilogue_dispatch maps the first two to the
+  // generic code for the 4-wave kernels)
+  static_assert(STORE == VDN_ST_PLAIN || STORE == VDN_ST_CONVT || STORE == VDN_ST_GEGLU || STORE == VDN_ST_HEADS ||
+                STORE == VDN_STX_SPLITK || STORE == VDN_STX_HALF || STORE == VDN_STX_RESHALF1 || STORE == VDN_STX_RESHALF2 ||
+                STORE == VDN_STX_RES, "emit4 serves these flavours");
   using H = Half<DT>;
   using T = typename H::T;
+  using V4 = typename H::V4;
   if (m >= p.M || n >= p.N) return;
   // ---- straight-line flavours of the hot epilogues (chosen on the host by epi_flavour()): the generic code
   // below tests ~40 wave-uniform descriptor fields per group, and with 32 groups per lane and only two waves
   // per SIMD those scalar branches were 12 us of every 31 us tile round at K = 32 (tools/gemm_ablate.sh).
   if constexpr (STORE == VDN_STX_SPLITK) {  // raw partial sums of one K slice (p.out / p.ldc were redirected to the slice)
     *(f32x4*)((float*)p.out + (size_t)m * p.ldc + n) = a;
-    return;
-  } else if constexpr (STORE == VDN_STX_FC1) {  // bias + GELU -> split half planes, plain rows
-    a = gelu4(a + bias_a);
-    // out_kt: the planes are written K-tile-major ([N/32][M][32] halves, [N/64][M][64] bytes) for the next 8-bit GEMM
-    const size_t o = p.out_kt ? ((size_t)(n >> 5) * p.M + m) * 32 + (n & 31) : (size_t)m * p.ldc + n;
-    typename H::V4 h, l;
-#pragma unroll
-    for (int e = 0; e < 4; e += 2) {
-      T h0, h1, l0, l1;
-      split2_rtz(a[e], a[e + 1], h0, h1, l0, l1);
-      h[e] = h0; h[e + 1] = h1; l[e] = l0; l[e + 1] = l1;
-    }
-    *(typename H::V4*)((T*)p.out + o) = h;
-    if (p.out_lo) *(typename H::V4*)((T*)p.out_lo + o) = l;
     return;
   } else if constexpr (STORE == VDN_STX_HALF || STORE == VDN_STX_RESHALF1 || STORE == VDN_STX_RESHALF2) {
     // [bias] [relu] [+ split-half residual(s)] -> split half planes, plain rows (the DPT head's convolutions)
@@ -253,65 +246,23 @@ __device__ __forceinline__ void emit4(const vdn_gemm_desc& p, int m, int n, f32x
       for (int e = 0; e < 4; ++e) a[e] = (a[e] < floor_v) ? floor_v : a[e];  // NaN passes through (fmaxf would hide it)
     } else {
       const size_t r1 = (size_t)m * p.ldr1 + n;
-      const typename H::V4 rh = *(const typename H::V4*)((const T*)p.res1 + r1), rl = *(const typename H::V4*)((const T*)p.res1_lo + r1);
+      const V4 rh = *(const V4*)((const T*)p.res1 + r1), rl = *(const V4*)((const T*)p.res1_lo + r1);
 #pragma unroll
       for (int e = 0; e < 4; ++e) a[e] += (float)rh[e] + (float)rl[e];
       if constexpr (STORE == VDN_STX_RESHALF2) {
         const size_t r2 = (size_t)m * p.ldr2 + n;
-        const typename H::V4 qh = *(const typename H::V4*)((const T*)p.res2 + r2), ql = *(const typename H::V4*)((const T*)p.res2_lo + r2);
+        const V4 qh = *(const V4*)((const T*)p.res2 + r2), ql = *(const V4*)((const T*)p.res2_lo + r2);
 #pragma unroll
         for (int e = 0; e < 4; ++e) a[e] += (float)qh[e] + (float)ql[e];
       }
     }
-    const size_t o = (size_t)m * p.ldc + n;
-    typename H::V4 h, l;
-#pragma unroll
-    for (int e = 0; e < 4; e += 2) {
-      T h0, h1, l0, l1;
-      split2_rtz(a[e], a[e + 1], h0, h1, l0, l1);
-      h[e] = h0; h[e + 1] = h1; l[e] = l0; l[e + 1] = l1;
-    }
-    *(typename H::V4*)((T*)p.out + o) = h;
-    *(typename H::V4*)((T*)p.out_lo + o) = l;
+    V4 h, l;
+    split_planes(a, h, l);
+    store_out_planes<false, T>(p, (size_t)m * p.ldc + n, h, l);
     return;
   } else if constexpr (STORE == VDN_STX_RES) {  // (acc + bias) * gamma + f32 residual -> f32 rows
     a = (a + bias_a) * gam + *(const f32x4*)((const float*)p.res1 + (size_t)m * p.ldr1 + n);
     *(f32x4*)((float*)p.out + (size_t)m * p.ldc + n) = a;
-    return;
-  } else if constexpr (STORE == VDN_STX_HEADS) {  // bias -> per-head Q / K rows or V^T columns, split planes, no RoPE
-    const int hc = p.heads * 64;
-    const int bt = m / p.tokens, tl = m - bt * p.tokens;
-    const int tk = tl + p.tok_off;
-    const int split = n / hc;
-    const int head = (n - split * hc) >> 6, e0 = n & 63;
-    const size_t hb = (size_t)bt * p.heads + head;
-    T* dst = (T*)p.dst[split];
-    T* dlo = (T*)p.dst_lo[split];
-    a += bias_a;
-    typename H::V4 h, l;
-#pragma unroll
-    for (int e = 0; e < 4; e += 2) {
-      T h0, h1, l0, l1;
-      split2_rtz(a[e], a[e + 1], h0, h1, l0, l1);
-      h[e] = h0; h[e + 1] = h1; l[e] = l0; l[e + 1] = l1;
-    }
-    if (p.transposed[split]) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const size_t o = (hb * 64 + e0 + e) * p.tpad + tk;
-        store_half_nearest(dst, dlo, o, a[e]);  // V^T: hi to nearest (the one-product P V reads it alone), lo = remainder
-      }
-    } else {
-      const size_t o = (hb * p.tpad + tk) * 64 + e0;
-      *(typename H::V4*)(dst + o) = h;
-      if (dlo) *(typename H::V4*)(dlo + o) = l;   // with 8-bit planes the fp16 lo plane is optional: the attention reads e5m2(lo 2^10) instead
-      if (p.dst8[split]) {
-        uint8_t* d8 = (uint8_t*)p.dst8[split] + (hb * p.tpad + tk) * 128 + e0;
-        const float k = VDN_LO8_SCALE;
-        *(uint32_t*)d8 = pk4_bf8(a[0], a[1], a[2], a[3]);
-        *(uint32_t*)(d8 + 64) = pk4_bf8(k * (float)l[0], k * (float)l[1], k * (float)l[2], k * (float)l[3]);
-      }
-    }
     return;
   }
   if constexpr (STORE == VDN_ST_PLAIN || STORE == VDN_ST_CONVT) {
@@ -344,18 +295,7 @@ __device__ __forceinline__ void emit4(const vdn_gemm_desc& p, int m, int n, f32x
     } else {
       o = (size_t)(p.row_group > 0 ? m + (m / p.row_group + 1) * p.row_skip : m) * p.ldc + n;
     }
-    if (p.out_dt == VDN_F32) {
-      *(f32x4*)((float*)p.out + o) = a;
-    } else if (p.out_lo) {
-      typename H::V4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { T x0, x1; split_rtz(a[e], x0, x1); h[e] = x0; l[e] = x1; }
-      *(typename H::V4*)((T*)p.out + o) = h;
-      *(typename H::V4*)((T*)p.out_lo + o) = l;
-    } else {
-      typename H::V4 h = {(T)a[0], (T)a[1], (T)a[2], (T)a[3]};
-      *(typename H::V4*)((T*)p.out + o) = h;
-    }
+    store_out4<DT>(p, o, a);
   } else if constexpr (STORE == VDN_ST_GEGLU) {
     // packed columns: 16-wide blocks alternate [h | gate]
     if ((n & 16) || n + 16 >= p.N) return;
@@ -367,20 +307,8 @@ __device__ __forceinline__ void emit4(const vdn_gemm_desc& p, int m, int n, f32x
     } else {
       a = a * gelu4(b);
     }
-    const size_t o = (size_t)m * p.ldc + ((n >> 5) << 4) + (n & 15);
-    if (p.out_dt == VDN_F32) {
-      *(f32x4*)((float*)p.out + o) = a;
-    } else if (p.out_lo) {
-      typename H::V4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { T x0, x1; split_rtz(a[e], x0, x1); h[e] = x0; l[e] = x1; }
-      *(typename H::V4*)((T*)p.out + o) = h;
-      *(typename H::V4*)((T*)p.out_lo + o) = l;
-    } else {
-      typename H::V4 h = {(T)a[0], (T)a[1], (T)a[2], (T)a[3]};
-      *(typename H::V4*)((T*)p.out + o) = h;
-    }
-  } else {  // VDN_ST_HEADS
+    store_out4<DT>(p, (size_t)m * p.ldc + ((n >> 5) << 4) + (n & 15), a);
+  } else {  // VDN_ST_HEADS, spelled out: with the decode, split and e5m2 writes in shared functions the 4-wave kernels allocate other registers
     const int hc = p.heads * 64;
     const int bt = m / p.tokens, tl = m - bt * p.tokens;
     const int tk = tl + p.tok_off;
@@ -493,13 +421,9 @@ __device__ __forceinline__ void emit8(const vdn_gemm_desc& p, int m, int n, f32x
     }
   }
   V8 h, l;
-#pragma unroll
-  for (int e = 0; e < 8; e += 2) {
-    T h0, h1, l0, l1;
-    split2_rtz(a[e], a[e + 1], h0, h1, l0, l1);
-    h[e] = h0; h[e + 1] = h1; l[e] = l0; l[e + 1] = l1;
-  }
+  split_planes(a, h, l);
   if constexpr (STORE == VDN_STX_HEADS) {
+    // (decoded here as in emit4's VDN_ST_HEADS: from a shared decode the eight V^T stores no longer share one multiply)
     const int hc = p.heads * 64;
     const int bt = m / p.tokens, tl = m - bt * p.tokens;
     const int tk = tl + p.tok_off;
@@ -515,22 +439,11 @@ __device__ __forceinline__ void emit8(const vdn_gemm_desc& p, int m, int n, f32x
         store_half_nearest(dst, dlo, o, a[e]);  // V^T: hi to nearest (the one-product P V reads it alone), lo = remainder
       }
     } else {
-      const size_t o = (hb * p.tpad + tk) * 64 + e0;
-      *(V8*)(dst + o) = h;
-      if (dlo) *(V8*)(dlo + o) = l;
-      if (p.dst8[split]) {  // e5m2 planes for the attention cross terms
-        uint8_t* d8 = (uint8_t*)p.dst8[split] + (hb * p.tpad + tk) * 128 + e0;
-        *(u32x2*)d8 = u32x2{pk4_bf8(a[0], a[1], a[2], a[3]), pk4_bf8(a[4], a[5], a[6], a[7])};
-        const float k = VDN_LO8_SCALE;
-        *(u32x2*)(d8 + 64) = u32x2{pk4_bf8(k * (float)l[0], k * (float)l[1], k * (float)l[2], k * (float)l[3]),
-                                   pk4_bf8(k * (float)l[4], k * (float)l[5], k * (float)l[6], k * (float)l[7])};
-      }
+      store_planes(dst, dlo, (hb * p.tpad + tk) * 64 + e0, h, l);
+      if (p.dst8[split]) store_bf8<8>((uint8_t*)p.dst8[split] + (hb * p.tpad + tk) * 128 + e0, a, l);  // e5m2 planes for the attention cross terms
     }
-  } else {
-    // out_kt (8-bit cross-term kernel): planes written K-tile-major for the next GEMM ([N/32][M][32] halves, [N/64][M][64] bytes)
-    const size_t o = p.out_kt ? ((size_t)(n >> 5) * p.M + m) * 32 + (n & 31) : (size_t)m * p.ldc + n;
-    *(V8*)((T*)p.out + o) = h;
-    if (p.out_lo) *(V8*)((T*)p.out_lo + o) = l;
+  } else {  // out_kt (8-bit cross-term kernel): planes written K-tile-major for the next GEMM
+    store_out_planes<true, T>(p, kt_half_offset(p.out_kt, m, n, p.M, p.ldc), h, l);
   }
 }
 
@@ -550,45 +463,45 @@ __device__ __forceinline__ void epilogue_regs(f32x4 (&acc)[TM][TN], const vdn_ge
 #pragma unroll
       for (int u = 0; u < TN / 2; ++u)
         emit8<DT, STORE>(p, mw + i * 16 + fr, nw + u * 32 + fq * 8, acc[i][2 * u], acc[i][2 * u + 1], bias4[2 * u], bias4[2 * u + 1]);
-    return;
-  }
+  } else {
 #pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = nw + j * 16 + fq * 4;
-    bias4[j] = (p.bias && n < p.N) ? *(const f32x4*)(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-    gam4[j] = (p.gamma && n < p.N) ? *(const f32x4*)(p.gamma + n) : f32x4{1.f, 1.f, 1.f, 1.f};
-  }
-  if constexpr (STORE == VDN_STX_RES) {
-    // residual rows are fetched one 16-row slab AHEAD of the stores: a load issued after a store waits for
-    // that store's acknowledgement (vmcnt counts both on gfx9), which serialised every group on a round trip
-    f32x4 r[2][TN];
-    auto fetch = [&](int i, f32x4 (&dst)[TN]) {
-      const int m = mw + i * 16 + fr;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = nw + j * 16 + fq * 4;
-        dst[j] = (m < p.M && n < p.N) ? *(const f32x4*)((const float*)p.res1 + (size_t)m * p.ldr1 + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    };
-    fetch(0, r[0]);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      if (i + 1 < TM) fetch(i + 1, r[(i + 1) & 1]);
-      const int m = mw + i * 16 + fr;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = nw + j * 16 + fq * 4;
-        if (m < p.M && n < p.N) *(f32x4*)((float*)p.out + (size_t)m * p.ldc + n) = (acc[i][j] + bias4[j]) * gam4[j] + r[i & 1][j];
-      }
+    for (int j = 0; j < TN; ++j) {
+      const int n = nw + j * 16 + fq * 4;
+      bias4[j] = (p.bias && n < p.N) ? *(const f32x4*)(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+      gam4[j] = (p.gamma && n < p.N) ? *(const f32x4*)(p.gamma + n) : f32x4{1.f, 1.f, 1.f, 1.f};
     }
-    return;
+    if constexpr (STORE == VDN_STX_RES) {
+      // residual rows are fetched one 16-row slab AHEAD of the stores: a load issued after a store waits for
+      // that store's acknowledgement (vmcnt counts both on gfx9), which serialised every group on a round trip
+      f32x4 r[2][TN];
+      auto fetch = [&](int i, f32x4 (&dst)[TN]) {
+        const int m = mw + i * 16 + fr;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          const int n = nw + j * 16 + fq * 4;
+          dst[j] = (m < p.M && n < p.N) ? *(const f32x4*)((const float*)p.res1 + (size_t)m * p.ldr1 + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      };
+      fetch(0, r[0]);
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        if (i + 1 < TM) fetch(i + 1, r[(i + 1) & 1]);
+        const int m = mw + i * 16 + fr;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          const int n = nw + j * 16 + fq * 4;
+          if (m < p.M && n < p.N) *(f32x4*)((float*)p.out + (size_t)m * p.ldc + n) = (acc[i][j] + bias4[j]) * gam4[j] + r[i & 1][j];
+        }
+      }
+      return;
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+        emit4<DT, STORE>(p, mw + i * 16 + fr, nw + j * 16 + fq * 4, acc[i][j], acc[i][j + 1 < TN ? j + 1 : j], bias4[j],
+                         bias4[j + 1 < TN ? j + 1 : j], gam4[j]);
   }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-      emit4<DT, STORE>(p, mw + i * 16 + fr, nw + j * 16 + fq * 4, acc[i][j], acc[i][j + 1 < TN ? j + 1 : j], bias4[j],
-                       bias4[j + 1 < TN ? j + 1 : j], gam4[j]);
 }
 
 // Sub-pixel convolution epilogue (8-wave kernels, paired columns): the bias of a row is the sum of its phase's per-neighbour
@@ -639,16 +552,8 @@ __device__ __forceinline__ void epilogue_subpix(f32x4 (&acc)[TM][4], const vdn_g
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       V8 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; e += 2) {
-        T h0, h1, l0, l1;
-        split2_rtz(acc[i][2 * u][e], acc[i][2 * u][e + 1], h0, h1, l0, l1);
-        h[e] = h0; h[e + 1] = h1; l[e] = l0; l[e + 1] = l1;
-        split2_rtz(acc[i][2 * u + 1][e], acc[i][2 * u + 1][e + 1], h0, h1, l0, l1);
-        h[4 + e] = h0; h[5 + e] = h1; l[4 + e] = l0; l[5 + e] = l1;
-      }
-      *(V8*)((T*)p.out + ob[i] + u * 32) = h;
-      *(V8*)((T*)p.out_lo + ob[i] + u * 32) = l;
+      split_planes(acc[i][2 * u], acc[i][2 * u + 1], h, l);
+      store_out_planes<false, T>(p, ob[i] + u * 32, h, l);
     }
   }
 }

@@ -358,26 +358,16 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
             const f32x4 g0 = gelu4(f32x4{acc[i][j][8 * u], acc[i][j][8 * u + 1], acc[i][j][8 * u + 2], acc[i][j][8 * u + 3]} + bias8[j][u][0]);
             const f32x4 g1 = gelu4(f32x4{acc[i][j][8 * u + 4], acc[i][j][8 * u + 5], acc[i][j][8 * u + 6], acc[i][j][8 * u + 7]} + bias8[j][u][1]);
             V8 hh, ll;
-#pragma unroll
-            for (int e = 0; e < 4; e += 2) {
-              _Float16 h0, h1, l0, l1;
-              split2_rtz(g0[e], g0[e + 1], h0, h1, l0, l1);
-              hh[e] = h0; hh[e + 1] = h1; ll[e] = l0; ll[e + 1] = l1;
-              split2_rtz(g1[e], g1[e + 1], h0, h1, l0, l1);
-              hh[4 + e] = h0; hh[5 + e] = h1; ll[4 + e] = l0; ll[5 + e] = l1;
-            }
+            split_planes(g0, g1, hh, ll);
 #pragma unroll
             for (int e = 0; e < 8; ++e) { hv[16 * j + 8 * u + e] = hh[e]; lv[16 * j + 8 * u + e] = ll[e]; }
             const int n = nw + 32 * j + 16 * u + 8 * h;
-            if (m < p.M && n < p.N) {
-              const size_t o = p.out_kt ? ((size_t)(n >> 5) * p.M + m) * 32 + (n & 31) : (size_t)m * p.ldc + n;
-              *(V8*)((_Float16*)p.out + o) = hh;
-              if (p.out_lo) *(V8*)((_Float16*)p.out_lo + o) = ll;
-            }
+            if (m < p.M && n < p.N)
+              store_planes((_Float16*)p.out, (_Float16*)p.out_lo, kt_half_offset(p.out_kt, m, n, p.M, p.ldc), hh, ll);
           }
         if (m < p.M && nw < p.N) {
           const int sb = x6_scale_byte(hv);
-          uint8_t* d8 = (uint8_t*)p.out8 + (p.out_kt ? ((size_t)(nw >> 6) * p.M + m) * 64 : (size_t)m * p.ldc + nw) + 32 * h;
+          uint8_t* d8 = (uint8_t*)p.out8 + kt_byte_offset(p.out_kt, m, nw, h, p.M, p.ldc);
           x6_store_half(d8, hv, sb);
           x6_store_half(d8 + (size_t)p.M * p.ldc, lv, sb - 10);
         }
@@ -424,7 +414,7 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
             }
             V8 hh[2], ll[2];
 #pragma unroll
-            for (int e = 0; e < 16; e += 2) {
+            for (int e = 0; e < 16; e += 2) {   // (spelled out: on the planes.hpp split and e5m2 writer this kernel goes 252 -> 256 VGPRs and into scratch)
               _Float16 h0, h1, l0, l1;
               split2_rtz(o[e], o[e + 1], h0, h1, l0, l1);
               hh[e >> 3][e & 7] = h0; hh[e >> 3][(e & 7) + 1] = h1; ll[e >> 3][e & 7] = l0; ll[e >> 3][(e & 7) + 1] = l1;
@@ -460,22 +450,10 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] = acc[i][j][8 * u + e] + bias8[j][u][0][e]; v[4 + e] = acc[i][j][8 * u + 4 + e] + bias8[j][u][1][e]; }
             V8 hh, ll;
-#pragma unroll
-            for (int e = 0; e < 8; e += 2) {
-              _Float16 h0, h1, l0, l1;
-              split2_rtz(v[e], v[e + 1], h0, h1, l0, l1);
-              hh[e] = h0; hh[e + 1] = h1; ll[e] = l0; ll[e + 1] = l1;
-            }
-            if (m < p.M) {
-              const size_t o = row * 64 + 32 * j + 16 * u + 8 * h;
-              *(V8*)(dst + o) = hh;
-              if (dlo) *(V8*)(dlo + o) = ll;
-            }
-            const float k = VDN_LO8_SCALE;
-            hi8[j][u][0] = pk4_bf8(v[0], v[1], v[2], v[3]);
-            hi8[j][u][1] = pk4_bf8(v[4], v[5], v[6], v[7]);
-            lo8[j][u][0] = pk4_bf8(k * (float)ll[0], k * (float)ll[1], k * (float)ll[2], k * (float)ll[3]);
-            lo8[j][u][1] = pk4_bf8(k * (float)ll[4], k * (float)ll[5], k * (float)ll[6], k * (float)ll[7]);
+            split_planes(v, hh, ll);
+            if (m < p.M) store_planes(dst, dlo, row * 64 + 32 * j + 16 * u + 8 * h, hh, ll);
+            pack_bf8<8>(v, hi8[j][u]);
+            pack_bf8_lo<8>(ll, lo8[j][u]);
           }
         // after the swap: lanes h = 0 hold (own, partner's) group of block j = 0, lanes h = 1 (partner's, own) of block j = 1
         u32x4 bh[2], bl[2];   // 32 bytes of each plane: [u0 h0 | u0 h1], [u1 h0 | u1 h1]

@@ -1,5 +1,5 @@
 // Normalisation / elementwise kernels (HBM-bound; one pass over the data, 8-16 B per lane).
-#include "common.hpp"
+#include "planes.hpp"
 #include "reduce.hpp"
 
 namespace {
@@ -87,11 +87,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const XT* __restrict__ x
           if (out_f) *(f32x4*)(out_f + orow * C + c) = y;
           if (out_h) {
             typename Half<DT>::V4 hv, lv;
-            // kt: K-tile-major planes for the 8-bit cross-term GEMM (include/vdn.h a_kt): [C/32][rows][32] halves, [C/64][rows][64] bytes
-            const size_t oh = kt ? ((size_t)(c >> 5) * rows + orow) * 32 + (c & 31) : orow * C + c;
+            const size_t oh = kt_half_offset(kt, orow, c, rows, C);   // kt: include/vdn.h a_kt
             if (out_l || out8) {
 #pragma unroll
-              for (int e = 0; e < 4; e += 2) {
+              for (int e = 0; e < 4; e += 2) {   // (the pair loop itself, not split_planes: with it the bf16 NV = 2 kernel takes 70 -> 72 VGPRs)
                 T h0, h1, l0, l1;
                 split2_rtz(y[e], y[e + 1], h0, h1, l0, l1);
                 hv[e] = h0; hv[e + 1] = h1; lv[e] = l0; lv[e + 1] = l1;
@@ -133,8 +132,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const XT* __restrict__ x
                 for (int e = 0; e < 8; ++e) xv[8 * q + e] = a[e];
               }
             } else xv = hv;
-            uint8_t* d8 = out8 + (size_t)plane * rows * C +
-                          (kt ? ((size_t)(hb >> 1) * rows + orow) * 64 + 32 * (hb & 1) : orow * C + (size_t)hb * 32);
+            uint8_t* d8 = out8 + (size_t)plane * rows * C + kt_byte_offset(kt, orow, (hb >> 1) * 64, hb & 1, rows, C);
             x6_store_half(d8, xv, plane ? sb - 10 : sb);
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // staging reads done before the next row overwrites it
@@ -264,6 +262,7 @@ __global__ __launch_bounds__(256) void groupnorm_apply_kernel(const typename Hal
       const int c = c0 + e, g = c / cg;
       const float xv = xl ? (float)v[e] + (float)vl[e] : (float)v[e];
       const float r = (xv - mr[2 * g]) * mr[2 * g + 1] * w[c] + b[c];
+      // value by value (not split_planes on all 8): with the 8 results live at once the kernel takes 47 -> 62 VGPRs
       if (yl) { T a, b2; split_rtz(r, a, b2); o[e] = a; ol[e] = b2; }
       else o[e] = (T)r;
     }
@@ -295,13 +294,8 @@ __global__ void addtab_cast_kernel(const float* __restrict__ x, const float* __r
     f32x4 a = *(const f32x4*)(x + row * C + c);
     if (tab) a += *(const f32x4*)(tab + (size_t)((row / tab_div) % tab_mod) * C + c);
     typename Half<DT>::V4 h, l;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (yl) { T x0, x1; split_rtz(a[e], x0, x1); h[e] = x0; l[e] = x1; }
-      else h[e] = (T)a[e];
-    }
-    *(typename Half<DT>::V4*)(y + row * C + c) = h;
-    if (yl) *(typename Half<DT>::V4*)(yl + row * C + c) = l;
+    split_or_round(yl != nullptr, a, h, l);
+    store_planes(y, yl, row * C + c, h, l);
   }
 }
 

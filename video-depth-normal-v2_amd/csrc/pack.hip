@@ -2,7 +2,7 @@
 // the layouts torch.nn keeps them, -> the K-contiguous 16-bit (hi [, lo]) planes vdn_gemm / vdn_depth_tail read.
 // A host in any language can therefore feed libvdn_hip.so from a raw checkpoint without Python. One thread per output
 // element computes its source index from the layout kind; K is zero padded to the plane stride `ldb`.
-#include "common.hpp"
+#include "planes.hpp"
 
 namespace {
 
@@ -162,11 +162,12 @@ __global__ __launch_bounds__(256) void pack_x8_kernel(const _Float16* __restrict
       }
     }
     if (hi_kt) {  // natural column order: K tile 2 slab + h of this row
-      _Float16* d = hi_kt + ((size_t)(2 * slab + h) * rows + r) * 32;
+      _Float16* d = hi_kt + kt_half_offset(1, r, (2 * slab + h) * 32, rows, ld);
 #pragma unroll
       for (int q = 0; q < 4; ++q) *(f16x8*)(d + 8 * q) = *(const f16x8*)(hr + 32 * h + 8 * q);
     }
     const int sb = x6_scale_byte(hv);
+    // kt_byte_offset(kt, r, slab * 64, h, rows, ld), written out: through the function the natural-order kernel takes 60 -> 62 VGPRs
     uint8_t* d8 = p8 + (kt ? ((size_t)slab * rows + r) * 64 + 32 * h : (size_t)r * ld + slab * 64 + 32 * h);
     x6_store_half(d8, hv, sb);
     x6_store_half(d8 + (size_t)rows * ld, lv, sb - 10);
@@ -181,17 +182,15 @@ __global__ __launch_bounds__(256) void pack_x8_f32_kernel(const float* __restric
     const int r = (int)(i / (ld >> 5)), hb = (int)(i - (size_t)r * (ld >> 5));
     const float* xr = x + (size_t)r * ld + hb * 32;
     f16x32 hv, lv;
+    float v[32];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const f32x4 a = *(const f32x4*)(xr + 4 * q);
 #pragma unroll
-      for (int e = 0; e < 4; e += 2) {
-        _Float16 h0, h1, l0, l1;
-        split2_rtz(a[e], a[e + 1], h0, h1, l0, l1);
-        hv[4 * q + e] = h0; hv[4 * q + e + 1] = h1; lv[4 * q + e] = l0; lv[4 * q + e + 1] = l1;
-      }
+      for (int e = 0; e < 4; ++e) v[4 * q + e] = a[e];
     }
-    _Float16* d = hi_kt + ((size_t)hb * rows + r) * 32;
+    split_planes(v, hv, lv);
+    _Float16* d = hi_kt + kt_half_offset(1, r, hb * 32, rows, ld);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       f16x8 o;
@@ -200,7 +199,7 @@ __global__ __launch_bounds__(256) void pack_x8_f32_kernel(const float* __restric
       *(f16x8*)(d + 8 * q) = o;
     }
     const int sb = x6_scale_byte(hv);
-    uint8_t* d8 = p8 + ((size_t)(hb >> 1) * rows + r) * 64 + 32 * (hb & 1);
+    uint8_t* d8 = p8 + kt_byte_offset(1, r, (hb >> 1) * 64, hb & 1, rows, ld);
     x6_store_half(d8, hv, sb);
     x6_store_half(d8 + (size_t)rows * ld, lv, sb - 10);
   }

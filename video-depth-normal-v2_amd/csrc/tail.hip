@@ -27,7 +27,7 @@
 //          One expf and one division per OUTPUT pixel, after 73.7 kFLOP of MFMA for that pixel at C = 128: the quarter
 //          rate of a transcendental does not show, so the exact expf is used rather than an exp2 of a rounded product.
 // Roofline: MFMA (19.8 GF per 518 x 518 frame at C = 128, x3 executed); HBM traffic = out1 once (+ halo) + depth.
-#include "common.hpp"
+#include "planes.hpp"
 #include "resample.hpp"
 
 namespace {
@@ -144,20 +144,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           a00[u] = *(const f32x4*)(c00 + 4 * u); a01[u] = *(const f32x4*)(c01 + 4 * u);
           a10[u] = *(const f32x4*)(c10 + 4 * u); a11[u] = *(const f32x4*)(c11 + 4 * u);
         }
+        float r[8];
 #pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-          float r[2];
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int u = (e + q) >> 2, k = (e + q) & 3;
-            const float top = (1.f - lx) * a00[u][k] + lx * a01[u][k];
-            const float bot = (1.f - lx) * a10[u][k] + lx * a11[u][k];
-            r[q] = (1.f - ly) * top + ly * bot;
-          }
-          T h0, h1, q0, q1;
-          split2_rtz(r[0], r[1], h0, h1, q0, q1);
-          oh[e] = h0; oh[e + 1] = h1; ol[e] = q0; ol[e + 1] = q1;
+        for (int e = 0; e < 8; ++e) {
+          const int u = e >> 2, k = e & 3;
+          const float top = (1.f - lx) * a00[u][k] + lx * a01[u][k];
+          const float bot = (1.f - lx) * a10[u][k] + lx * a11[u][k];
+          r[e] = (1.f - ly) * top + ly * bot;
         }
+        split_planes(r, oh, ol);
       }
       const int off = (py * PWS + px) * 64 + ((ch ^ ((py + (px >> 2)) & 3)) << 4);
       *(V8*)(smem + off) = oh;

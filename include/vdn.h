@@ -768,6 +768,36 @@ int vdn_refine_normalize(const float* x, float max_depth, float* out, size_t n, 
 int vdn_refine_mix(const float* depth, const float* x, float a0, float a1, float c0, float a2, float c1, float* out, size_t n,
                    vdn_stream stream);
 
+/* The end of one window of the refiners' clip driver (refiner.refine_video_depth: models/video_depth_model_v5.py:215-283 on
+ * depth windows), in one launch. A window's T slots show the clip frames slots[0..T): copies of the previous window's
+ * keyframes, new frames, padding; the finish of slot t needs the scaled input of THAT frame, scaled[slots[t]], which the
+ * driver keeps once per clip frame. For slot t and output pixel (oy, ox):
+ *   d   = (IH, IW) == (OH, OW) ? net[t][oy][ox]
+ *                              : max(bilinear align-corners sample of net[t] at (oy, ox), 0)   (v5:184-185; the pixel of
+ *                                vdn_upsample_bilinear_f32(relu = 1), never stored at full resolution)
+ *   out[t][oy][ox] =
+ *     VDN_TAIL_SHIFT, residual != 0   (scaled[f] + (c0 * d + c1)) * c2      c0, c1 = the shift head's weight and bias, c2 =
+ *                                     max_depth or 1 (v5:188-192, v4:144-148, v3:203-204): the pixel of vdn_refine_finish
+ *     VDN_TAIL_SHIFT, residual == 0   d * c2; scaled is not read and may be NULL
+ *     VDN_TAIL_MIX                    relu(c3 * relu(c0 * d + c1 * scaled[f] + c2) + c4), (c0 .. c4) = vdn_refine_mix's (a0, a1,
+ *                                     c0, a2, c1) (v2:96-98); residual is ignored
+ * with f = slots[t]. net f32 [T, IH, IW] is the head's rectified map, scaled f32 [frames, OH, OW], slots int32 [T] in device
+ * memory with every entry in [0, frames) (the caller checks the table on the host before it uploads it; an entry outside the
+ * range reads nothing and fills its slot with NaN), out f32 [T, OH, OW], overlapping no input. The pixel expressions are the
+ * three entries' own device functions, so out has the bits of: gather scaled by slots, vdn_upsample_bilinear_f32(relu = 1) where
+ * the sizes differ, vdn_refine_finish / vdn_refine_mix.
+ * Load shapes: where OW is a multiple of 4 and the bases read or written in place are 16-byte aligned, a lane handles four
+ * pixels of a row per 16-byte access; one pixel otherwise. The values are the same either way.
+ * vdn_refine_window_tail_trip(wide): the pixels of one slot that one trip of the grid covers (64 blocks x 256 lanes x 4 or 1); a
+ * larger frame sends the lanes round their stride loop again.
+ * Errors, all returned before anything is launched. VDN_EINVAL: a null required pointer, a size <= 0, T > 65535, an unknown
+ * kind. VDN_EUNSUPPORTED: OH * OW or IH * IW above INT32_MAX. VDN_EALIGN: a pointer off 4 bytes.                        */
+enum { VDN_TAIL_SHIFT = 0, VDN_TAIL_MIX = 1 };
+int vdn_refine_window_tail_trip(int wide);
+int vdn_refine_window_tail(const float* net, int IH, int IW, const float* scaled, int frames, const int32_t* slots, int T,
+                           int OH, int OW, int kind, int residual, float c0, float c1, float c2, float c3, float c4,
+                           float* out, vdn_stream stream);
+
 /* Fused depth tail (depth_anything_v2/dpt.py:146-151; video_depth_anything/dpt_temporal.py:106-111 runs the same ops
  * in micro-batches): bilinear resize (align_corners=True) of the fp32 NHWC map x [B, IH, IW, C] (output_conv1's result,
  * written as ONE fp32 plane) to (OH, OW), Conv3x3(C -> 32, pad 1) + bias2 + ReLU, Conv1x1(32 -> 1) + b1 [+ ReLU when

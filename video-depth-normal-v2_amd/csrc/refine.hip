@@ -13,8 +13,15 @@
 //   vdn_refine_normalize — x / max_depth, a true fp32 division (v2 has no scale head, so no median is computed for it);
 //   vdn_refine_mix    — relu(a2 * relu(a0 * depth + a1 * x + c0) + c1): v2's final_res (Conv2d(2,1,1) - BatchNorm - ReLU -
 //                       Conv2d(1,1,1) - BatchNorm - ReLU) with the eval-mode BatchNorms folded on the host, NaN in -> NaN out.
+//   vdn_refine_window_tail — the end of one window of the clip driver (refiner.refine_video_depth): for window slot t, which
+//                       shows clip frame f = slots[t], the head's rectified map of slot t sampled at the output pixel
+//                       (ac_sample_f32 of resample.hpp, rectified again; or read in place at equal sizes), then the finish
+//                       (finish_px) or the mix (MixOp) against scaled[f], the frame of the clip-level scaled input. The
+//                       pixel functions are those of vdn_upsample_bilinear_f32, vdn_refine_finish and vdn_refine_mix, so the
+//                       result has the bits of gather -> upsample -> finish without the gathered and the resized window.
 // All one pass over HBM.
 #include "common.hpp"
+#include "resample.hpp"
 #include "select.hpp"
 
 namespace {
@@ -91,13 +98,40 @@ __global__ __launch_bounds__(256) void refine_pack_kernel(const float* __restric
   }
 }
 
+// the shift finish on one pixel: (scaled + (w * depth + b)) * max_depth. w * depth + b is ONE fused operation, the sum and the
+// product are rounded on their own: what hipcc has always made of refine_finish_kernel's __fadd_rn(__fmul_rn(d, w), b) (the _rn
+// intrinsics are plain operators to it, and it contracts them), written out under contract(off) so that every caller, the window
+// tail included, gets these roundings whatever the compiler would choose there.
+__device__ __forceinline__ float finish_px(float s, float d, float w, float b, float max_depth) {
+#pragma clang fp contract(off)
+  return (s + fmaf(d, w, b)) * max_depth;
+}
+// without the residual: depth * max_depth
+__device__ __forceinline__ float finish_px(float d, float max_depth) { return d * max_depth; }
+
 __global__ __launch_bounds__(256) void refine_finish_kernel(const float* __restrict__ scaled, const float* __restrict__ depth, float w,
                                                             float b, float max_depth, int residual, float* __restrict__ out,
                                                             size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const float d = depth[i];
-    out[i] = residual ? __fmul_rn(__fadd_rn(scaled[i], __fadd_rn(__fmul_rn(d, w), b)), max_depth) : __fmul_rn(d, max_depth);
+    out[i] = residual ? finish_px(scaled[i], d, w, b, max_depth) : finish_px(d, max_depth);
   }
+}
+
+template <int PPL>
+__device__ __forceinline__ void load_px(const float* p, int i, float (&v)[PPL]) {
+  if constexpr (PPL == 4) {
+    const f32x4 q = *(const f32x4*)(p + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = q[j];
+  } else {
+    v[0] = p[i];
+  }
+}
+template <int PPL>
+__device__ __forceinline__ void store_px(float* p, int i, const float (&v)[PPL]) {
+  if constexpr (PPL == 4) *(f32x4*)(p + i) = f32x4{v[0], v[1 % PPL], v[2 % PPL], v[3 % PPL]};
+  else p[i] = v[0];
 }
 
 // v2's folded final_res on one pixel; the comparison (not fmaxf) keeps torch.relu's NaN: NaN < 0 is false
@@ -139,6 +173,76 @@ __global__ __launch_bounds__(256) void elementwise_kernel(const float* __restric
     if constexpr (Op::kInputs == 2) vb = b[j];
     out[j] = op(a[j], vb);
   }
+}
+
+// The window tail's finish kinds as (depth, scaled) -> out functors; kInputs == 1 never reads `scaled`.
+struct ShiftOp {
+  static constexpr int kInputs = 2;
+  float w, b, max_depth;
+  __device__ __forceinline__ float operator()(float d, float s) const { return finish_px(s, d, w, b, max_depth); }
+};
+struct UnitOp {
+  static constexpr int kInputs = 1;
+  float max_depth;
+  __device__ __forceinline__ float operator()(float d, float) const { return finish_px(d, max_depth); }
+};
+
+// One window: block (b, t) owns the pixels (b * 256 + lane) * PPL + k * trip of slot t, trip = WT_BPS * 256 * PPL; PPL = 4 where
+// a row is a multiple of 4 pixels and the bases are 16-byte aligned (the host decides), so a lane's four pixels lie in one row
+// and go as one 16-byte load per input and one 16-byte store. RESAMPLE: net is [T, IH, IW] and is sampled; otherwise it has
+// the output's size and is read in place. A slot outside [0, frames) (the host range-checks the table, so: a corrupted one)
+// reads nothing of `scaled` and writes NaN, which the driver's range check reports.
+constexpr int WT_BPS = 64;  // blocks per window slot
+template <class Op, bool RESAMPLE, int PPL>
+__global__ __launch_bounds__(256) void refine_window_tail_kernel(const float* __restrict__ net, int IH, int IW,
+                                                                 const float* __restrict__ scaled, int frames,
+                                                                 const int32_t* __restrict__ slots, int OH, int OW,
+                                                                 float* __restrict__ out, Op op) {
+  const int t = blockIdx.y, f = slots[t];
+  const bool bad = (unsigned)f >= (unsigned)frames;
+  const int n = OH * OW;
+  const float* nb = net + (size_t)t * (RESAMPLE ? (size_t)IH * IW : (size_t)n);
+  const float* sb = scaled + (size_t)(bad ? 0 : f) * n;   // not dereferenced when Op::kInputs == 1 (scaled may be null) or bad
+  float* ob = out + (size_t)t * n;
+  const float sy = ac_scale(IH, OH), sx = ac_scale(IW, OW);
+  const int trip = WT_BPS * 256 * PPL;
+  for (int64_t q64 = (int64_t)(blockIdx.x * 256 + (int)threadIdx.x) * PPL; q64 < n; q64 += trip) {
+    const int q = (int)q64;
+    float d[PPL], s[PPL] = {}, o[PPL];
+    if constexpr (RESAMPLE) {
+      const int oy = q / OW, ox = q - oy * OW;
+#pragma unroll
+      for (int j = 0; j < PPL; ++j) d[j] = ac_sample_f32(nb, IH, IW, oy, ox + j, sy, sx, 1);
+    } else {
+      load_px<PPL>(nb, q, d);
+    }
+    if constexpr (Op::kInputs == 2) {
+      if (!bad) load_px<PPL>(sb, q, s);
+    }
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) o[j] = bad ? __builtin_nanf("") : op(d[j], s[j]);
+    store_px<PPL>(ob, q, o);
+  }
+}
+
+template <class Op>
+int launch_window_tail(const float* net, int IH, int IW, const float* scaled, int frames, const int32_t* slots, int T, int OH, int OW,
+                       float* out, Op op, vdn_stream stream) {
+  const bool resample = IH != OH || IW != OW;
+  const uintptr_t bases = (uintptr_t)out | (Op::kInputs == 2 ? (uintptr_t)scaled : 0) | (resample ? 0 : (uintptr_t)net);
+  const bool wide = OW % 4 == 0 && (bases & 15) == 0;
+  const dim3 grid(WT_BPS, T), block(256);
+  hipStream_t s = (hipStream_t)stream;
+#define VDN_WT(R, P) \
+  hipLaunchKernelGGL((refine_window_tail_kernel<Op, R, P>), grid, block, 0, s, net, IH, IW, scaled, frames, slots, OH, OW, out, op)
+  if (resample) {
+    if (wide) VDN_WT(true, 4); else VDN_WT(true, 1);
+  } else {
+    if (wide) VDN_WT(false, 4); else VDN_WT(false, 1);
+  }
+#undef VDN_WT
+  VDN_CHECK_LAUNCH();
+  return VDN_OK;
 }
 
 template <class Op>
@@ -213,4 +317,20 @@ extern "C" int vdn_refine_mix(const float* depth, const float* x, float a0, floa
                               size_t n, vdn_stream stream) {
   if (!depth || !x || !out || n == 0) return VDN_EINVAL;
   return launch_elementwise(depth, x, out, n, MixOp{a0, a1, c0, a2, c1}, stream);
+}
+
+extern "C" int vdn_refine_window_tail_trip(int wide) { return WT_BPS * 256 * (wide ? 4 : 1); }
+
+extern "C" int vdn_refine_window_tail(const float* net, int IH, int IW, const float* scaled, int frames, const int32_t* slots, int T,
+                                      int OH, int OW, int kind, int residual, float c0, float c1, float c2, float c3, float c4,
+                                      float* out, vdn_stream stream) {
+  if (!net || !slots || !out || T <= 0 || T > 65535 || frames <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return VDN_EINVAL;
+  if (kind != VDN_TAIL_SHIFT && kind != VDN_TAIL_MIX) return VDN_EINVAL;
+  if ((kind == VDN_TAIL_MIX || residual) && !scaled) return VDN_EINVAL;
+  if ((size_t)OH * OW > (size_t)INT32_MAX || (size_t)IH * IW > (size_t)INT32_MAX) return VDN_EUNSUPPORTED;
+  if (((uintptr_t)net | (uintptr_t)scaled | (uintptr_t)out | (uintptr_t)slots) & 3) return VDN_EALIGN;
+  if (kind == VDN_TAIL_MIX)
+    return launch_window_tail(net, IH, IW, scaled, frames, slots, T, OH, OW, out, MixOp{c0, c1, c2, c3, c4}, stream);
+  if (residual) return launch_window_tail(net, IH, IW, scaled, frames, slots, T, OH, OW, out, ShiftOp{c0, c1, c2}, stream);
+  return launch_window_tail(net, IH, IW, nullptr, frames, slots, T, OH, OW, out, UnitOp{c2}, stream);
 }

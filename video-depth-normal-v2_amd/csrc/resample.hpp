@@ -44,7 +44,8 @@ __host__ __device__ __forceinline__ AcCoord ac_coord(int o, float scale, int in)
 }
 
 // (1 - ly) ((1 - lx) a00 + lx a01) + ly ((1 - lx) a10 + lx a11) on floats, under contract(fast): which products are
-// fused into the sums is the compiler's choice per call site. upsample_kernel and upsample_f32_kernel only: in
+// fused into the sums is the compiler's choice per call site. upsample_kernel only (ac_sample_f32 below is the fp32 map's,
+// with the roundings pinned): in
 // depth_tail_kernel and dn_tail_kernel a call of this function changes that choice and with it the last bit of the result,
 // so they keep the expression in place; oc1_combine_kernel's four corner weights and resize_bilinear_hp_kernel's separately
 // rounded products are other expressions, on purpose.
@@ -54,6 +55,28 @@ __device__ __forceinline__ T bilerp(T a00, T a01, T a10, T a11, float lx, float 
   const T top = (1.f - lx) * a00 + lx * a01;
   const T bot = (1.f - lx) * a10 + lx * a11;
   return (1.f - ly) * top + ly * bot;
+}
+
+// One output pixel (oy, ox) of the align-corners bilinear resize of the fp32 map xb [IH, IW], rounded weights, rectified when
+// relu != 0 (fmaxf: a NaN sample becomes 0): the pixel of upsample_f32_kernel, and of refine_window_tail_kernel, which
+// samples the head's map where it finishes a window and never stores the resized one. sy, sx = ac_scale of the two axes.
+// The blend is bilerp's expression with its roundings WRITTEN OUT, under contract(off): the ones hipcc chose for
+// upsample_f32_kernel while that kernel held a call of bilerp (it packs the two rows into one v_pk_fma_f32 pair, hence the
+// mirrored rows: the upper row rounds its left product, the lower row its right one, and both products of the last line are
+// rounded). A second caller of bilerp gets other fusions (measured: one v_fmac per line), so the two kernels would differ
+// in the last bit; written out, both give the bits upsample_f32_kernel has always given (profiles/refine_clip.md).
+__device__ __forceinline__ float ac_sample_f32(const float* __restrict__ xb, int IH, int IW, int oy, int ox, float sy, float sx,
+                                               int relu) {
+#pragma clang fp contract(off)
+  const auto [y0, y1, ly] = ac_coord<AcWeight::rounded>(oy, sy, IH);
+  const auto [x0, x1, lx] = ac_coord<AcWeight::rounded>(ox, sx, IW);
+  const float a00 = xb[y0 * IW + x0], a01 = xb[y0 * IW + x1], a10 = xb[y1 * IW + x0], a11 = xb[y1 * IW + x1];
+  const float mx = 1.f - lx, my = 1.f - ly;
+  const float top = fmaf(lx, a01, mx * a00);
+  const float bot = fmaf(mx, a10, lx * a11);
+  float v = my * top + ly * bot;
+  if (relu) v = fmaxf(v, 0.f);
+  return v;
 }
 
 // Half-pixel source position (dst + 0.5) * scale - 0.5 with scale = in / out (or 1 / scale_factor), fused: the float32

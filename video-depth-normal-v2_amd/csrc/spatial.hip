@@ -59,12 +59,7 @@ __global__ __launch_bounds__(256) void upsample_f32_kernel(const float* __restri
     const size_t t = i / OW;
     const int oy = (int)(t % OH);
     const int b = (int)(t / OH);
-    const auto [y0, y1, ly] = ac_coord<AcWeight::rounded>(oy, sy, IH);
-    const auto [x0, x1, lx] = ac_coord<AcWeight::rounded>(ox, sx, IW);
-    const float* xb = x + (size_t)b * IH * IW;
-    float v = bilerp(xb[y0 * IW + x0], xb[y0 * IW + x1], xb[y1 * IW + x0], xb[y1 * IW + x1], lx, ly);
-    if (relu) v = fmaxf(v, 0.f);
-    y[i] = v;
+    y[i] = ac_sample_f32(x + (size_t)b * IH * IW, IH, IW, oy, ox, sy, sx, relu);
   }
 }
 

@@ -15,6 +15,7 @@ A_PLAIN, A_CONV3X3 = 0, 1
 ST_PLAIN, ST_HEADS, ST_CONVT, ST_GEGLU = 0, 1, 2, 3
 EVAL_DEPTH, EVAL_DISP = 0, 1
 EVAL_TGM_ROWS, EVAL_TGM_FRAMES = 0, 1
+TAIL_SHIFT, TAIL_MIX = 0, 1   # finish of vdn_refine_window_tail (include/vdn.h VDN_TAIL_*)
 PACK_LINEAR, PACK_CONV3X3, PACK_CONV3X3_TAPS, PACK_CONVT, PACK_GEGLU, PACK_ROPE = 0, 1, 2, 3, 4, 5
 
 i32, vp, fp = C.c_int32, C.c_void_p, C.c_void_p
@@ -118,6 +119,9 @@ EXPORTS = {
     "vdn_refine_finish": (C.c_int, [fp, fp, C.c_float, C.c_float, C.c_float, C.c_int, fp, C.c_size_t, vp]),
     "vdn_refine_normalize": (C.c_int, [fp, C.c_float, fp, C.c_size_t, vp]),
     "vdn_refine_mix": (C.c_int, [fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, fp, C.c_size_t, vp]),
+    "vdn_refine_window_tail_trip": (C.c_int, [C.c_int]),
+    "vdn_refine_window_tail": (C.c_int, [fp, C.c_int, C.c_int, fp, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                         C.c_float, C.c_float, C.c_float, C.c_float, fp, vp]),
     "vdn_dn_attn": (C.c_int, [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_float, vp]),
     "vdn_dn_prologue": (C.c_int, [C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, vp, vp, vp]),

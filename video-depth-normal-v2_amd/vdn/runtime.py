@@ -668,6 +668,24 @@ class Runtime:
         self._launch(abi.lib.vdn_refine_mix, pd, checked_ptr("refine_mix: x", x, dev, _f32, count=n), a0, a1, c0, a2, c1,
                      checked_ptr("refine_mix: out", out, dev, _f32, count=n), n)
 
+    def refine_window_tail(self, net, scaled, slots, kind: int, residual: bool, coef, out):
+        """out f32 [T, OH, OW] <- the finish of one window (vdn_refine_window_tail): net f32 [T, IH, IW] is the head's rectified
+        map (sampled at the output pixels where the sizes differ), scaled f32 [frames, OH, OW] the clip's scaled input, slots
+        int32 [T] the clip frame each slot shows (range-checked by the caller before the upload), coef five floats: (w, b, unit,
+        0, 0) for abi.TAIL_SHIFT, refiner.fold_final_res's for abi.TAIL_MIX. scaled may be None where it is not read."""
+        dev = self.device
+        po = checked_ptr("refine_window_tail: out", out, dev, _f32, 3)
+        T, OH, OW = out.shape
+        pn = checked_ptr("refine_window_tail: net", net, dev, _f32, (T, None, None))
+        reads = kind == abi.TAIL_MIX or bool(residual)
+        ps = checked_ptr("refine_window_tail: scaled", scaled, dev, _f32, (None, OH, OW), optional=not reads)
+        if kind not in (abi.TAIL_SHIFT, abi.TAIL_MIX) or len(coef) != 5:
+            raise abi.VdnError(f"refine_window_tail: kind {kind} with {len(coef)} coefficients")
+        frames = scaled.shape[0] if scaled is not None else 1 << 30   # nothing of `scaled` is indexed then
+        self._launch(abi.lib.vdn_refine_window_tail, pn, net.shape[1], net.shape[2], ps, frames,
+                     C.cast(checked_ptr("refine_window_tail: slots", slots, dev, torch.int32, (T,)), C.POINTER(C.c_int32)), T, OH, OW, int(kind), int(bool(residual)),
+                     *(float(c) for c in coef), po)
+
     def dn_attn(self, qkv, out, rows: int, Cn: int, heads: int, L: int, estride: int, n0: int, s0: int, n1: int, s1: int,
                 scale: float):
         """Grouped self-attention of the depth + normal head (include/vdn.h vdn_dn_attn): qkv [rows, 3C], out [rows, C]."""

@@ -71,6 +71,17 @@ def window_table(n_frames: int) -> List[List[int]]:
     return table
 
 
+def window_slots(n_frames: int) -> np.ndarray:
+    """window_table as the int32 [windows, INFER_LEN] array a kernel indexes the clip with (vdn_refine_window_tail), checked
+    here, on the host, before it is uploaded: every entry is a frame of the clip."""
+    if n_frames < 1:
+        raise ValueError(f"a clip has at least one frame, got {n_frames}")
+    slots = np.asarray(window_table(n_frames), dtype=np.int32)
+    if slots.ndim != 2 or slots.shape[1] != INFER_LEN or slots.min() < 0 or slots.max() >= n_frames:
+        raise ValueError(f"window table of a {n_frames}-frame clip: shape {slots.shape}, range [{slots.min()}, {slots.max()}]")
+    return np.ascontiguousarray(slots)
+
+
 def stitch(depth_list: List[np.ndarray], org_len: int) -> np.ndarray:
     """Affine-align each window to the running result and blend the 8 overlap frames
     (video_depth.py:118-156)."""

@@ -4,7 +4,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import modules, util
+from . import clip, modules, util
 from .depth_anything_v2 import _EngineOwner
 from .engine import DPTEngine, EncoderEngine, ReadoutEngine
 
@@ -236,60 +236,28 @@ class VideoDepthAnything(_EngineOwner):
 
     # bytes of encoder taps one frame keeps in the clip-level cache: 4 taps x P tokens x C channels x 16-bit planes
     def _tap_bytes_per_frame(self, H: int, W: int) -> int:
-        rt = self._engines()["rt"]
-        return 4 * (H // 14) * (W // 14) * self.pretrained.embed_dim * 2 * (2 if rt.split else 1)
+        return clip.tap_bytes_per_frame(self._engines()["rt"], self.pretrained.embed_dim, H, W)
 
     def window_depths(self, net_in: torch.Tensor, table, windows=None):
-        """Depth [32,H,W] of the windows `windows` (default: all) of a clip whose pre-processed frames are net_in [n,3,H,W].
-        The reference runs the encoder on all 32 slots of every window (video_depth.py:96-103), but 10 of the 32 are
-        copies of earlier input frames (Appendix B of SURVEY.md: slot 0 = frame 0, slot 1 = the previous window's
-        keyframe, slots 2..9 = the previous window's last 8), and the encoder is per-frame: here every DISTINCT frame
-        goes through the encoder once (its 4 final-normed taps stay in HBM, 22 MB per 518x518 ViT-L frame), and a
-        window's head reads its 32 slots from that cache — 256 instead of 384 encoder passes for a 256-frame clip,
-        same numbers. Every encoder batch holds INFER_LEN frames, the clip's ragged tail filled up with copies of its last
-        frame (never more encoder passes than the reference's 32 per window): vdn_gemm picks its kernel by the row count, so a
-        frame encoded in a batch of 2 is 1e-5 away from the same frame in `forward`'s batch of 32, and a clip's depth would
-        depend on how its length splits. Falls back to per-window encoding when the cache would not fit (VDN_TAP_CACHE_GB,
-        default 96)."""
-        import os
+        """Depth [32,H,W] of the windows `windows` (default: all) of a clip whose pre-processed frames are net_in [n,3,H,W]:
+        every DISTINCT frame goes through the encoder once, in batches of INFER_LEN, and a window's head reads its 32 slots
+        from the clip-level tap cache (vdn/clip.py, shared with the depth refiners' clip driver, says why and how). Falls back
+        to per-window encoding when the cache would not fit (VDN_TAP_CACHE_GB, default 96)."""
         e = self._engines()
         rt, enc, head = e["rt"], e["enc"], e["head"]
         n, _, H, W = net_in.shape
         windows = list(range(len(table))) if windows is None else list(windows)
-        need = sorted({f for w in windows for f in table[w]})
-        budget = float(os.environ.get("VDN_TAP_CACHE_GB", "96")) * 2 ** 30
-        T = util.INFER_LEN
-        batches = -(-len(need) // T)
-        if batches * T * self._tap_bytes_per_frame(H, W) > budget:
+        need, fits = clip.tap_cache_plan(rt, self.pretrained.embed_dim, H, W, table, windows)
+        if not fits:
             for w in windows:
                 yield self.forward(net_in[torch.tensor(table[w], device=rt.device)][None])[0]
             return
-        ph, pw = H // 14, W // 14
-        P, C = ph * pw, self.pretrained.embed_dim
-        slot = {f: i for i, f in enumerate(need)}        # cache row block of frame f
-        cache = [rt.hbuf(f"clip_tap{j}", (batches * T * P, C)) for j in range(4)]
-        for c0 in range(0, len(need), T):   # encoder batches of 32 distinct frames
-            fr = need[c0:c0 + T]
-            fr = fr + fr[-1:] * (T - len(fr))
+
+        def net_batch(fr):
             x = net_in[torch.tensor(fr, device=rt.device)] if fr != list(range(fr[0], fr[0] + len(fr))) else net_in[fr[0]:fr[0] + len(fr)]
-            enc.run(x.contiguous(), tap_out=[t.narrow0(c0 * P, T * P) for t in cache])
-        for w in windows:
-            rows = [slot[f] for f in table[w]]
-            if rows == list(range(rows[0], rows[0] + T)):          # one contiguous run: read the cache in place
-                taps = [t.narrow0(rows[0] * P, T * P) for t in cache]
-            else:                                                   # copy the (typically 3) runs of slots into a window buffer
-                taps = [rt.hbuf(f"win_tap{j}", (T * P, C)) for j in range(4)]
-                i = 0
-                while i < T:
-                    k = i
-                    while k + 1 < T and rows[k + 1] == rows[k] + 1:
-                        k += 1
-                    for src, dst in zip(cache, taps):
-                        dst.hi[i * P:(k + 1) * P].copy_(src.hi[rows[i] * P:(rows[k] + 1) * P])
-                        if dst.lo is not None:
-                            dst.lo[i * P:(k + 1) * P].copy_(src.lo[rows[i] * P:(rows[k] + 1) * P])
-                    i = k + 1
-            yield head.run(taps, T, ph, pw, T=T, relu=True).reshape(T, H, W)
+            return x.contiguous()
+
+        yield from clip.cached_window_depths(rt, enc, head, self.pretrained.embed_dim, net_batch, H, W, table, windows, need)
 
 
 class DeviceStitcher:

@@ -615,6 +615,72 @@ int vdn_depth_loss_trimmed_backward(const float* prediction, const float* target
                                     const double* frame_stats, const int64_t* frame_counts, const double* out,
                                     const float* coeff, void* workspace, float* grad_prediction, vdn_stream stream);
 
+/* The SSIM term of the depth criterion: DepthShallowSSIMLoss of loss/loss.py:296-323 with reduction "batch-based" and the
+ * weights [1, 0, 0, 0, 0] that VideoDepthLoss constructs it with (scripts/train*.py: --ssim_loss_scale), the forward.
+ * pytorch_msssim's MS_SSIM is restated from its published algorithm (the library's own file is not pinned: DESIGN.md 5.18):
+ * with those weights the four pooled levels enter its product as value ** 0 == 1 with a zero gradient and are not computed.
+ * prediction, target f32 [B, T, H, W] row-major, mask u8 [B, T, H, W] (non-zero = keep, required; it takes part in the
+ * maximum alone, as in the reference). scale_shift f32 [B][2] or NULL: with it the term is taken on the aligned prediction
+ * a = fadd_rn(fmul_rn(scale, p), shift), vdn_depth_loss's alignment (the composite criterion); a = p without.
+ *   max      per item over its T * H * W pixels: pm = max of the kept a, tm = max of the kept target; when the item drops a
+ *            pixel 0 takes part in both (the reference multiplies by the mask; a dropped pixel's own value is never read);
+ *            max_val = max(max(pm, tm), 1e-8f), all float32.
+ *   scale    x = fdiv_rn(a, max_val), y = fdiv_rn(target, max_val) at every pixel, dropped or not. From here on fp64 computed
+ *            from these float32 values, separate multiply and add roundings (contraction is off).
+ *   window   g_k, k = 0 .. 10: the float32 values of exp(-(k - 5)^2 / 4.5) / sum as torch computes them, widened to double,
+ *            kept as literals (vdn.loss.SSIM_WINDOW). "Valid" filtering, along H and then W, taps in ascending order:
+ *            mu1, mu2, e11, e22, e12 = the filtered x, y, x^2, y^2, x y on the (H - 10) x (W - 10) outputs.
+ *   map      A = 2 (e12 - mu1 mu2) + C2, D = (e11 - mu1^2) + (e22 - mu2^2) + C2, C2 = 0.03^2; cs = A / D.
+ *   frame    cs_f = sum of cs over the frame's outputs / ((H - 10)(W - 10)); loss = 1 - sum_f relu(cs_f) / (B T).
+ * out f64 [4] = {loss, mean_f relu(cs_f), frames with cs_f <= 0 or NaN (gated by relu), B * T}; frame_cs f64 [B * T] = cs_f;
+ * item_max f64 [B][4] = {max_val, who holds it, the weight of the prediction's path, index}: who = 0 a kept prediction
+ * (weight 1), 1 the target (0), 2 a dropped pixel's zero (0), 3 the clamp (0: max(pm, tm) < 1e-8f), 4 prediction and target
+ * equally (1/2, torch.max's rule); index = the lowest index in the item's T * H * W pixels of a kept prediction equal to the
+ * largest kept one, -1 when a dropped pixel's zero comes before it or nothing is kept. All three are required.
+ * One block takes a 16 x 32 tile of a frame's outputs (vdn_ssim_tile): x and y with the halo of 10 in LDS, the moments along
+ * H into LDS, along W into registers; no plane is written. Determinism: a tile's sum in the order of the block reduction (a
+ * lane's two outputs, the wave's xor-shuffle, the four waves); a frame's tiles by one block, a lane adding the tiles lane,
+ * lane + 256, .. and the lanes by the block reduction; the frames likewise by one block; no atomics. Two runs give the same
+ * bits.
+ * workspace: vdn_ssim_loss_workspace_bytes(B, T, H, W) bytes, 8-byte aligned.
+ * VDN_EINVAL: a null pointer (scale_shift excepted), a size <= 0, H < 11 or W < 11 (the library's own rule, min(H, W) > 160,
+ * belongs to the Python classes). VDN_EUNSUPPORTED: H * W > INT32_MAX, B * T > 65535, more than INT32_MAX tiles. VDN_EALIGN: a
+ * float pointer off 4 bytes; workspace, out, frame_cs or item_max off 8. All returned before anything is launched.          */
+int vdn_ssim_tile(int* tile_h, int* tile_w);
+size_t vdn_ssim_loss_workspace_bytes(int B, int T, int H, int W);
+int vdn_ssim_loss(const float* prediction, const float* target, const uint8_t* mask, const float* scale_shift, int B, int T,
+                  int H, int W, void* workspace, double* out, double* frame_cs, double* item_max, vdn_stream stream);
+
+/* The gradient of coeff * (that loss) with respect to `prediction`. coeff f32 [1] is read on the device (no host
+ * synchronisation). prediction .. W are the arguments of the vdn_ssim_loss call that wrote out, frame_cs and item_max.
+ * Gradients with respect to target, and second derivatives, are not computed; the float32 roundings of a, x and y have the
+ * derivative of the exact operation. With T(.) the transpose of the valid filter (zero outside the outputs), P = 1 / D,
+ * Q = A / D^2, N = mu1 Q - mu2 P, and per frame w = -coeff / (B T (H - 10)(W - 10)) when cs_f > 0, else nothing at all:
+ *   g_x      = (2 w ((y T(P) - x T(Q)) + T(N))), the sum over the outputs of d cs / d x: the adjoint stencil; +0.0 in a frame
+ *              that relu gates.
+ *   max      dL / d max_val = -sum_j (g_x x + g_y y)_j / max_val over the item, g_y the mirror image of g_x. The adjoint turns
+ *            the sum into outputs alone: sum_j (g_x x + g_y y)_j = 2 C2 w sum_o (A - D) / D^2 per frame (cs is invariant
+ *            under a common scale but for C2), and that closed form is what is evaluated: it has no cancelling parts. It is
+ *            given, times item_max's weight, to the pixel item_max's index names; to nobody when the weight is 0.
+ *   g_a      = g_x / max_val + that term at the holder.
+ *   fit      with scale_shift: g_p = sc g_a + keep * (G0 (dN0 - sc dD) + G1 (dN1 - sh dD)) / D as in
+ *            vdn_depth_loss_backward (the same code), with G0 = sum g_a p and G1 = sum g_a over ALL the item's pixels (the
+ *            term ignores the mask, the fit does not) and the fit's masked sums summed again in vdn_depth_loss_backward's
+ *            order; 0 for an item with det == 0. Without scale_shift g_p = g_a.
+ *   write    accumulate == 0: grad_prediction = (float)g_p. accumulate != 0: (float)((double)grad_prediction + g_p), one
+ *            rounding: how the composite adds the term to vdn_depth_loss_backward's result.
+ * Passes: the fit's sums (with scale_shift), the forward's tile kernel leaving P, Q, N as fp64 planes over the outputs, the
+ * fold of a frame's tiles and a one-block solve, the adjoint in 16 x 32 tiles of pixels (g_a into an fp64 plane, the tile's
+ * sums for G0 and G1), the same fold and a one-block solve (an item's frames in index order), the write. No atomics, fixed order: two runs give the same bits, and as in vdn_depth_loss_backward the
+ * order depends on the shape alone, not on where a tensor starts.
+ * workspace: vdn_ssim_loss_backward_workspace_bytes(B, T, H, W) bytes, 8-byte aligned: B T (3 (H - 10)(W - 10) + H W) doubles
+ * and a part that depends on B, T and the number of tiles.
+ * Errors as vdn_ssim_loss, returned before anything is launched; every pointer but scale_shift is required.               */
+size_t vdn_ssim_loss_backward_workspace_bytes(int B, int T, int H, int W);
+int vdn_ssim_loss_backward(const float* prediction, const float* target, const uint8_t* mask, const float* scale_shift, int B,
+                           int T, int H, int W, const double* out, const double* frame_cs, const double* item_max,
+                           const float* coeff, int accumulate, void* workspace, float* grad_prediction, vdn_stream stream);
+
 /* The batch preparation that scripts/train.py, train_v2.py .. train_v4.py and scripts/evaluate.py, evaluate_v2.py ..
  * evaluate_v4.py repeat between the loader and the model: preprocess_rgb_sequences, preprocess_rgb_viz_sequences,
  * preprocess_depth_sequences (with its batch_wise_min_max_norm) and gt = 1. / torch.clamp(gt, min=1e-8). Stateless, caller's

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Dump the raw bytes of everything the criteria that share csrc/frame_sums.hpp produce (loss, loss_grad, normals,
-normals_grad, eval, metric), for a byte-for-byte comparison of two builds of the library (profiles/criteria_refactor.md is
+"""Dump the raw bytes of everything the criteria that share csrc/frame_sums.hpp produce (loss, loss_grad, ssim,
+normals, normals_grad, eval, metric), for a byte-for-byte comparison of two builds of the library (profiles/criteria_refactor.md is
 such a comparison):
 
     python tools/criteria_dump.py DIR                          # this tree's library
@@ -186,6 +186,30 @@ def main():
     silog("256", 256)
     silog(str(wide_n), wide_n)
     silog(f"{single_n}_offset", single_n, off=True)
+
+    # ---- the SSIM term: alone and on the aligned prediction, forward, backward and the accumulating backward. Last, so that
+    # the seeds of the cases above stay what they were.
+    def ssim(case, B, T, H, W, off=False):
+        target = rand(B, T, H, W) * 2.0 + 0.5
+        pred = put(target * 0.7 + 0.3 + randn(B, T, H, W) * 0.2, off)
+        mask = (rand(B, T, H, W) > 0.2).to(torch.uint8).to(dev)
+        target = put(target, off)
+        coeff = torch.tensor([0.3], device=dev)
+        fit = empty(B, 2)
+        fresh().depth_loss(pred, target, mask, None, scale_shift=fit)
+        for ss, sname in ((None, "alone"), (fit, "aligned")):
+            out, cs, im = empty(4, dtype=f64), empty(B * T, dtype=f64), empty(B, 4, dtype=f64)
+            fresh().ssim_loss(pred, target, mask, ss, out, cs, im)
+            grad = empty(B, T, H, W, off=off)
+            fresh().ssim_loss_backward(pred, target, mask, ss, out, cs, im, coeff, grad)
+            added = put(randn(B, T, H, W) * 1e-3, off)
+            fresh().ssim_loss_backward(pred, target, mask, ss, out, cs, im, coeff, added, accumulate=True)
+            dump(f"ssim_{case}_{sname}", out=out, frame_cs=cs, item_max=im, grad=grad, grad_accumulated=added)
+
+    ssim("2x3x12x37", 2, 3, 12, 37)
+    ssim("1x2x26x42", 1, 2, 26, 42)            # one tile of outputs and a second row and column of tiles of pixels
+    ssim("1x2x27x43_offset", 1, 2, 27, 43, off=True)
+    ssim("1x300x11x13", 1, 300, 11, 13)        # more frames than the lanes of the one-block folds
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@
 //   solve 1    one block: g_s, g_m, the median's holder and the float32 temporal threshold per frame; the fit's sums per item
 //   fit sums   g_a per kept pixel; per frame in DL_BPF blocks sum g_a p and sum g_a
 //   solve 2    one block: an item's frames in index order
-//   write      g_p = sc g_a + keep * (fit correction), rounded to float32 once; +0.0 at a dropped pixel
+//   write      g_p = sc g_a + keep * (fit correction) (FitGrad, loss_px.hpp), rounded to float32 once; +0.0 at a dropped pixel
 // g_x is a gather: a pixel reads its left, right, upper and lower neighbour at stride 2^k on every grid it belongs to, inside
 // its own frame, and no lane writes another lane's pixel. There are no atomics; sums have the fixed order of frame_sums.hpp.
 // Pass 1 leaves g_x in an fp64 plane of the workspace, pass 3 turns it into g_a in place and pass 5 reads it, so the stencil is
@@ -314,9 +314,8 @@ __global__ __launch_bounds__(256) void grad_write_kernel(GRAD_ARGS, float* __res
   const int f = blockIdx.x / DL_BPF, b = blockIdx.x % DL_BPF;
   const GRAD_CTX;
   const double* it = ws.item + (size_t)(f / T) * I_SLOTS;
-  const double a01 = it[I_A01], a11 = it[I_A11], b0 = it[I_B0], b1 = it[I_B1], D = it[I_D], G0 = it[I_G0], G1 = it[I_G1];
+  const FitGrad fit{it[I_A01], it[I_A11], it[I_B0], it[I_B1], it[I_D], it[I_G0], it[I_G1], (double)c.sc, (double)c.sh};
   const bool ok = it[I_OK] != 0.0;
-  const double scd = (double)c.sc, shd = (double)c.sh;
   float* gf = grad + (size_t)f * c.hw;
   // the start IS sweep_first<PPL>(b) of frame_sums.hpp, spelled out, and must stay equal to it (profiles/criteria_refactor.md
   // says why it is not a call)
@@ -328,11 +327,7 @@ __global__ __launch_bounds__(256) void grad_write_kernel(GRAD_ARGS, float* __res
     for (int j = 0; j < PPL; ++j) {
       r[j] = 0.f;
       if (q.k[j] && ok) {
-        const double g = ws.plane[(size_t)f * c.hw + p0 + j];
-        const double pd = (double)q.p[j], td = (double)q.t[j];
-        const double dN0 = a11 * td - b1, dN1 = -b0 - a01 * td + 2.0 * pd * b1, dD = 2.0 * (pd * a11 - a01);
-        const double fit = (G0 * (dN0 - scd * dD) + G1 * (dN1 - shd * dD)) / D;
-        r[j] = (float)(scd * g + fit);
+        r[j] = (float)fit(ws.plane[(size_t)f * c.hw + p0 + j], (double)q.p[j], (double)q.t[j]);
       }
     }
     store_px<PPL, VEC>(gf + p0, r);

@@ -1,5 +1,5 @@
 // What the passes of the depth criterion share (loss.hip forward, loss_grad.hip backward): the blocks per frame, the aligned
-// prediction, the trimmed criterion's residuals and a lane's pixels (swept, loaded and summed as frame_sums.hpp states). Include it AFTER the unit's `#pragma clang fp contract(off)`: aligned()
+// prediction, the trimmed criterion's residuals, the gradient through the fit (which ssim.hip shares) and a lane's pixels (swept, loaded and summed as frame_sums.hpp states). Include it AFTER the unit's `#pragma clang fp contract(off)`: aligned()
 // is a multiply that feeds an add, and both units must round it twice.
 #pragma once
 #include "common.hpp"
@@ -45,6 +45,18 @@ __device__ __forceinline__ double trim_weight(const double* __restrict__ tr, uin
   const uint32_t thr = __builtin_bit_cast(uint32_t, (float)tr[3]);
   return key < thr ? 1.0 : (key == thr ? tr[4] : 0.0);
 }
+
+// The gradient through the fit at a kept pixel of an item (loss_grad.hip's write pass, ssim.hip's): from g_a of the aligned
+// prediction, g_p = sc g_a + (G0 (dN0 - sc dD) + G1 (dN1 - sh dD)) / D with G0 = sum g_a p, G1 = sum g_a over the pixels the
+// criterion sums, a01 .. b1 the masked sums of the fit, D = det + 1e-6 (include/vdn.h, vdn_depth_loss_backward).
+struct FitGrad {
+  double a01, a11, b0, b1, D, G0, G1, sc, sh;
+  __device__ __forceinline__ double operator()(double g, double pd, double td) const {
+    const double dN0 = a11 * td - b1, dN1 = -b0 - a01 * td + 2.0 * pd * b1, dD = 2.0 * (pd * a11 - a01);
+    const double fit = (G0 * (dN0 - sc * dD) + G1 * (dN1 - sh * dD)) / D;
+    return sc * g + fit;
+  }
+};
 
 // PPL consecutive pixels of a frame, loaded as frame_sums.hpp loads them (VEC: one 16-byte load per float plane and one 4-byte
 // load of the mask, which the bases must allow; the lane owns the same pixels either way), and which of them the mask keeps.

@@ -156,6 +156,11 @@ EXPORTS = {
     "vdn_depth_loss_trimmed_backward_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vdn_depth_loss_trimmed_backward": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, fp,
                                                   vp, vp, vp, fp, vp, fp, vp]),
+    "vdn_ssim_tile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vdn_ssim_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vdn_ssim_loss": (C.c_int, [fp, fp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "vdn_ssim_loss_backward_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vdn_ssim_loss_backward": (C.c_int, [fp, fp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, fp, C.c_int, vp, fp, vp]),
     "vdn_prep_trip": (C.c_int, [C.c_int]),
     "vdn_prep_depth_workspace_bytes": (C.c_size_t, [C.c_int]),
     "vdn_prep_rgb": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

@@ -30,9 +30,21 @@ TrimmedVideoDepthLoss (and the keyword `trim` of depth_loss and depth_loss_grad)
 device per term, the rank computed on the device, forward and backward (include/vdn.h, vdn_depth_loss_trimmed).
 VideoDepthLoss itself keeps refusing trim != 0.
 
-Not computed, each raising NotImplementedError: trim != 0 in VideoDepthLoss (use TrimmedVideoDepthLoss),
-reduction != "batch-based" (the reference's image-based branch indexes a 1-D vector with the mask's coordinates) and
-ssim_loss_scale > 0 (the reference's term needs pytorch_msssim). scales above 4 (the reference's default) likewise."""
+The SSIM term. The reference's VideoDepthLoss takes `ssim_loss_scale` as its fifth argument (the scripts' --ssim_loss_scale):
+with it above 0 the dictionary gains 'ssim_loss' = DepthShallowSSIMLoss of the aligned prediction and total_loss gains
+ssim_loss_scale times it. Here DepthShallowSSIMLoss is the term alone and SSIMVideoDepthLoss the criterion with all of its
+terms (and `trim`), both differentiable in the prediction: csrc/ssim.hip, include/vdn.h (vdn_ssim_loss and its backward).
+pytorch_msssim's MS_SSIM is restated from its published algorithm, not linked: with the weights [1, 0, 0, 0, 0] the reference
+uses, it is 1 - mean over frames of relu(mean of the contrast-structure map of an 11-tap Gaussian window, SSIM_WINDOW), and
+the four pooled levels are factors of exactly 1. Parity with the library's own file cannot be pinned without it (DESIGN.md
+5.18). The library asserts min(H, W) > 160 for its four downsamplings; the classes raise ValueError there, the functions
+ssim_loss and ssim_loss_grad take any frame of 11 x 11 or more. VideoDepthLoss and TrimmedVideoDepthLoss keep refusing
+ssim_loss_scale > 0: the criterion with the term is SSIMVideoDepthLoss.
+
+Not computed, each raising NotImplementedError: trim != 0 in VideoDepthLoss (use TrimmedVideoDepthLoss), ssim_loss_scale > 0
+in VideoDepthLoss (use SSIMVideoDepthLoss), reduction != "batch-based" (the reference's image-based branch indexes a 1-D
+vector with the mask's coordinates, and cannot run), weights of the SSIM term other than [1, 0, 0, 0, 0] (they need the four
+pooled levels). scales above 4 (the reference's default) likewise."""
 from __future__ import annotations
 
 from typing import Dict, Tuple
@@ -45,6 +57,13 @@ OUT_SLOTS = 20   # include/vdn.h: the layout of vdn_depth_loss's out
 TRIM_SLOTS = 40  # ... and of vdn_depth_loss_trimmed's: 20 + 5 * term: k | n_less | n_tied | threshold | weight
 MAX_SCALES = 4
 _SLOT = {"spatial_loss": 0, "stable_loss": 1, "absRel_loss": 2, "d1": 3, "total_loss": 4}
+# The eleven taps of the SSIM term's window: the float32 values of exp(-(k - 5)^2 / (2 * 1.5^2)) / sum as torch computes them
+# (pytorch_msssim's _fspecial_gauss_1d(11, 1.5)), widened to double. csrc/ssim.hip holds the same literals.
+SSIM_WINDOW = tuple(float.fromhex(h) for h in (
+    "0x1.0d9570p-10", "0x1.f1fe02p-8", "0x1.26eb18p-5", "0x1.bff0fep-4", "0x1.b43c3ep-3", "0x1.106560p-2", "0x1.b43c3ep-3",
+    "0x1.bff0fep-4", "0x1.26eb18p-5", "0x1.f1fe02p-8", "0x1.0d9570p-10"))
+SSIM_MIN_SIDE = 160   # the library asserts min(H, W) > (11 - 1) * 2 ** 4 for its four downsamplings
+SSIM_HOLDERS = ("prediction", "target", "dropped", "clamp", "tie")   # who holds an item's maximum (include/vdn.h, item_max)
 
 
 def _check(prediction, target, mask, dims: int) -> tuple:
@@ -169,7 +188,7 @@ class VideoDepthLoss(torch.nn.Module):
         stable_scale > 0, where the reference divides by zero. With gradients enabled and a prediction that requires one, the
         values carry a grad_fn whose backward gives prediction.grad in the prediction's dtype and shape."""
         if self.ssim_loss_scale > 0:      # the attribute is public, as in the reference
-            raise NotImplementedError("ssim_loss_scale > 0 is not computed")
+            raise NotImplementedError("ssim_loss_scale > 0 is not computed here: SSIMVideoDepthLoss is the criterion with the term")
         if wants_grad(prediction, target):
             v = _DepthLossFn.apply(prediction, target, mask, self._alpha, self.scales, float(self.stable_scale), self.device,
                                    self._keep)
@@ -194,6 +213,209 @@ class TrimmedVideoDepthLoss(VideoDepthLoss):
         super().__init__(alpha, scales, 0.0, stable_scale, device=device)
         self.trim = trim
         self._keep = keep
+
+
+# ------------------------------------------------------------------------------------------------ the SSIM term
+def ssim_tile() -> Tuple[int, int]:
+    """(rows, columns) of the outputs one block of the SSIM kernels takes (vdn_ssim_tile): a frame of tile + 10 is one tile."""
+    import ctypes
+    from . import _abi as abi
+    th, tw = ctypes.c_int(), ctypes.c_int()
+    abi.check(abi.lib.vdn_ssim_tile(ctypes.byref(th), ctypes.byref(tw)), "vdn_ssim_tile")
+    return th.value, tw.value
+
+
+def _check_ssim(prediction, target, mask, library_rule: bool) -> tuple:
+    B, T, H, W = _check(prediction, target, mask, 4)
+    if library_rule and min(H, W) <= SSIM_MIN_SIDE:
+        raise ValueError(f"the SSIM term needs min(H, W) > {SSIM_MIN_SIDE} (pytorch_msssim asserts it for its four "
+                         f"downsamplings), got {H} x {W}")
+    if min(H, W) < len(SSIM_WINDOW):
+        raise ValueError(f"the SSIM term needs frames of {len(SSIM_WINDOW)} x {len(SSIM_WINDOW)} or more, got {H} x {W}")
+    return B, T, H, W
+
+
+def _ssim_launch(rt, p, t, m, ss):
+    """One launch of vdn_ssim_loss on staged tensors -> its state, float64 on the device in a tensor of its own: out [4] |
+    frame_cs [B T] | item_max [B, 4]."""
+    B, T = p.shape[:2]
+    with torch.cuda.device(rt.device):
+        st = torch.empty((4 + B * T + 4 * B,), dtype=torch.float64, device=rt.device)
+        rt.ssim_loss(p, t, m, ss, st[:4], st[4:4 + B * T], st[4 + B * T:])
+    return st
+
+
+def _ssim_backward(rt, p, t, m, ss, st, coeff, grad, accumulate: bool):
+    F = p.shape[0] * p.shape[1]
+    with torch.cuda.device(rt.device):
+        rt.ssim_loss_backward(p, t, m, ss, st[:4], st[4:4 + F], st[4 + F:], coeff, grad, accumulate)
+    return grad
+
+
+def _ssim_stage(prediction, target, mask, device, aligned: bool):
+    """-> runtime, the staged f32 prediction, target and u8 mask, and the fit f32 [B, 2] when `aligned` (else None)."""
+    rt = runtime_for(device, prediction, target, mask)
+    p = stage(prediction, rt.device, torch.float32)
+    t = stage(target, rt.device, torch.float32)
+    m = stage(mask, rt.device, torch.uint8)
+    ss = None
+    if aligned:
+        with torch.cuda.device(rt.device):
+            ss = torch.empty((p.shape[0], 2), dtype=torch.float32, device=rt.device)
+            rt.depth_loss(p, t, m, None, scale_shift=ss)
+    return rt, p, t, m, ss
+
+
+class _SsimLossFn(torch.autograd.Function):
+    """The SSIM term alone as a 0-dim float32 tensor, differentiable in `prediction`."""
+
+    @staticmethod
+    def forward(ctx, prediction, target, mask, device):
+        rt, p, t, m, _ = _ssim_stage(prediction, target, mask, device, False)
+        st = _ssim_launch(rt, p, t, m, None)
+        ctx.save_for_backward(p, t, m, st)
+        ctx.args = (rt, prediction.dtype, prediction.device)
+        with torch.cuda.device(rt.device):
+            return st[0].to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        p, t, m, st = ctx.saved_tensors
+        rt, dtype, device = ctx.args
+        with torch.cuda.device(rt.device):
+            coeff = g.to(device=rt.device, dtype=torch.float32).reshape(1)
+            grad = torch.empty_like(p)
+        _ssim_backward(rt, p, t, m, None, st, coeff, grad, False)
+        return grad.to(device=device, dtype=dtype), None, None, None
+
+
+class DepthShallowSSIMLoss(torch.nn.Module):
+    """loss/loss.py:296-323 with the reference's constructor signature: 1 - MS_SSIM(data_range=1, channel=1, weights)(x, y) of
+    the prediction and target divided by the item's masked maximum, for the weights [1, 0, 0, 0, 0] the reference's criterion
+    uses. reduction other than "batch-based" and any other weights raise NotImplementedError."""
+
+    def __init__(self, reduction="batch-based", weights=[1.0, 0.0, 0.0, 0.0, 0.0], *, device="cuda"):
+        super().__init__()
+        if reduction != "batch-based":
+            raise NotImplementedError(f"reduction={reduction!r}: only 'batch-based' is computed")
+        w = [float(x) for x in weights]
+        if w != [1.0, 0.0, 0.0, 0.0, 0.0]:
+            raise NotImplementedError(f"weights={list(weights)!r}: only [1, 0, 0, 0, 0] is computed; other weights need the four "
+                                      "pooled levels of MS_SSIM")
+        self.device = device
+
+    def forward(self, prediction, target, mask) -> torch.Tensor:
+        """prediction, target, mask [B, S, H, W] -> a 0-dim float32 tensor on the device, no host synchronisation. ValueError for
+        min(H, W) <= 160, where the library asserts. With gradients enabled and a prediction that requires one, the value
+        carries a grad_fn (once differentiable); a target that requires one raises NotImplementedError."""
+        _check_ssim(prediction, target, mask, True)
+        if wants_grad(prediction, target):
+            return _SsimLossFn.apply(prediction, target, mask, self.device)
+        rt, p, t, m, _ = _ssim_stage(prediction, target, mask, self.device, False)
+        st = _ssim_launch(rt, p, t, m, None)
+        with torch.cuda.device(rt.device):
+            return st[0].to(torch.float32)
+
+
+class _SsimDepthLossFn(torch.autograd.Function):
+    """The criterion with the SSIM term as one float32 [6] tensor: the slots of _SLOT (total_loss without the term) and the term
+    in slot 5, differentiable in `prediction`."""
+
+    @staticmethod
+    def forward(ctx, prediction, target, mask, alpha, scales, stable_scale, device, keep):
+        rt, res, ss, p, t, m = _launch(prediction, target, mask, alpha, scales, stable_scale, device, True, state=True, keep=keep)
+        st = _ssim_launch(rt, p, t, m, ss)
+        with torch.cuda.device(rt.device):
+            res = res.clone()
+            v = torch.cat((res[:5], st[:1])).to(torch.float32)
+        ctx.save_for_backward(p, t, m, ss, res, st)
+        ctx.args = (rt, alpha, scales, stable_scale, prediction.dtype, prediction.device, keep)
+        return v
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        p, t, m, ss, res, st = ctx.saved_tensors
+        rt, alpha, scales, stable_scale, dtype, device, keep = ctx.args
+        with torch.cuda.device(rt.device):
+            g = g.to(device=rt.device, dtype=torch.float32)
+            coeff = torch.stack((g[4] + g[0], g[4] * stable_scale + g[1], g[2]))
+            c_ssim = g[5:6].contiguous()
+        grad = _backward(rt, p, t, m, alpha, scales, stable_scale, ss, res, coeff, keep)
+        _ssim_backward(rt, p, t, m, ss, st, c_ssim, grad, True)   # added to the other terms' gradient in fp64, rounded once
+        return grad.to(device=device, dtype=dtype), None, None, None, None, None, None, None
+
+
+class SSIMVideoDepthLoss(VideoDepthLoss):
+    """The reference's VideoDepthLoss(alpha, scales, trim, stable_scale, ssim_loss_scale) with all of its terms, in its
+    positional order: the fit, the criterion's launch (trimmed when trim > 0), then with ssim_loss_scale > 0 the SSIM term on
+    the aligned prediction (loss/loss.py:358-360). The dictionary then holds 'ssim_loss' after 'stable_loss', and total_loss
+    is the float32 sum the reference forms: spatial_loss + stable_loss * stable_scale + ssim_loss * ssim_loss_scale.
+    Differentiable in the prediction: the criterion's backward launch, then the term's, which adds its gradient to the first's.
+    ValueError for min(H, W) <= 160 when the term is on. With ssim_loss_scale == 0 this is TrimmedVideoDepthLoss bit for bit,
+    and launches nothing else."""
+
+    def __init__(self, alpha=0.5, scales=4, trim=0.0, stable_scale=10, ssim_loss_scale=0.0, *, device="cuda"):
+        keep = _check_trim(trim)
+        if isinstance(ssim_loss_scale, bool) or not isinstance(ssim_loss_scale, (int, float)) or ssim_loss_scale != ssim_loss_scale:
+            raise ValueError(f"ssim_loss_scale={ssim_loss_scale!r}: a number (the term is computed when it is above 0)")
+        super().__init__(alpha, scales, 0.0, stable_scale, device=device)
+        self.trim = trim
+        self._keep = keep
+        self.ssim_loss_scale = ssim_loss_scale
+
+    @property
+    def keys(self) -> Tuple[str, ...]:
+        """The keys of forward's dictionary, in the reference's order."""
+        return (("spatial_loss",) + (("stable_loss",) if self.stable_scale > 0 else ())
+                + (("ssim_loss",) if self.ssim_loss_scale > 0 else ()) + ("absRel_loss", "d1", "total_loss"))
+
+    def forward(self, prediction, target, mask) -> Dict[str, torch.Tensor]:
+        if not self.ssim_loss_scale > 0:      # zero or negative: the reference adds no term either
+            return super().forward(prediction, target, mask)
+        _check_ssim(prediction, target, mask, True)
+        args = (self._alpha, self.scales, float(self.stable_scale), self.device, self._keep)
+        if wants_grad(prediction, target):
+            v = _SsimDepthLossFn.apply(prediction, target, mask, *args)
+        else:
+            rt, res, ss, p, t, m = _launch(prediction, target, mask, *args[:4], False, state=True, keep=self._keep)
+            st = _ssim_launch(rt, p, t, m, ss)
+            with torch.cuda.device(rt.device):
+                v = torch.cat((res[:5], st[:1])).to(torch.float32)
+        total = v[0]
+        if self.stable_scale > 0:
+            total = total + v[1] * self.stable_scale
+        total = total + v[5] * self.ssim_loss_scale
+        return {k: (total if k == "total_loss" else v[5] if k == "ssim_loss" else v[_SLOT[k]]) for k in self.keys}
+
+
+def ssim_loss(prediction, target, mask, *, aligned=False, device="cuda") -> dict:
+    """The fp64 values of one launch of the SSIM term, read with one synchronising copy. prediction, target, mask [B, T, H, W]
+    with H, W >= 11 (the library's rule min(H, W) > 160 is the classes'). aligned: on scale * prediction + shift of the masked
+    fit, as SSIMVideoDepthLoss takes it. Returns Python floats 'ssim_loss' and 'mean_cs', the integer 'gated' (frames whose cs
+    relu sets to 0) and CPU tensors 'cs' float64 [B, T], 'max_val' float64 [B] (a float32 value), 'holder' int64 [B] (an index
+    into SSIM_HOLDERS), 'weight' float64 [B] and 'index' int64 [B] (include/vdn.h, item_max)."""
+    B, T, _, _ = _check_ssim(prediction, target, mask, False)
+    rt, p, t, m, ss = _ssim_stage(prediction, target, mask, device, aligned)
+    host = _ssim_launch(rt, p, t, m, ss).cpu()
+    im = host[4 + B * T:].view(B, 4)
+    return dict(ssim_loss=float(host[0]), mean_cs=float(host[1]), gated=int(host[2]), cs=host[4:4 + B * T].view(B, T).clone(),
+                max_val=im[:, 0].clone(), holder=im[:, 1].to(torch.int64), weight=im[:, 2].clone(), index=im[:, 3].to(torch.int64))
+
+
+def ssim_loss_grad(prediction, target, mask, *, aligned=False, coeff=1.0, prior=None, device="cuda") -> torch.Tensor:
+    """The gradient of coeff * ssim_loss with respect to prediction without autograd: float32 [B, T, H, W] on the device (the
+    forward's launch and one of vdn_ssim_loss_backward); what DepthShallowSSIMLoss's backward computes, and with `aligned` the
+    term's part of SSIMVideoDepthLoss's. prior: a float32 gradient the result is added to in fp64 and rounded once (the
+    accumulating write; `prior` itself is left as it is)."""
+    _check_ssim(prediction, target, mask, False)
+    rt, p, t, m, ss = _ssim_stage(prediction, target, mask, device, aligned)
+    st = _ssim_launch(rt, p, t, m, ss)
+    with torch.cuda.device(rt.device):
+        c = torch.tensor([float(coeff)], dtype=torch.float32, device=rt.device)
+        grad = torch.empty_like(p) if prior is None else stage(prior, rt.device, torch.float32).clone().view(p.shape)
+    return _ssim_backward(rt, p, t, m, ss, st, c, grad, prior is not None)
 
 
 def compute_scale_and_shift(prediction, target, mask, *, device="cuda"):

@@ -538,6 +538,38 @@ class Runtime:
         ws = self._ws("depth_loss_backward_ws", size(B, T, H, W))
         self._launch(entry, p, t, m, B, T, H, W, float(alpha), int(scales), float(stable_scale), ss, fs, fc, o, c, ws.data_ptr(), g)
 
+    def _ssim_args(self, what: str, prediction, target, mask, scale_shift, out, frame_cs, item_max):
+        """-> B, T, H, W and the pointers of f32 prediction and target and the u8 mask [B, T, H, W], scale_shift f32 [B, 2] or
+        None, out f64 [4], frame_cs f64 [B T] and item_max f64 [B, 4] (include/vdn.h, vdn_ssim_loss)."""
+        dev = self.device
+        p = checked_ptr(what + ": prediction", prediction, dev, _f32, 4)
+        B, T, H, W = shape = prediction.shape
+        return (B, T, H, W, p, checked_ptr(what + ": target", target, dev, _f32, shape), checked_ptr(what + ": mask", mask, dev, _u8, shape),
+                checked_ptr(what + ": scale_shift", scale_shift, dev, _f32, count=2 * B, optional=True),
+                checked_ptr(what + ": out", out, dev, _f64, count=4), checked_ptr(what + ": frame_cs", frame_cs, dev, _f64, count=B * T),
+                checked_ptr(what + ": item_max", item_max, dev, _f64, count=4 * B))
+
+    def ssim_loss(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, scale_shift: Optional[torch.Tensor],
+                  out: torch.Tensor, frame_cs: torch.Tensor, item_max: torch.Tensor):
+        """out f64 [4], frame_cs f64 [B T], item_max f64 [B, 4] <- the SSIM term of f32 prediction, target [B, T, H, W] under the
+        u8 mask (vdn_ssim_loss); scale_shift f32 [B, 2]: on the aligned prediction."""
+        B, T, H, W, p, t, m, ss, o, fc, im = self._ssim_args("ssim_loss", prediction, target, mask, scale_shift, out, frame_cs, item_max)
+        ws = self._ws("ssim_loss_ws", abi.lib.vdn_ssim_loss_workspace_bytes(B, T, H, W))
+        self._launch(abi.lib.vdn_ssim_loss, p, t, m, ss, B, T, H, W, ws.data_ptr(), o, fc, im)
+
+    def ssim_loss_backward(self, prediction: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, scale_shift: Optional[torch.Tensor],
+                           out: torch.Tensor, frame_cs: torch.Tensor, item_max: torch.Tensor, coeff: torch.Tensor, grad: torch.Tensor,
+                           accumulate: bool = False):
+        """grad f32 [B, T, H, W] <- (accumulate: +=, rounded once) the gradient of coeff * ssim_loss with respect to the f32
+        prediction (vdn_ssim_loss_backward); coeff f32 [1] on the device; out, frame_cs and item_max are what ssim_loss wrote for
+        the same inputs and scale_shift."""
+        B, T, H, W, p, t, m, ss, o, fc, im = self._ssim_args("ssim_loss_backward", prediction, target, mask, scale_shift, out, frame_cs,
+                                                             item_max)
+        c = checked_ptr("ssim_loss_backward: coeff", coeff, self.device, _f32, count=1)
+        g = checked_ptr("ssim_loss_backward: grad", grad, self.device, _f32, prediction.shape)
+        ws = self._ws("ssim_loss_backward_ws", abi.lib.vdn_ssim_loss_backward_workspace_bytes(B, T, H, W))
+        self._launch(abi.lib.vdn_ssim_loss_backward, p, t, m, ss, B, T, H, W, o, fc, im, c, int(bool(accumulate)), ws.data_ptr(), g)
+
     def prep_rgb(self, x: torch.Tensor, out: torch.Tensor, normalize: bool):
         """out f32 [F, 3, H, W] <- clamp(x, 0, 1), then the ImageNet mean / std when `normalize` (vdn_prep_rgb); out may be x."""
         px = checked_ptr("prep_rgb: x", x, self.device, _f32, (None, 3, None, None))

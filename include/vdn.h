@@ -32,7 +32,8 @@ enum vdn_status { VDN_OK = 0, VDN_EINVAL = -1, VDN_EUNSUPPORTED = -2, VDN_EALIGN
 enum vdn_dtype { VDN_F16 = 0, VDN_BF16 = 1, VDN_F32 = 2, VDN_NONE = 3 };
 enum vdn_act { VDN_ACT_NONE = 0, VDN_ACT_GELU = 1, VDN_ACT_RELU = 2,
                VDN_ACT_SILU = 3 /* only as the gate of VDN_ST_GEGLU: out = h * silu(gate) (SwiGLU, dinov2_layers/swiglu_ffn.py:29-33) */ };
-enum vdn_amode { VDN_A_PLAIN = 0, VDN_A_CONV3X3 = 1 };
+enum vdn_amode { VDN_A_PLAIN = 0, VDN_A_CONV3X3 = 1,
+                 VDN_A_PAD3X3 = 2 /* 3x3 stride-1 convolution on padded-row operand planes (cross-term kernel only; see pad_hi) */ };
 enum vdn_store {
   VDN_ST_PLAIN = 0,   /* out[row(m) * ldc + n]                                                   */
   VDN_ST_HEADS = 1,   /* n -> (split, head, e<64); per-split buffer, token- or dim-major          */
@@ -201,6 +202,25 @@ typedef struct vdn_gemm_desc {
    * vdn/pack.py subpixel_conv builds both from the reference's parameters.                                                */
   int32_t subpix;
   const float* subpix_bias;
+  /* Padded-row operand planes: a 3x3, stride-1, pad-1 convolution F -> N as a cross-term GEMM whose nine taps are row shifts
+   * (a_mode = VDN_A_PAD3X3; the ResidualConvUnit convolutions of the two high-resolution fusion blocks, util/blocks.py:68-74).
+   * An operand map is NHWC with a one-pixel ZERO RING per frame: Mp = cB (cH + 2) (cW + 2) rows of cC channels, row
+   * (b, y, x) = (b (cH + 2) + y) (cW + 2) + x with the image at y in 1..cH, x in 1..cW. It is stored as the K-tile-major planes of
+   * a_kt above: fp16 hi [cC / 32][Mp][32] and the two planes of x6 rows [cC / 64][Mp][64] (A8; plane 1 follows plane 0), and
+   * every allocation carries cW + 3 GUARD ROWS (64 bytes each) in front of its first plane and behind its last: tap (dy, dx) of
+   * output row m is row m + dy (cW + 2) + dx of the same plane, for every row including the ring, a wave-uniform shift that
+   * stays inside the allocation. Ring pixels hold zero bits in all three planes (a zero code is zero under any scale byte), so
+   * the shifted rows ARE the convolution's zero padding; what a ring row itself accumulates is never stored.
+   *   M = Mp, K = 9 cC = ldb, cC % 64 == 0 and <= 4096, a_kt = w_kt = 1; W / W8 from vdn_pack_x8 (order 1) of the weight in
+   *   K = (tap, channel) order (VDN_PACK_CONV3X3_TAPS); fp16 only; cOH, cOW, cstride, lda, relu_a unused (0).
+   * Two epilogues, both with N == ldc, N % 64 == 0:
+   *   act = VDN_ACT_RELU, out_kt = 1, out + out8, no residual: relu(acc + bias) as the padded operand planes of the NEXT such
+   *     convolution (out = its fp16 hi plane, out8 = its x6 rows, guards as above; ring rows are written as zero bits).
+   *   act = VDN_ACT_NONE, out_kt = 0, out + out_lo, res1 (+ res2) with their lo planes: v = acc + bias + res1 [+ res2] on the
+   *     UNPADDED rows (b cH + y - 1) cW + x - 1 of row-major split planes [cB cH cW, ld*] (ring rows read and store nothing
+   *     there); when pad_hi and out8 are given, relu(v) is also written as padded operand planes (pad_hi = fp16 hi plane,
+   *     out8 = x6 rows; ring rows zero bits).                                                                              */
+  void* pad_hi;
 } vdn_gemm_desc;
 
 int vdn_gemm(const vdn_gemm_desc* d, vdn_stream stream);
@@ -992,6 +1012,12 @@ int vdn_pack_x8(const void* hi, const void* lo, int rows, int ld, void* hi_kt, v
  * feeds a GEMM without a LayerNorm in between: the memory feature of memory_encoder.py:173-181 before the key / value
  * projections of memory_attention.py): hi_kt = fp16 hi plane toward zero, K-tile-major; planes8 = u8 [2][ld/64][rows][64], order 0. */
 int vdn_pack_x8_f32(const float* x, int rows, int ld, void* hi_kt, void* planes8, vdn_stream stream);
+
+/* Padded-row operand planes (vdn_gemm_desc.pad_hi) of relu(x): x = split planes hi / lo, row-major [B H W, C] (C % 64 == 0) ->
+ * hi_pad fp16 [C / 32][Mp][32] and planes8 u8 [2][C / 64][Mp][64] (x6 rows, order 1: that of the epilogues), Mp = B (H + 2) (W + 2). Image rows get
+ * the values, ring rows zero bits; the guard rows around the planes are not touched. The first convolution of a fusion
+ * block's ResidualConvUnit reads these; the later ones get theirs from the GEMM epilogues.                            */
+int vdn_pack_x8_relu_pad(const void* hi, const void* lo, int B, int H, int W, int C, void* hi_pad, void* planes8, vdn_stream stream);
 
 /* Workspace sizing (the library allocates nothing): bytes of split-K scratch worth passing as vdn_gemm_desc.splitk_ws
  * for this descriptor (0 = the shape never splits), and the partial-sum buffer of vdn_groupnorm.

@@ -254,6 +254,13 @@ __device__ __forceinline__ void x6_store_half(uint8_t* dst, const f16x32& v, int
   *(u32x4*)dst = u32x4{c[0], c[1], c[2], c[3]};
   *(u32x4*)(dst + 16) = u32x4{c[4], c[5], (unsigned)scale_byte, 0u};
 }
+// the same with the scale byte stored only where `keep` (rows that must be zero BITS pass all-zero values and keep = false:
+// their codes are zero under the scale the conversion ran with)
+__device__ __forceinline__ void x6_store_half(uint8_t* dst, const f16x32& v, int scale_byte, bool keep) {
+  const u32x6 c = __builtin_amdgcn_cvt_scalef32_pk32_bf6_f16(v, __builtin_bit_cast(float, (unsigned)scale_byte << 23));
+  *(u32x4*)dst = u32x4{c[0], c[1], c[2], c[3]};
+  *(u32x4*)(dst + 16) = u32x4{c[4], c[5], keep ? (unsigned)scale_byte : 0u, 0u};
+}
 // Column of a 64-wide K slab that sits at stream position p (0..31) of half h, by the ORDER the producer of the activation
 // planes writes (the weight planes of the consuming GEMM are packed in the same order, vdn_pack_x8):
 //   0 natural        col = 32 h + p                                  vdn_layernorm, vdn_pack_x8 on activations

@@ -73,6 +73,24 @@ extern "C" int vdn_gemm(const vdn_gemm_desc* dp, vdn_stream stream) {
     if (d.cOH != (d.cH + 2 - 3) / d.cstride + 1 || d.cOW != (d.cW + 2 - 3) / d.cstride + 1) return VDN_EINVAL;
   } else if (d.a_mode == VDN_A_PLAIN) {
     if ((d.lda & 7) || d.lda < d.K) return VDN_EALIGN;
+  } else if (d.a_mode == VDN_A_PAD3X3) {
+    // padded-row 3x3 mode (include/vdn.h pad_hi): everything its kernel relies on, stated once; the generic checks below still run
+    if (d.dt != VDN_F16 || !d.A8 || !d.W8 || !d.a_kt || !d.w_kt || d.relu_a || d.subpix || d.x8_terms) return VDN_EINVAL;
+    if (d.cB <= 0 || d.cH <= 0 || d.cW <= 0 || d.cC <= 0 || (d.cC & 63) || d.cC > 4096 || d.K != 9 * d.cC || d.ldb != d.K) return VDN_EINVAL;
+    if ((long)d.cB * (d.cH + 2) * (d.cW + 2) != d.M) return VDN_EINVAL;
+    if (d.store != VDN_ST_PLAIN || !d.bias || d.rowadd || d.gamma || d.tab || d.row_group > 0 || d.out_dt != VDN_F16 || d.ldc != d.N ||
+        (d.N & 63) || !d.out || ((uintptr_t)d.out & 15) || ((uintptr_t)d.bias & 15))
+      return VDN_EINVAL;
+    if (d.act == VDN_ACT_RELU) {   // -> the next convolution's operand planes
+      if (!d.out_kt || !d.out8 || d.out_lo || d.res1 || d.res2 || d.pad_hi) return VDN_EINVAL;
+    } else if (d.act == VDN_ACT_NONE) {   // + residual(s) -> the unpadded split planes [and operand planes]
+      if (d.out_kt || !d.out_lo || !d.res1 || !d.res1_lo || d.res1_dt != VDN_F16 || (d.ldr1 & 7) || ((uintptr_t)d.res1 | (uintptr_t)d.res1_lo) & 15)
+        return VDN_EINVAL;
+      if (d.res2 && (!d.res2_lo || d.res2_dt != VDN_F16 || (d.ldr2 & 7) || ((uintptr_t)d.res2 | (uintptr_t)d.res2_lo) & 15)) return VDN_EINVAL;
+      if ((d.pad_hi == nullptr) != (d.out8 == nullptr) || ((uintptr_t)d.pad_hi & 15)) return VDN_EINVAL;
+    } else {
+      return VDN_EINVAL;
+    }
   } else {
     return VDN_EUNSUPPORTED;
   }
@@ -83,8 +101,8 @@ extern "C" int vdn_gemm(const vdn_gemm_desc* dp, vdn_stream stream) {
   if (d.out_lo && (d.out_dt == VDN_F32 || !d.out)) return VDN_EINVAL;
   if ((d.res1 && (d.ldr1 & 3)) || (d.res2 && (d.ldr2 & 3))) return VDN_EALIGN;
   if (((uintptr_t)d.A8 | (uintptr_t)d.W8 | (uintptr_t)d.out8) & 15) return VDN_EALIGN;
-  if ((d.A8 || d.W8) && (d.dt != VDN_F16 || d.a_mode != VDN_A_PLAIN || (d.K & 63) || (d.lda != d.K && !d.a_kt))) return VDN_EINVAL;
-  if (d.out8 && (d.dt != VDN_F16 || d.store != VDN_ST_PLAIN || d.out_dt != VDN_F16 || d.act != VDN_ACT_GELU || d.N != d.ldc || (d.N & 63) || !d.A8 || !d.W8))
+  if ((d.A8 || d.W8) && (d.dt != VDN_F16 || (d.a_mode != VDN_A_PLAIN && d.a_mode != VDN_A_PAD3X3) || (d.K & 63) || (d.lda != d.K && !d.a_kt))) return VDN_EINVAL;
+  if (d.out8 && (d.dt != VDN_F16 || d.store != VDN_ST_PLAIN || d.out_dt != VDN_F16 || (d.act != VDN_ACT_GELU && d.a_mode != VDN_A_PAD3X3) || d.N != d.ldc || (d.N & 63) || !d.A8 || !d.W8))
     return VDN_EINVAL;
   if ((d.a_kt || d.w_kt || d.out_kt || d.x8_terms) && (!d.A8 || !d.W8)) return VDN_EINVAL;
   // the 8-bit kernel addresses a lane's rows with 32-bit byte offsets inside a plane (row-major planes: rows * ld elements)
@@ -92,7 +110,8 @@ extern "C" int vdn_gemm(const vdn_gemm_desc* dp, vdn_stream stream) {
     return VDN_EUNSUPPORTED;
   if (d.x8_terms < 0 || d.x8_terms > 2) return VDN_EINVAL;  // K-tile-major planes: the 8-bit cross-term kernel only
   if (d.out_kt && (d.store != VDN_ST_PLAIN || d.out_dt != VDN_F16 || d.ldc != d.N || (d.N & 63) || d.res1 || d.res2 || d.tab ||
-                   d.rowadd || d.gamma || d.row_group > 0 || d.act == VDN_ACT_RELU)) return VDN_EINVAL;
+                   d.rowadd || d.gamma || d.row_group > 0 || (d.act == VDN_ACT_RELU && d.a_mode != VDN_A_PAD3X3))) return VDN_EINVAL;
+  if (d.pad_hi && d.a_mode != VDN_A_PAD3X3) return VDN_EINVAL;
   if (((uintptr_t)d.bias | (uintptr_t)d.gamma | (uintptr_t)d.tab | (uintptr_t)d.res1 | (uintptr_t)d.res2) & 7) return VDN_EALIGN;
   switch (d.store) {
     case VDN_ST_PLAIN:

@@ -165,7 +165,8 @@ struct APiece {
 
 // internal store codes (never in a descriptor): specialised epilogues, see emit4 / epi_flavour
 constexpr int VDN_STX_FC1 = 100, VDN_STX_RES = 101, VDN_STX_HEADS = 102, VDN_STX_HALF = 103, VDN_STX_RESHALF1 = 104,
-              VDN_STX_RESHALF2 = 105, VDN_STX_SPLITK = 106, VDN_STX_SUBPIX = 107;
+              VDN_STX_RESHALF2 = 105, VDN_STX_SPLITK = 106, VDN_STX_SUBPIX = 107,
+              VDN_STX_RCU1 = 108, VDN_STX_RCU2 = 109;   // the two epilogues of the padded-row 3x3 mode (gemm_x8.hip; include/vdn.h pad_hi)
 
 // ---- sub-pixel convolution (include/vdn.h: subpix): which low-resolution taps a phase reads, and in what order its tiles run.
 // Phase (a, b) of a ck x ck pixel shuffle sees the source rows {-1, 0} (a == 0), {0, 1} (a == ck - 1) or {0}, columns alike.
@@ -1396,8 +1397,10 @@ int launch_dt(const vdn_gemm_desc& d, hipStream_t s) {
   // 8-bit cross terms (gemm_x8.hip): plain A, fp16, K a multiple of 64, enough rows to fill 256 x 256 tiles
   if constexpr (DT == VDN_F16) {
     if (d.A8 && d.W8) {
-      if (d.a_mode == VDN_A_PLAIN && !d.relu_a && !(d.K & 63) && d.N >= 192 && (long)d.M * d.N >= 1024L * 1024 && tuning(d).x8 != 0)
+      if ((d.a_mode == VDN_A_PLAIN || d.a_mode == VDN_A_PAD3X3) && !d.relu_a && !(d.K & 63) && d.N >= 192 &&
+          (long)d.M * d.N >= 1024L * 1024 && tuning(d).x8 != 0)
         return x8_entry(d, s);
+      if (d.a_mode == VDN_A_PAD3X3) return VDN_EUNSUPPORTED;   // padded-row planes: no other kernel reads them
       // only that kernel reads K-tile-major planes and writes out8 / a lo-less half output
       if (d.a_kt || d.w_kt || d.out_kt || d.out8 || !d.A_lo || !d.W_lo) return VDN_EUNSUPPORTED;
     }

@@ -62,7 +62,10 @@ constexpr int x8_inflight(int newest, int k, bool four) {
 }
 
 // PAIR: the W rows of a tile are loaded in the order that gives every lane 8 consecutive output columns per block row
-template <int STORE, bool PAIR, int X8_BM>
+// TAPS: the padded-row 3x3 mode (include/vdn.h pad_hi): K = (tap, channel); slab s reads channel slab s % (cC / 64) of the
+// operand planes at the rows shifted by tap s / (cC / 64), a wave-uniform offset on the scalar base of issue(). Everything
+// else of the main loop is the plain kernel's; the mode has its own two epilogues (RCU1 / RCU2).
+template <int STORE, bool PAIR, int X8_BM, bool TAPS = false>
 __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
   using H = Half<VDN_F16>;
   using V8 = H::V8;
@@ -111,7 +114,10 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
   const char* Wh = (const char*)p.W;
   const char* A8v = (const char*)p.A8;             // x6 rows of A_hi; the remainder plane follows at + M K bytes
   const char* W8v = (const char*)p.W8;             // x6 rows of W_hi; remainder plane at + N ldb bytes
-  const size_t a8l = (size_t)p.M * p.K, w8l = (size_t)p.N * p.ldb;
+  const size_t a8l = (size_t)p.M * (TAPS ? p.cC : p.K), w8l = (size_t)p.N * p.ldb;
+  // TAPS: channel slabs per tap and 2^16 / that, rounded up (slab / cpt as a multiply: exact for slab < 9 cpt, cpt <= 64)
+  const int cpt = TAPS ? p.cC >> 6 : 1;
+  const unsigned tap_rcp = TAPS ? (65536u + cpt - 1) / cpt : 0u;
   // issue this wave's pieces of unit (slab, ph) into ring slot `slot` (ph is a compile-time constant)
   auto issue = [&](int slab, auto phc, int slot) {
     constexpr int ph = decltype(phc)::value;
@@ -119,11 +125,18 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
     char* ua = smem + slot * X8_U;
     char* uw = ua + X8_H;
     const char *ba, *bw;  // wave-uniform bases
+    int as = slab;        // K slab of the A planes
+    long sh = 0;          // TAPS: byte offset of the tap's row shift (rows are 64 bytes in every plane)
+    if constexpr (TAPS) {
+      const int tap = (int)(((unsigned)slab * tap_rcp) >> 16), ty = (tap * 11) >> 5;   // ty = tap / 3 for tap < 9
+      as = slab - tap * cpt;
+      sh = (long)((ty - 1) * (p.cW + 2) + (tap - 3 * ty - 1)) * 64;
+    }
     if constexpr (ph < 2) {
-      ba = Ah + (size_t)(2 * slab + ph) * a_kts;
+      ba = Ah + (size_t)(2 * as + ph) * a_kts + sh;
       bw = Wh + (size_t)(2 * slab + ph) * w_kts;
     } else {  // phase 2: A_lo6 with W_hi6; phase 3: A_hi6 with W_lo6
-      ba = A8v + (ph == 2 ? a8l : 0) + (size_t)slab * a8_kts;
+      ba = A8v + (ph == 2 ? a8l : 0) + (size_t)as * a8_kts + sh;
       bw = W8v + (ph == 2 ? 0 : w8l) + (size_t)slab * w8_kts;
     }
 #pragma unroll
@@ -343,7 +356,139 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const vdn_gemm_desc p) {
           const int n = nw + 32 * j + 16 * u + 8 * h + 4 * q;
           bias8[j][u][q] = (p.bias && n < p.N) ? *(const f32x4*)(p.bias + n) : z4;
         }
-    if (STORE == VDN_STX_FC1 && p.out8) {
+    if constexpr (STORE == VDN_STX_RCU1 || STORE == VDN_STX_RCU2) {
+      // ---- the padded-row 3x3 mode. A lane owns one padded activation row: one row -> (frame, y, x) decode gives its ring flag
+      // and its unpadded row. The bias goes into the accumulators first: its registers are free before the residual loads.
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[i][j][e] += bias8[j][e >> 3][(e >> 2) & 1][e & 3];
+      const int pw = p.cW + 2, fr = (p.cH + 2) * pw;
+      auto decode = [&](int m, size_t& mu) {   // inside the image (and the launch)? its row of the unpadded planes
+        const int b = m / fr, rem = m - b * fr, y = rem / pw, x = rem - y * pw;
+        mu = (size_t)(b * p.cH + y - 1) * p.cW + (x - 1);
+        return m < p.M && y >= 1 && y <= p.cH && x >= 1 && x <= p.cW;
+      };
+      // one row of padded operand planes: the lane's 32 values (stream position 16 j + 8 u + e = column 32 j + 16 u + 8 h + e of
+      // the wave's slab: one half of its x6 row-slab, as in the bias + GELU flavour below); ring rows pass zeros: zero bits
+      auto store_pad = [&](_Float16* hip, int m, bool img, const f16x32& hv, const f16x32& lv) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          V8 o;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = hv[8 * q + e];
+          *(V8*)(hip + kt_half_offset(1, m, nw + 32 * (q >> 1) + 16 * (q & 1) + 8 * h, p.M, p.ldc)) = o;
+        }
+        const int sb = x6_scale_byte(hv);
+        uint8_t* d8 = (uint8_t*)p.out8 + kt_byte_offset(1, m, nw, h, p.M, p.ldc);
+        x6_store_half(d8, hv, sb, img);
+        x6_store_half(d8 + (size_t)p.M * p.ldc, lv, sb - 10, img);
+      };
+      if constexpr (STORE == VDN_STX_RCU1) {   // relu(acc + bias) -> the next convolution's operand planes
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          const int m = mw + 32 * i + r;
+          size_t mu;
+          const bool img = decode(m, mu);
+          f16x32 hv, lv;
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              float v[8];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) {
+                const float a = acc[i][j][8 * u + e];
+                v[e] = img ? (a < 0.f ? 0.f : a) : 0.f;   // NaN passes through, as in the three-product path
+              }
+              V8 hh, ll;
+              split_planes(v, hh, ll);
+#pragma unroll
+              for (int e = 0; e < 8; ++e) { hv[16 * j + 8 * u + e] = hh[e]; lv[16 * j + 8 * u + e] = ll[e]; }
+            }
+          if (m < p.M && nw < p.N) store_pad((_Float16*)p.out, m, img, hv, lv);
+        }
+      } else {
+        // acc + bias + res1 [+ res2] -> the unpadded split planes; relu of it -> padded operand planes when a convolution
+        // follows (pad_hi / out8). Every residual row is added into the accumulators BEFORE the first store: res1 and res2 each
+        // have one set of registers, and the load of block row i + 1 is issued as soon as block row i has been added, so two
+        // loads are always in flight and none queues behind a store.
+        using T = _Float16;
+        V8 rh[2][2][2] = {}, rl[2][2][2] = {};   // [residual][j][u]
+        const bool two = p.res2 != nullptr;
+        // (unconditional loads from a clamped row, zeroed afterwards: behind a per-lane condition every load becomes a branch)
+        unsigned keep[NI];   // all ones for a row inside the image
+        auto load = [&](int i, int rr) {
+          size_t mu;
+          const bool img = decode(mw + 32 * i + r, mu);
+          if (rr == 0) keep[i] = img ? ~0u : 0u;
+          if ((rr == 1 && !two) || nw >= p.N) return;   // wave-uniform: no second residual / a column slab beyond N (N % 64 == 0)
+          const T* rp = (const T*)(rr ? p.res2 : p.res1);
+          const T* rq = (const T*)(rr ? p.res2_lo : p.res1_lo);
+          const size_t o = (img ? mu : 0) * (size_t)(rr ? p.ldr2 : p.ldr1) + nw + 8 * h;
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              rh[rr][j][u] = *(const V8*)(rp + o + 32 * j + 16 * u);
+              rl[rr][j][u] = *(const V8*)(rq + o + 32 * j + 16 * u);
+            }
+        };
+        auto add = [&](int i, int rr) {
+          if (rr == 1 && !two) return;
+          typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              const V8 a = __builtin_bit_cast(V8, __builtin_bit_cast(u32x4v, rh[rr][j][u]) & keep[i]);
+              const V8 b = __builtin_bit_cast(V8, __builtin_bit_cast(u32x4v, rl[rr][j][u]) & keep[i]);
+#pragma unroll
+              for (int e = 0; e < 8; ++e) acc[i][j][8 * u + e] += (float)a[e] + (float)b[e];
+            }
+        };
+        // (scheduling barriers: left alone, the scheduler hoists every load to the top and spills 368 registers)
+        load(0, 0);
+        load(0, 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          add(i, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (i + 1 < NI) load(i + 1, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          add(i, 1);
+          __builtin_amdgcn_sched_barrier(0);
+          if (i + 1 < NI) load(i + 1, 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          const int m = mw + 32 * i + r;
+          size_t mu;
+          const bool img = decode(m, mu);
+          f16x32 hv, lv;
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              float v[8];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] = img ? acc[i][j][8 * u + e] : 0.f;
+              V8 hh, ll;
+              split_planes(v, hh, ll);
+              const int n = nw + 32 * j + 16 * u + 8 * h;
+              if (img && n < p.N) store_out_planes<false, T>(p, mu * p.ldc + n, hh, ll);
+              hh = relu8(hh); ll = relu8(ll);   // hi and lo share their sign: the split of relu(v)
+#pragma unroll
+              for (int e = 0; e < 8; ++e) { hv[16 * j + 8 * u + e] = hh[e]; lv[16 * j + 8 * u + e] = ll[e]; }
+            }
+          if (p.out8 && m < p.M && nw < p.N) store_pad((_Float16*)p.pad_hi, m, img, hv, lv);
+        }
+      }
+    } else if (STORE == VDN_STX_FC1 && p.out8) {
       // bias + GELU -> the fp16 hi plane and the two planes of 6-bit rows of the consuming GEMM's A operand. The lane's 32
       // values of block row i (stream position 16 j + 8 u + e = column 32 j + 16 u + 8 h + e of the wave's 64-wide slab) are
       // one HALF of the slab: its scale comes from the lane's own values, no exchange (common.hpp x6 rows, order 1).
@@ -563,6 +708,20 @@ static int x8_launch(const vdn_gemm_desc& d, hipStream_t s) {
     if (attr != hipSuccess) return -(1000 + (int)attr);                                                                  \
     hipLaunchKernelGGL((gemm_x8_kernel<ST, PAIR, BM>), g, b, LDS, s, d);                                                 \
   } while (0)
+  if (d.a_mode == VDN_A_PAD3X3) {   // padded-row 3x3 mode (validated by vdn_gemm): its two epilogues
+#define VDN_X8T(ST)                                                                                                      \
+  do {                                                                                                                   \
+    static const hipError_t attr = hipFuncSetAttribute((const void*)gemm_x8_kernel<ST, true, BM, true>,                  \
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS); /* once */      \
+    if (attr != hipSuccess) return -(1000 + (int)attr);                                                                  \
+    hipLaunchKernelGGL((gemm_x8_kernel<ST, true, BM, true>), g, b, LDS, s, d);                                           \
+  } while (0)
+    if (d.act == VDN_ACT_RELU) VDN_X8T(VDN_STX_RCU1);
+    else VDN_X8T(VDN_STX_RCU2);
+#undef VDN_X8T
+    VDN_CHECK_LAUNCH();
+    return VDN_OK;
+  }
   int fl = epi_flavour(d);
   // plane-output flavours store 8 columns (16 bytes) per lane: column counts and strides must keep that aligned
   const bool a8 = !(d.N & 7) && !(d.ldc & 7) && !((uintptr_t)d.out & 15) && !((uintptr_t)d.out_lo & 15) && !((uintptr_t)d.out8 & 7);

@@ -205,7 +205,54 @@ __global__ __launch_bounds__(256) void pack_x8_f32_kernel(const float* __restric
   }
 }
 
+// Padded-row operand planes of relu(x) (include/vdn.h: vdn_pack_x8_relu_pad): one thread per PADDED row, 64-wide channel slab and
+// half. Image rows gather their 32 values in stream order 1 (the order of the GEMM epilogues that write the later convolutions'
+// planes); ring rows write zero bits. hi and lo share their sign, so the ReLU acts on each plane.
+__global__ __launch_bounds__(256) void pack_x8_relu_pad_kernel(const _Float16* __restrict__ hi, const _Float16* __restrict__ lo, int B, int H,
+                                                               int W, int C, _Float16* __restrict__ hi_pad, uint8_t* __restrict__ p8) {
+  const int pw = W + 2, fr = (H + 2) * pw, Mp = B * fr, hbs = C >> 5;
+  const size_t total = (size_t)Mp * hbs;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int m = (int)(i / hbs), hb = (int)(i - (size_t)m * hbs), slab = hb >> 1, h = hb & 1;
+    const int b = m / fr, rem = m - b * fr, y = rem / pw, x = rem - y * pw;
+    const bool img = y >= 1 && y <= H && x >= 1 && x <= W;
+    f16x32 hv = {}, lv = {};
+    f16x8 nat[4] = {};   // the hi plane's K tile 2 slab + h in natural column order
+    if (img) {
+      const size_t src = ((size_t)(b * H + y - 1) * W + (x - 1)) * C + slab * 64;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = 32 * (q >> 1) + 16 * (q & 1) + 8 * h;
+        const f16x8 a = relu8(*(const f16x8*)(hi + src + c)), l = relu8(*(const f16x8*)(lo + src + c));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { hv[8 * q + e] = a[e]; lv[8 * q + e] = l[e]; }
+        nat[q] = relu8(*(const f16x8*)(hi + src + 32 * h + 8 * q));
+      }
+    }
+    _Float16* d = hi_pad + kt_half_offset(1, m, hb * 32, Mp, C);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) *(f16x8*)(d + 8 * q) = nat[q];
+    const int sb = x6_scale_byte(hv);
+    uint8_t* d8 = p8 + kt_byte_offset(1, m, slab * 64, h, Mp, C);
+    x6_store_half(d8, hv, sb, img);
+    x6_store_half(d8 + (size_t)Mp * C, lv, sb - 10, img);
+  }
+}
+
 }  // namespace
+
+extern "C" int vdn_pack_x8_relu_pad(const void* hi, const void* lo, int B, int H, int W, int C, void* hi_pad, void* planes8,
+                                    vdn_stream stream) {
+  if (!hi || !lo || !hi_pad || !planes8 || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 63)) return VDN_EINVAL;
+  if ((long)B * (H + 2) * (W + 2) >= (1L << 25)) return VDN_EUNSUPPORTED;   // the row limit of the kernel that reads the planes
+  if (((uintptr_t)hi | (uintptr_t)lo | (uintptr_t)hi_pad | (uintptr_t)planes8) & 15) return VDN_EALIGN;
+  const size_t work = (size_t)B * (H + 2) * (W + 2) * (C >> 5);
+  const dim3 g((unsigned)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192));
+  hipLaunchKernelGGL(pack_x8_relu_pad_kernel, g, dim3(256), 0, (hipStream_t)stream, (const _Float16*)hi, (const _Float16*)lo, B, H, W, C,
+                     (_Float16*)hi_pad, (uint8_t*)planes8);
+  VDN_CHECK_LAUNCH();
+  return VDN_OK;
+}
 
 extern "C" int vdn_pack_x8_f32(const float* x, int rows, int ld, void* hi_kt, void* planes8, vdn_stream stream) {
   if (!x || !hi_kt || !planes8 || rows <= 0 || ld <= 0 || (ld & 63)) return VDN_EINVAL;

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("VDN_LIB") or os.path.join(PKG, "lib", "libvdn_hip.so"
 F16, BF16, F32, NONE = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SILU = 0, 1, 2, 3
 OUT_NONE, OUT_RELU, OUT_SIGMOID = 0, 1, 2   # final activation of a DPT head (include/vdn.h VDN_OUT_*)
-A_PLAIN, A_CONV3X3 = 0, 1
+A_PLAIN, A_CONV3X3, A_PAD3X3 = 0, 1, 2
 ST_PLAIN, ST_HEADS, ST_CONVT, ST_GEGLU = 0, 1, 2, 3
 EVAL_DEPTH, EVAL_DISP = 0, 1
 EVAL_TGM_ROWS, EVAL_TGM_FRAMES = 0, 1
@@ -45,6 +45,7 @@ class GemmDesc(C.Structure):
         ("a_kt", i32), ("w_kt", i32), ("out_kt", i32), ("x8_terms", i32),
         ("tuning", vp),
         ("subpix", i32), ("subpix_bias", fp),
+        ("pad_hi", vp),
     ]
 
 
@@ -103,6 +104,7 @@ EXPORTS = {
     "vdn_pack_bias": (C.c_int, [C.c_int, fp, C.c_int, C.c_int, C.c_int, fp, vp]),
     "vdn_pack_x8": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp]),
     "vdn_pack_x8_f32": (C.c_int, [fp, C.c_int, C.c_int, vp, vp, vp]),
+    "vdn_pack_x8_relu_pad": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "vdn_gemm_workspace_bytes": (C.c_size_t, [C.POINTER(GemmDesc)]),
     "vdn_groupnorm_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "vdn_mask_down1": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, vp]),

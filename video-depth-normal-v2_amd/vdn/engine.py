@@ -351,15 +351,25 @@ class DPTEngine:
             sc = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + 1e-5)
             return w * sc[:, None, None, None], (b - bn.running_mean.detach().float()) * sc + bn.bias.detach().float()
 
-        def rcu(r):
+        # The RCU convolutions of the two high-resolution fusion blocks on the cross-term kernel (include/vdn.h pad_hi; DESIGN.md
+        # §5 item 2c): their weights once more as that kernel's planes. VDN_RCU_X3 keeps the three-product launches (A/B switch)
+        self.rcu_x8 = rt.x8_capable(features) and features % 256 == 0 and not os.environ.get("VDN_RCU_X3")
+        self.rcu_path = {}     # fusion block -> "x8" | "x3": what its last _fusion call launched (tests, tools)
+        self._rcu_x8_ok = True  # run(): off for the temporal head's sharded and streaming calls
+
+        def rcu(r, x8):
             w1, b1 = fold(r.conv1, getattr(r, "bn1", None))
             w2, b2 = fold(r.conv2, getattr(r, "bn2", None))
-            return dict(w1=pack.conv3x3(w1, h), b1=pack.f32(b1), w2=pack.conv3x3(w2, h), b2=pack.f32(b2))
+            d = dict(w1=pack.conv3x3(w1, h), b1=pack.f32(b1), w2=pack.conv3x3(w2, h), b2=pack.f32(b2))
+            if x8:
+                d.update(x1=pack.conv3x3_x8(w1, h), x2=pack.conv3x3_x8(w2, h))
+            return d
 
         self.ref = {}
         for i in range(1, 5):
             f = getattr(s, f"refinenet{i}")
-            self.ref[i] = dict(r1=rcu(f.resConfUnit1), r2=rcu(f.resConfUnit2),
+            x8 = self.rcu_x8 and i in (1, 2)
+            self.ref[i] = dict(r1=rcu(f.resConfUnit1, x8), r2=rcu(f.resConfUnit2, x8),
                                wo=pack.conv1x1(f.out_conv.weight, h), bo=pack.f32(f.out_conv.bias))
         self.oc1 = (pack.conv3x3(s.output_conv1.weight, h), pack.f32(s.output_conv1.bias))
         self.oc2 = (pack.conv3x3(s.output_conv2[0].weight, h), pack.f32(s.output_conv2[0].bias))
@@ -412,9 +422,26 @@ class DPTEngine:
         H, W = size_in
         f = self.ref[i]
         x = prev
-        if skip is not None:
-            x = self._rcu(f["r1"], skip, Bf, H, W, f"ff{i}_s", extra=prev)
-        u = self._rcu(f["r2"], x, Bf, H, W, f"ff{i}_u")
+        M = Bf * H * W
+        if self.rcu_x8 and self._rcu_x8_ok and i in (1, 2) and rt.x8_rows(Bf * (H + 2) * (W + 2)):
+            # Four shifted-row cross-term GEMMs on padded operand planes that ping-pong between two buffers: one pack pass for
+            # the block's first operand, every later one comes out of the convolution before it. The results land where the
+            # three-product path writes them (ff{i}_s, ff{i}_u: unpadded split planes)
+            self.rcu_path[i] = "x8"
+            pa, pb = rt.pad_operand("rcu_pa", Bf, H, W, F), rt.pad_operand("rcu_pb", Bf, H, W, F)
+            rt.pack_x8_relu_pad(skip if skip is not None else x, pa)
+            if skip is not None:
+                r = f["r1"]
+                rt.conv3x3_pad(pa, r["x1"], F, r["b1"], out_pad=pb)
+                x = rt.conv3x3_pad(pb, r["x2"], F, r["b2"], out=rt.hbuf(f"ff{i}_s", (M, F)), res1=skip, res2=prev, out_pad=pa)
+            r = f["r2"]
+            rt.conv3x3_pad(pa, r["x1"], F, r["b1"], out_pad=pb)
+            u = rt.conv3x3_pad(pb, r["x2"], F, r["b2"], out=rt.hbuf(f"ff{i}_u", (M, F)), res1=x)
+        else:
+            self.rcu_path[i] = "x3"
+            if skip is not None:
+                x = self._rcu(f["r1"], skip, Bf, H, W, f"ff{i}_s", extra=prev)
+            u = self._rcu(f["r2"], x, Bf, H, W, f"ff{i}_u")
         if size_out is None:  # run(): out_conv and the resize are taken over by the low-resolution output_conv1
             return u
         v = rt.hbuf(f"ff{i}_v", (Bf * H * W, F))
@@ -432,6 +459,7 @@ class DPTEngine:
         OUT_SIGMOID (the metric head, metric_depth/depth_anything_v2/dpt.py:112-113,183); both are launch arguments of the
         last kernel, whichever of the three endings below runs."""
         rt, C, F, oc = self.rt, self.C, self.F, self.oc
+        self._rcu_x8_ok = exch is None and stream is None
         P = ph * pw
         pr = []
         for i in range(4):

@@ -106,6 +106,13 @@ def conv3x3_taps(w: torch.Tensor, half) -> torch.Tensor:
     return _pack(abi.PACK_CONV3X3_TAPS, w, co, ci, 0, half)
 
 
+def conv3x3_x8(w: torch.Tensor, half) -> "X8":
+    """[Co,Ci,3,3] -> the cross-term kernel's weight planes of the padded-row 3x3 mode (include/vdn.h pad_hi): K = (tap, ci),
+    K-tile-major, x6 rows in the stream order of the GEMM epilogues that write the activation planes."""
+    assert w.shape[1] % 64 == 0, w.shape
+    return X8(conv3x3_taps(w, half), ORDER_GEMM)
+
+
 def lowres_oc1_compose(w: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """output_conv1 moved in front of the 2x resize (DPTEngine.run): w [Co, F, 3, 3] (dpt.py:145), wo [F, F(,1,1)] / bo [F] the
     1x1 out_conv of refinenet1 (blocks.py:146). Returns fp64 ([9 Co, F], [9 Co]): row t*Co + c = (W_t Wo)[c], bias W_t bo,

@@ -74,6 +74,22 @@ class KT:
         self.hi, self.p8 = hi, p8
 
 
+class PadKT:
+    """A 3x3 convolution's operand map in the padded-row planes of the cross-term GEMM (include/vdn.h pad_hi): `hi` fp16
+    [C/32, Mp, 32] and `p8` u8 [2, C/64, Mp, 64] with Mp = B (H+2) (W+2), views into `hi_store` / `p8_store`, which carry `guard` =
+    W + 3 zero rows of 64 bytes in front and behind. Ring rows are zero bits. Written by Runtime.pack_x8_relu_pad and by the two
+    epilogues of Runtime.conv3x3_pad; Runtime.pad_operand hands it out."""
+    __slots__ = ("hi", "p8", "hi_store", "p8_store", "guard", "B", "H", "W", "C", "rows")
+
+    def __init__(self, hi_store: torch.Tensor, p8_store: torch.Tensor, B: int, H: int, W: int, C: int):
+        self.B, self.H, self.W, self.C = B, H, W, C
+        self.rows, self.guard = B * (H + 2) * (W + 2), W + 3
+        g, Mp = self.guard, self.rows
+        self.hi_store, self.p8_store = hi_store, p8_store
+        self.hi = hi_store[32 * g:32 * g + C * Mp].view(C // 32, Mp, 32)
+        self.p8 = p8_store[64 * g:64 * g + 2 * C * Mp].view(2, C // 64, Mp, 64)
+
+
 def _hl(t):
     """(hi tensor, lo pointer or None) of an HL, a KT or a plain tensor."""
     if isinstance(t, HL):
@@ -160,6 +176,14 @@ class Runtime:
             return self.hbuf(name, shape)
         return KT(self.buf(name + "_kt", shape, self.half), self.buf(name + "8", (2, *shape), torch.uint8))
 
+    def pad_operand(self, name: str, B: int, H: int, W: int, C: int) -> PadKT:
+        """The padded-row operand planes of a B x H x W x C map, by name (zero-initialised once: nothing ever writes the guard
+        rows, and every producer rewrites the ring rows as zeros)."""
+        assert C % 64 == 0 and self.half == torch.float16, (C, self.half)
+        Mp, g = B * (H + 2) * (W + 2), W + 3
+        return PadKT(self.buf(name + "_pkt", (C * Mp + 64 * g,), self.half, zero=True),
+                     self.buf(name + "_p8", (2 * C * Mp + 128 * g,), torch.uint8, zero=True), B, H, W, C)
+
     def x8_capable(self, Cn: int) -> bool:
         """Can an engine whose linears are Cn wide use the cross-term kernel (csrc/gemm_x8.hip)? fp16 split planes only;
         VDN_X8=0 keeps the three-fp16-product kernels."""
@@ -240,7 +264,7 @@ class Runtime:
              row_skip: int = 0, heads: Optional[dict] = None, convt: Optional[dict] = None, tag: Optional[str] = None,
              a8: Optional[torch.Tensor] = None, w8: Optional[torch.Tensor] = None, out8: Optional[torch.Tensor] = None,
              a_kt: bool = False, w_kt: bool = False, out_kt: bool = False, x8_terms: int = 0,
-             subpix_bias: Optional[torch.Tensor] = None):
+             subpix_bias: Optional[torch.Tensor] = None, pad: Optional[PadKT] = None, pad_out: Optional[PadKT] = None):
         """A, W and out may be operand objects: a pack.Linear weight follows its activation, on the cross-term kernel for a KT
         (a8 / w8 / a_kt / w_kt filled from the two), else on its split planes, where x8_terms does not apply; a KT `out`
         fills out8 / out_kt. The keywords give the same planes by hand (tests and tools). subpix_bias (with conv= on the
@@ -270,6 +294,9 @@ class Runtime:
             d.cOH, d.cOW, d.cstride = conv["OH"], conv["OW"], conv["stride"]
             d.lda = conv["C"]
             d.conv_korder = conv.get("korder", 1 if conv["C"] % 64 == 0 else 0)  # must match pack.conv3x3
+        elif pad is not None:   # padded-row 3x3 mode (include/vdn.h pad_hi; conv3x3_pad below)
+            d.a_mode = abi.A_PAD3X3
+            d.cB, d.cH, d.cW, d.cC = pad.B, pad.H, pad.W, pad.C
         else:
             d.a_mode = abi.A_PLAIN
             d.lda = lda if lda is not None else K
@@ -318,6 +345,8 @@ class Runtime:
             d.A8, d.W8 = a8.data_ptr(), w8.data_ptr()
         if out8 is not None:
             d.out8 = out8.data_ptr()
+        if pad_out is not None:   # relu of a residual-flavour result as the next convolution's padded operand planes
+            d.pad_hi, d.out8 = pad_out.hi.data_ptr(), pad_out.p8.data_ptr()
         d.a_kt, d.w_kt, d.out_kt = int(a_kt), int(w_kt), int(out_kt)   # K-tile-major planes (include/vdn.h)
         d.x8_terms = int(x8_terms)
         if subpix_bias is not None:
@@ -855,6 +884,27 @@ class Runtime:
         (include/vdn.h vdn_pack_x8), for activations whose producer writes plain split planes."""
         rows, ld = t.hi.shape
         self._launch(abi.lib.vdn_pack_x8, t.hi.data_ptr(), t.lo.data_ptr(), rows, ld, hi_kt.data_ptr(), planes8.data_ptr(), 1, order)
+
+    def pack_x8_relu_pad(self, x: HL, out: PadKT):
+        """relu(x), split planes [B H W, C] row-major -> the padded-row operand planes `out` (include/vdn.h vdn_pack_x8_relu_pad)."""
+        assert x.lo is not None and tuple(x.hi.shape) == (out.B * out.H * out.W, out.C) and x.hi.dtype == torch.float16, x.hi.shape
+        self._launch(abi.lib.vdn_pack_x8_relu_pad, x.hi.data_ptr(), x.lo.data_ptr(), out.B, out.H, out.W, out.C, out.hi.data_ptr(),
+                     out.p8.data_ptr())
+
+    def conv3x3_pad(self, a: PadKT, w, N: int, bias: torch.Tensor, *, out_pad: Optional[PadKT] = None, out: Optional[HL] = None,
+                    res1: Optional[HL] = None, res2: Optional[HL] = None, tag: Optional[str] = None):
+        """3x3, stride 1, pad 1 convolution of the padded-row operand `a` with `w` (pack.conv3x3_x8) on the cross-term kernel.
+        Without `out`: relu(conv + bias) -> `out_pad`, the next convolution's operand. With `out` (unpadded split planes
+        [B H W, N]): conv + bias + res1 [+ res2] -> out, and relu of it -> `out_pad` if given."""
+        kw = dict(a8=a.p8, w8=w.p8, a_kt=True, w_kt=True, bias=bias, pad=a, tag=tag)
+        if out is None:
+            assert out_pad is not None and res1 is None and res2 is None and (out_pad.B, out_pad.H, out_pad.W, out_pad.C) == (a.B, a.H, a.W, N)
+            self.gemm(HL(a.hi), HL(w.hi), a.rows, N, 9 * a.C, out=HL(out_pad.hi.view(-1, N)), out8=out_pad.p8, out_kt=True, act=abi.ACT_RELU, **kw)
+            return out_pad
+        assert res1 is not None and tuple(out.hi.shape) == (a.B * a.H * a.W, N)
+        assert out_pad is None or (out_pad.B, out_pad.H, out_pad.W, out_pad.C) == (a.B, a.H, a.W, N)
+        self.gemm(HL(a.hi), HL(w.hi), a.rows, N, 9 * a.C, out=out, res1=res1, res2=res2, pad_out=out_pad, **kw)
+        return out
 
     def pack_x8_f32(self, x: torch.Tensor, hi_kt: torch.Tensor, planes8: torch.Tensor):
         """fp32 [rows, ld] -> the cross-term GEMM's A operand (include/vdn.h vdn_pack_x8_f32)."""

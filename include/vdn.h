@@ -477,6 +477,50 @@ int vdn_normal_loss_backward_trip(int wide);
 int vdn_normal_loss_backward(const float* pred, const float* target, int target_is_depth, const uint8_t* mask, int frames,
                              int H, int W, const double* count, const double* coeff, float* grad_pred, vdn_stream stream);
 
+/* Angular error of predicted normals, and normals as a picture. An extension beyond the reference, which has the criterion
+ * above and nothing else for normals. pred, target, target_is_depth and mask as for vdn_normal_eval.
+ * The angle of a pixel with prediction a and target b, three f32 components each, widened to fp64:
+ *   b        the stored target, or with target_is_depth (-Ix, -Iy, 1) of the Sobel / 8 stencil on the reflect-padded depth;
+ *            the division by sqrt(|.|^2 + 1e-8) of vdn_normal_vector does not change the direction and is not applied;
+ *   angle    atan2(|a x b|, a . b) * 180 / pi, every product and sum rounded on its own (contraction is off). Not acos of a
+ *            cosine: that loses half the digits near 0 and 180 degrees;
+ *   NaN      when any of the six components is NaN or +-inf; otherwise 90 when |a|^2 == 0 or |b|^2 == 0, the angle whose
+ *            cosine is the 0 that the clamped norms of F.cosine_similarity give the criterion.
+ * Kept pixels: mask non-zero (NULL = all ones), after the erosion of vdn_erode_mask3 when erode != 0, which is what
+ * vdn_normal_eval scores. A dropped pixel is selected away and never multiplied: NaN under it reaches nothing.
+ * vdn_normal_angle_map   — out f32 [frames, H, W]: the angle rounded to f32 once, NaN at a dropped pixel.
+ * vdn_normal_angle_stats — rows f64 [1 + B + B T][9]: row 0 all kept pixels of the batch, rows 1 .. B each item, rows 1 + B ..
+ *                          each frame. Columns n, mean, median, rmse, a5, a7_5, a11_25, a22_5, a30: the kept pixels, the mean
+ *                          angle, numpy.median of the angles rounded to f32 (the mean of the two middle values for even n,
+ *                          taken in fp64), sqrt(mean(angle^2)), and the share of kept pixels with angle < 5, 7.5, 11.25,
+ *                          22.5 and 30 degrees (strict, compared in fp64). A set with n == 0 has n = 0 and NaN elsewhere; a set
+ *                          with a NaN angle under a kept pixel has NaN in every column but n, and the sets that do not
+ *                          contain it are untouched.
+ *                          One sweep over the inputs leaves per-block partial sums and the f32 angle plane in `workspace`
+ *                          (vdn_normal_angle_stats_workspace_bytes(B, T, H, W); 8-byte aligned); a one-block fold makes the
+ *                          sums of frames, items and batch and the two median ranks of every set; the exact three-pass
+ *                          radix select runs over the plane for frames, items and batch. Sums are fp64 in a fixed order (a
+ *                          lane's stride, the wave's xor-shuffle, the four waves, a frame's blocks, an item's frames and
+ *                          the items, each in index order) without floating-point atomics; the select's integer
+ *                          histograms are exact in any order: two runs give the same bits. A lane owns four consecutive
+ *                          pixels whenever H * W is a multiple of 4 (by 16-byte loads where pred, a stored target and the
+ *                          workspace are 16-byte aligned, a load per pixel otherwise), so the order depends on the shape
+ *                          alone, not on where a tensor starts.
+ * vdn_normal_colorize    — x f32 [N, 3, H, W] normals of any length, or with from_depth a depth map [N, H, W] whose normal
+ *                          is made per pixel as above; out u8 [N, H, W, 3], no alignment needed.
+ *                          v_c = ((a_c / |a|) * 0.5 + 0.5) * 255 in fp64 with separate roundings, byte = (uint8)floor(v_c +
+ *                          0.5); x, y, z go to R, G, B, reversed when bgr != 0. A zero or non-finite vector gives 128, 128, 128.
+ * VDN_EINVAL: a null required pointer, a size <= 0, H < 2 or W < 2 (vdn_normal_colorize: only with from_depth).
+ * VDN_EUNSUPPORTED: H * W > INT32_MAX, frames or B * T > 65535, B * T * H * W >= 2^32 (vdn_normal_angle_stats: the batch is
+ * one set of the select). VDN_EALIGN: a float pointer off 4 bytes, workspace or rows off 8. All returned before anything is
+ * launched.                                                                                                              */
+int vdn_normal_angle_map(const float* pred, const float* target, int target_is_depth, const uint8_t* mask, int erode, int frames,
+                         int H, int W, float* out, vdn_stream stream);
+size_t vdn_normal_angle_stats_workspace_bytes(int B, int T, int H, int W);
+int vdn_normal_angle_stats(const float* pred, const float* target, int target_is_depth, const uint8_t* mask, int erode, int B, int T,
+                           int H, int W, void* workspace, double* rows, vdn_stream stream);
+int vdn_normal_colorize(const float* x, int from_depth, int bgr, uint8_t* out, int N, int H, int W, vdn_stream stream);
+
 /* The depth criterion on the device: VideoDepthLoss of loss/loss.py:326-367 as the reference's scripts construct it
  * (trim = 0, batch-based reduction, no SSIM term), the forward (its gradient: vdn_depth_loss_backward below);
  * scripts/train*.py validate:

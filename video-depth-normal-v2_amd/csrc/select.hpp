@@ -10,6 +10,9 @@
 //   vdn_frame_median       (refine.hip)  a set per frame, one key per element, ranks floor and ceil of (n - 1) / 2;
 //   vdn_depth_loss         (loss.hip)    a set per frame, slot 0 the aligned prediction, slot 1 the target, one rank;
 //   vdn_depth_loss_trimmed (loss.hip)    one set of all frames, slots data / stable / absRel, ranks computed on the device.
+// A caller whose ranks differ from set to set writes the states itself and starts select_passes:
+//   vdn_normal_angle_stats (normal_metrics.hip)  frames, items and the batch as three selects over one plane, each set's
+//                                        ranks floor and ceil of (m - 1) / 2 among its own m keys, written by its fold kernel.
 // Passes take the top 11, the next 11 and the last 10 bits: a histogram per (set, slot) of the keys that match the prefix
 // decided so far (integer atomics, in LDS and then in `hist`: counts do not depend on the order, so two runs give the same
 // bits), then a one-block scan that finds the bin holding the rank, extends the prefix and clears the bins. After
@@ -124,7 +127,25 @@ __global__ __launch_bounds__(256) void select_scan_kernel(SelState* st, uint32_t
 }
 
 inline size_t select_workspace_bytes(int sets, int slots) { return (size_t)sets * slots * (NBIN * sizeof(uint32_t) + sizeof(SelState)); }
-inline SelState* select_state(void* workspace, int sets, int slots) { return (SelState*)((uint32_t*)workspace + (size_t)sets * slots * NBIN); }
+__host__ __device__ inline SelState* select_state(void* workspace, int sets, int slots) { return (SelState*)((uint32_t*)workspace + (size_t)sets * slots * NBIN); }
+
+// The six launches of the three passes, for a workspace whose bins are zero and whose states hold prefix 0 and each
+// (set, slot)'s own rank: what select_launch starts after its init kernel, and what a caller starts itself when the ranks
+// differ from set to set (vdn_normal_angle_stats: the median of each set's own count, written by its fold kernel).
+template <typename KeyFn>
+inline void select_passes(const KeyFn& key_of, int frames, int group, size_t n, void* workspace, hipStream_t s) {
+  constexpr int S = KeyFn::SLOTS;
+  const int sets = frames / group;
+  uint32_t* hist = (uint32_t*)workspace;
+  SelState* st = select_state(workspace, sets, S);
+  const dim3 grid(grid_for((n + KeyFn::PER - 1) / KeyFn::PER, 64), frames), scan(sets * S), block(256);
+  hipLaunchKernelGGL((select_hist_kernel<0, KeyFn>), grid, block, 0, s, key_of, n, group, st, hist);
+  hipLaunchKernelGGL(select_scan_kernel<0>, scan, block, 0, s, st, hist);
+  hipLaunchKernelGGL((select_hist_kernel<1, KeyFn>), grid, block, 0, s, key_of, n, group, st, hist);
+  hipLaunchKernelGGL(select_scan_kernel<1>, scan, block, 0, s, st, hist);
+  hipLaunchKernelGGL((select_hist_kernel<2, KeyFn>), grid, block, 0, s, key_of, n, group, st, hist);
+  hipLaunchKernelGGL(select_scan_kernel<2>, scan, block, 0, s, st, hist);
+}
 
 // `frames` frames of n elements each (n a multiple of KeyFn::PER, n < 2^32), `group` frames to a set (frames a multiple of
 // group; fewer than 2^32 keys per set); workspace of select_workspace_bytes(frames / group, KeyFn::SLOTS), 4-byte aligned.
@@ -134,16 +155,9 @@ inline void select_launch(const KeyFn& key_of, int frames, int group, size_t n, 
                           hipStream_t s) {
   constexpr int S = KeyFn::SLOTS;
   const int sets = frames / group;
-  uint32_t* hist = (uint32_t*)workspace;
-  SelState* st = select_state(workspace, sets, S);
-  const dim3 grid(grid_for((n + KeyFn::PER - 1) / KeyFn::PER, 64), frames), scan(sets * S), block(256);
-  hipLaunchKernelGGL(select_init_kernel<S>, dim3(grid_for((size_t)sets * S * NBIN, 1024)), block, 0, s, st, hist, sets, ranks);
-  hipLaunchKernelGGL((select_hist_kernel<0, KeyFn>), grid, block, 0, s, key_of, n, group, st, hist);
-  hipLaunchKernelGGL(select_scan_kernel<0>, scan, block, 0, s, st, hist);
-  hipLaunchKernelGGL((select_hist_kernel<1, KeyFn>), grid, block, 0, s, key_of, n, group, st, hist);
-  hipLaunchKernelGGL(select_scan_kernel<1>, scan, block, 0, s, st, hist);
-  hipLaunchKernelGGL((select_hist_kernel<2, KeyFn>), grid, block, 0, s, key_of, n, group, st, hist);
-  hipLaunchKernelGGL(select_scan_kernel<2>, scan, block, 0, s, st, hist);
+  hipLaunchKernelGGL(select_init_kernel<S>, dim3(grid_for((size_t)sets * S * NBIN, 1024)), dim3(256), 0, s,
+                     select_state(workspace, sets, S), (uint32_t*)workspace, sets, ranks);
+  select_passes(key_of, frames, group, n, workspace, s);
 }
 
 }  // namespace

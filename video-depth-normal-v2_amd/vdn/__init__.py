@@ -36,6 +36,9 @@ def __getattr__(name):
     if name == "normals":  # normal_vector and VideoNormalLoss on the device (vdn/normals.py)
         import importlib
         return importlib.import_module(".normals", __name__)
+    if name == "normal_metrics":  # angular-error statistics of predicted normals on the device (vdn/normal_metrics.py)
+        import importlib
+        return importlib.import_module(".normal_metrics", __name__)
     if name == "loss":   # VideoDepthLoss on the device (vdn/loss.py)
         import importlib
         return importlib.import_module(".loss", __name__)

@@ -12,7 +12,7 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libvdn_hip.so")
 SOURCES = ["gemm_big_f16.hip", "gemm_big_bf16.hip", "gemm_small_f16.hip", "gemm_small_bf16.hip", "gemm_x8.hip", "gemm.hip", "attn.hip",
            "norm.hip", "spatial.hip", "tail.hip", "pack.hip", "stitch.hip", "refine.hip",
-           "dn_head.hip", "hiera.hip", "lane_attn.hip", "eval.hip", "vis.hip", "normals.hip", "normals_grad.hip", "loss.hip",
+           "dn_head.hip", "hiera.hip", "lane_attn.hip", "eval.hip", "vis.hip", "normals.hip", "normals_grad.hip", "normal_metrics.hip", "loss.hip",
            "loss_grad.hip", "ssim.hip", "prep.hip", "metric.hip", "points.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

@@ -508,6 +508,36 @@ class Runtime:
         ws = self._ws("normal_eval_ws", abi.lib.vdn_normal_eval_workspace_bytes(F))
         self._launch(abi.lib.vdn_normal_eval, p, t, int(target.dim() == 3), m, F, H, W, ws.data_ptr(), fs, fc, o)
 
+    def normal_angle_map(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], erode: bool, out: torch.Tensor):
+        """out f32 [F, H, W] <- the angle in degrees between pred f32 [F, 3, H, W] and target, normals [F, 3, H, W] or a depth map
+        [F, H, W]; NaN where the u8 mask (eroded first with `erode`) drops the pixel (vdn_normal_angle_map)."""
+        F, H, W, p, t, m = self._normal_args("normal_angle_map", pred, target, mask)
+        self._launch(abi.lib.vdn_normal_angle_map, p, t, int(target.dim() == 3), m, int(erode), F, H, W,
+                     checked_ptr("normal_angle_map: out", out, self.device, _f32, (F, H, W)))
+
+    def normal_angle_stats(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], erode: bool, B: int, T: int,
+                           rows: torch.Tensor):
+        """rows f64 [1 + B + B T, 9] <- n, mean, median, rmse and the five shares of the angles of pred f32 [B T, 3, H, W]
+        against target, for the batch, each item and each frame (vdn_normal_angle_stats)."""
+        F, H, W, p, t, m = self._normal_args("normal_angle_stats", pred, target, mask)
+        if F != B * T:
+            raise abi.VdnError(f"normal_angle_stats: {F} frames are not B * T = {B} * {T}")
+        r = checked_ptr("normal_angle_stats: rows", rows, self.device, _f64, (1 + B + F, 9))
+        nbytes = abi.lib.vdn_normal_angle_stats_workspace_bytes(B, T, H, W)
+        if nbytes == 0:
+            raise abi.VdnError(f"normal_angle_stats: unsupported shape B, T, H, W = {(B, T, H, W)} (B * T <= 65535)")
+        ws = self._ws("normal_angle_ws", nbytes)
+        self._launch(abi.lib.vdn_normal_angle_stats, p, t, int(target.dim() == 3), m, int(erode), B, T, H, W, ws.data_ptr(), r)
+
+    def normal_colorize(self, x: torch.Tensor, out: torch.Tensor, bgr: bool = False):
+        """out u8 [N, H, W, 3] <- the unit vector of f32 normals x [N, 3, H, W], or of the normals of a depth map x [N, H, W], as
+        bytes (vdn_normal_colorize)."""
+        from_depth = getattr(x, "ndim", 4) == 3
+        px = checked_ptr("normal_colorize: x", x, self.device, _f32, 3 if from_depth else (None, 3, None, None))
+        N, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+        self._launch(abi.lib.vdn_normal_colorize, px, int(from_depth), int(bgr),
+                     checked_ptr("normal_colorize: out", out, self.device, _u8, (N, H, W, 3)), N, H, W)
+
     def normal_loss_backward(self, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], count: torch.Tensor,
                              coeff: torch.Tensor, grad: torch.Tensor):
         """grad f32 [F, 3, H, W] <- coeff * d normal_loss / d pred (vdn_normal_loss_backward). pred, target and mask as for

@@ -29,6 +29,7 @@ import torch
 from . import prep
 from .eval import eval_batch_by_data
 from .metric import KEYS as DEPTH_METRIC_KEYS, eval_depth_batch
+from .normal_metrics import angular_error
 
 
 def prepare_batch(batch, *, input_key="depth_anything_v2", normalize_input=False, device="cuda") -> Dict[str, torch.Tensor]:
@@ -144,6 +145,23 @@ def evaluate_step(model, batch, *, with_rgb=True, meter: Optional[MetricMeter] =
     depth, _ = _predict(model, t, with_rgb)
     rows = eval_batch_by_data(depth, t["gt"], device=device, seq_len=t["gt"].shape[1], domain=domain,
                               dataset_max_depth=dataset_max_depth)
+    if meter is not None:
+        meter.add(rows)
+    return rows
+
+
+@torch.no_grad()
+def evaluate_normals_step(model, batch, *, meter: Optional[MetricMeter] = None, erode=True, input_key="depth_anything_v2",
+                          device="cuda") -> torch.Tensor:
+    """evaluate_step's body for the normals -> float64 [B, 9] on the device: per item the nine vdn.normal_metrics
+    (normal_metric_names: n, mean, median, rmse and the shares under 5 .. 30 degrees) of the normals of model(input_depth, rgb)
+    against the normals of the inverse ground-truth depth, made per pixel (from_depth), under the batch's mask (eroded as
+    VideoNormalLoss erodes it, unless erode=False); also added to `meter`, a MetricMeter, whose means() are then the NaN-means
+    of the columns over the items. An extension: the reference's scripts do not score normals in degrees. No host
+    synchronisation."""
+    t = prepare_batch(batch, input_key=input_key, device=device)
+    _, normals = _predict(model, t, True)
+    rows = angular_error(normals, t["gt"], t["mask"], from_depth=True, erode=erode, device=device)["items"]
     if meter is not None:
         meter.add(rows)
     return rows

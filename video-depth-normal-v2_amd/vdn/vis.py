@@ -7,14 +7,17 @@ Three cases the reference leaves to an undefined float -> uint8 cast are defined
 constant map (max == min) gives palette index 0 everywhere, a depth outside a caller-supplied [min, max] clamps to index 0 /
 255, and a NaN depth gives index 0.
 
-matplotlib is not needed: the palettes are literals (vdn/_palettes.py, written by tools/make_vis_palettes.py)."""
+matplotlib is not needed: the palettes are literals (vdn/_palettes.py, written by tools/make_vis_palettes.py).
+
+colorize_normals is the picture of a normal map, which the reference does not have: each unit vector's x, y, z as the red,
+green and blue byte (csrc/normal_metrics.hip)."""
 from __future__ import annotations
 
 from typing import Dict, Optional
 
 import torch
 
-from ._device import runtime as _runtime
+from ._device import runtime as _runtime, runtime_for as _runtime_for, stage
 from ._palettes import PALETTES
 from .runtime import Runtime
 
@@ -117,3 +120,43 @@ def colorize(depth: torch.Tensor, palette: str = "Spectral_r", order: str = "bgr
     with torch.cuda.device(d.device):
         out = _colorize(_runtime(d.device), d, palette, order, scope, grayscale, gray_channels, raw, margin, minmax)
     return out if depth.dim() == 3 else out[0]
+
+
+def colorize_normals(normals: torch.Tensor, *, from_depth: bool = False, order: str = "rgb", device="cuda") -> torch.Tensor:
+    """normals [N, 3, H, W] or [B, T, 3, H, W] of any length -> uint8 [N, H, W, 3] or [B, T, H, W, 3] on the device: each
+    component of the unit vector as the byte floor(((a_c / |a|) * 0.5 + 0.5) * 255 + 0.5), in fp64; x, y, z are red, green and
+    blue in that order, or reversed for order='bgr'. A zero-length or non-finite vector gives 128, 128, 128 (grey).
+
+    from_depth=True takes a depth clip [N, H, W], [B, T, H, W] or [B, T, 1, H, W] instead and paints the normal (-Ix, -Iy, 1) of
+    the Sobel / 8 stencil on the reflect-padded map, made per pixel and never stored: the picture of
+    vdn.normals.normal_vector(depth) without that tensor or its rounding to float32 (H, W >= 2). A tensor that is not on a GPU
+    is copied to `device` once."""
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
+    if not isinstance(normals, torch.Tensor):
+        raise ValueError(f"expected a torch tensor, got {type(normals).__name__}")
+    shape = tuple(normals.shape)
+    if from_depth:
+        if len(shape) == 5 and shape[2] == 1:
+            shape = shape[:2] + shape[3:]
+        if len(shape) not in (3, 4):
+            raise ValueError(f"depth must be [N, H, W], [B, T, H, W] or [B, T, 1, H, W], got {tuple(normals.shape)}")
+        if shape[-2] < 2 or shape[-1] < 2:
+            raise ValueError(f"H and W must be at least 2 (the reflect pad of the Sobel stencil), got {shape[-2]} x {shape[-1]}")
+        lead = shape[:-2]
+    else:
+        if len(shape) not in (4, 5) or shape[-3] != 3:
+            raise ValueError(f"normals must be [N, 3, H, W] or [B, T, 3, H, W], got {shape}")
+        lead = shape[:-3]
+    H, W = shape[-2:]
+    N = 1
+    for n in lead:
+        N *= n
+    if N * H * W == 0:
+        raise ValueError("empty input")
+    rt = _runtime_for(device, normals)
+    x = stage(normals.detach(), rt.device, torch.float32).view((N, H, W) if from_depth else (N, 3, H, W))
+    with torch.cuda.device(rt.device):
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=rt.device)
+        rt.normal_colorize(x, out, order == "bgr")
+    return out.view(*lead, H, W, 3)

@@ -374,6 +374,24 @@ int vdn_stitch_fit(const float* pred, const float* target, size_t n, void* works
 int vdn_stitch_apply(const float* window, const float* coef, float* out_tail, float* out_new, float* ref1, size_t hw,
                      int T, int align_len, int overlap, int ref_frame, vdn_stream stream);
 
+/* Window stitcher of VideoDepthEstimationModel.infer_video (the depth + normal model's clip driver): one launch maps, blends
+ * and stores one window's depth f32 [T, hw] and normal f32 [T, 3, hw] (nx, ny, nz planes) into the clip, whose frame `start`
+ * out_depth [>= keep, hw] and out_normal [>= keep, 3, hw] point at. coef = {scale, shift} on the device (vdn_stitch_fit's,
+ * or {1, 0}). With d' = d * scale + shift (a multiply, then an add: two float32 roundings), clamped as d' < 0 ? 0 : d' if and
+ * only if clamp0 (a NaN stays a NaN), and n' = (scale * nx, scale * ny, 1), the gradient of the mapped depth, which the clamp
+ * does not alter:
+ *   frames t < overlap         : out = out * (1 - w_t) + new * w_t for depth, nx and ny, w = 0, 1 * (1 / (overlap-1)), .., 1
+ *                                (get_interpolate_frames, utils/util.py:65-73), every operation rounded to float32; nz = 1
+ *   frames overlap <= t < keep : out = new (nz = 1)
+ *   frames t >= keep           : neither read nor written (the window's pad slots behind the end of the clip).
+ * overlap = 0 is a first window: nothing of out_* is read. VDN_EINVAL, nothing written, for a NULL pointer, hw == 0, T < 1,
+ * T > 8192, overlap < 0, overlap == 1 (no cross-fade has one frame), overlap > T / 2, keep < 1, keep > T, or keep <= overlap
+ * when overlap > 0. No alignment is required: 16-byte accesses are used where hw % 4 == 0 and all four tensors are 16-byte
+ * aligned, 4-byte ones otherwise. Launch grid: y = 4 * keep (frame, plane) pairs, x = min(ceil(groups / 256),
+ * max(1, 2048 / (4 * keep))) blocks of 256 lanes striding over the plane's groups = hw / 4 (or hw) pixel groups.        */
+int vdn_dn_stitch_apply(const float* depth, const float* normal, const float* coef, float* out_depth, float* out_normal,
+                        size_t hw, int T, int overlap, int keep, int clamp0, vdn_stream stream);
+
 /* Clip evaluation on the device: eval_single_by_data of eval_depthcrafter/eval.py:55-151 with the seven eval_metrics of
  * eval_depthcrafter/metric.py, for pred f32 [frames, H, W], gt f32 [frames, H, W] and an optional mask u8 [frames, H, W]
  * (NULL = all ones; non-zero = use). valid = gt > dmin && gt < dmax && mask, compared in float32 as numpy does for a

@@ -135,6 +135,7 @@ EXPORTS = {
     "vdn_stitch_workspace_bytes": (C.c_size_t, []),
     "vdn_stitch_fit": (C.c_int, [fp, fp, C.c_size_t, vp, fp, vp]),
     "vdn_stitch_apply": (C.c_int, [fp, fp, fp, fp, fp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_dn_stitch_apply": (C.c_int, [fp, fp, fp, fp, fp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "vdn_eval_workspace_bytes": (C.c_size_t, [C.c_int]),
     "vdn_eval_fit": (C.c_int, [fp, fp, vp, C.c_int, C.c_size_t, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
     "vdn_eval_metrics": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp]),

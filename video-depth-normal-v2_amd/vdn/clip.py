@@ -25,13 +25,18 @@ def tap_bytes_per_frame(rt, embed_dim: int, H: int, W: int) -> int:
     return 4 * (H // 14) * (W // 14) * embed_dim * 2 * (2 if rt.split else 1)
 
 
+def cache_budget_bytes() -> float:
+    """Bytes a clip-level cache may take: VDN_TAP_CACHE_GB, default 96. A driver whose cache does not fit runs its own
+    `forward` window by window."""
+    return float(os.environ.get("VDN_TAP_CACHE_GB", "96")) * 2 ** 30
+
+
 def tap_cache_plan(rt, embed_dim: int, H: int, W: int, table, windows: Sequence[int]):
     """-> (the distinct frames the windows `windows` of `table` show, sorted; does their cache fit the budget VDN_TAP_CACHE_GB,
     default 96). A driver whose cache does not fit encodes window by window (its own `forward`)."""
     need = sorted({f for w in windows for f in table[w]})
-    budget = float(os.environ.get("VDN_TAP_CACHE_GB", "96")) * 2 ** 30
     batches = -(-len(need) // util.INFER_LEN)
-    return need, batches * util.INFER_LEN * tap_bytes_per_frame(rt, embed_dim, H, W) <= budget
+    return need, batches * util.INFER_LEN * tap_bytes_per_frame(rt, embed_dim, H, W) <= cache_budget_bytes()
 
 
 def cached_window_depths(rt, enc, head, embed_dim: int, net_batch: Callable[[List[int]], torch.Tensor], H: int, W: int, table,

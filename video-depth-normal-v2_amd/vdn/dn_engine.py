@@ -161,7 +161,9 @@ class DNHeadEngine:
         return toks
 
     def run_model(self, a, b, B: int, S: int, sizes, OH: int, OW: int, depth_in, relu: bool, depth, normal):
-        """The wrapper after its trunks: features -> head -> resize / residual / ReLU / normal (video_depth_model.py:89-123)."""
+        """The wrapper after its trunks: features -> head -> resize / residual / ReLU / normal (video_depth_model.py:89-123).
+        a, b: per level a contiguous f32 tensor of B*S frames, the trunk's own output or rows [start, start + S) of the clip
+        driver's feature cache (VideoDepthEstimationModel.infer_video), which have the same layout."""
         toks = self.tokens(a, b, B, S, sizes)
         y, (H, W) = self.decode(toks, B * S, sizes)
         self.rt.dn_tail(y, B * S, H, W, self.c_mid, self.w_out, self.b_out, OH, OW, depth_in=depth_in, relu=relu, depth=depth,

@@ -438,6 +438,22 @@ class Runtime:
                      checked_ptr("stitch_apply: ref1", ref1, dev, _f32, frame),
                      window[0].numel(), T, align_len, overlap, ref_frame)
 
+    def dn_stitch_apply(self, depth: torch.Tensor, normal: torch.Tensor, coef: torch.Tensor, out_depth: torch.Tensor,
+                        out_normal: torch.Tensor, overlap: int, keep: int, clamp0: bool):
+        """One window of the depth + normal model, depth f32 [T, H, W] and normal f32 [T, 3, H, W], into the clip from the
+        window's first frame on: out_depth f32 [>= keep, H, W] and out_normal f32 [>= keep, 3, H, W] are the clip's frames
+        start .. (include/vdn.h vdn_dn_stitch_apply); coef f32 [2] is what stitch_fit wrote, or {1, 0}."""
+        dev = self.device
+        d = checked_ptr("dn_stitch_apply: depth", depth, dev, _f32, 3)
+        T, H, W = depth.shape
+        po = checked_ptr("dn_stitch_apply: out_depth", out_depth, dev, _f32, (None, H, W))
+        if out_depth.shape[0] < keep:
+            raise abi.VdnError(f"dn_stitch_apply: {keep} frames to write, the clip has {out_depth.shape[0]} left")
+        self._launch(abi.lib.vdn_dn_stitch_apply, d, checked_ptr("dn_stitch_apply: normal", normal, dev, _f32, (T, 3, H, W)),
+                     checked_ptr("dn_stitch_apply: coef", coef, dev, _f32, count=2), po,
+                     checked_ptr("dn_stitch_apply: out_normal", out_normal, dev, _f32, (out_depth.shape[0], 3, H, W)),
+                     H * W, T, overlap, keep, int(bool(clamp0)))
+
     def _eval_args(self, what: str, pred, gt, mask):
         """-> the pointers of f32 pred, gt [T, H, W], the u8 or bool mask [T, H, W] (or None) and the clip's workspace."""
         p = checked_ptr(what + ": pred", pred, self.device, _f32, 3)

@@ -108,6 +108,67 @@ def stitch(depth_list: List[np.ndarray], org_len: int) -> np.ndarray:
     return np.stack(out[:org_len], axis=0)
 
 
+def dn_check_overlap(S: int, overlap) -> int:
+    """The overlap of VideoDepthEstimationModel.infer_video's windows of S slots: S // 4 by default; 0, or 2 .. S // 2 (one frame
+    cannot be cross-faded; more than half a window would put a frame into three windows)."""
+    if overlap is None:
+        overlap = S // 4
+    if isinstance(overlap, bool) or not isinstance(overlap, (int, np.integer)) or not (overlap == 0 or 2 <= overlap <= S // 2):
+        raise ValueError(f"overlap must be 0 or 2 .. {S // 2} (sequence_length // 2), got {overlap!r}"
+                         + (" (the default, sequence_length // 4: pass one)" if overlap == S // 4 else ""))
+    return int(overlap)
+
+
+def dn_window_table(N: int, S: int, overlap: int) -> List[List[int]]:
+    """Clip frame behind every slot of every S-slot window of the depth + normal model's clip driver: windows start at 0,
+    S - overlap, 2 (S - overlap), .. while start == 0 or start + overlap < N (a later window brings at least one new frame),
+    slot i shows frame min(start + i, N - 1): the tail is filled with copies of the last frame (v5:215-283). Every window is
+    a contiguous slice of the padded clip."""
+    if N < 1 or S < 1:
+        raise ValueError(f"a clip has at least one frame and a window one slot, got N = {N}, S = {S}")
+    overlap = dn_check_overlap(S, overlap)
+    step = S - overlap
+    return [[min(start + i, N - 1) for i in range(S)] for start in range(0, N, step) if start == 0 or start + overlap < N]
+
+
+def dn_stitch(depths: List[np.ndarray], normals: List[np.ndarray], N: int, overlap: int, align: bool = True, clamp0: bool = False):
+    """Host restatement, in float32, of VideoDepthEstimationModel.infer_video's stitch (vdn_stitch_fit + vdn_dn_stitch_apply per
+    window): depths [S, H, W] and normals [S, 3, H, W] of every window of dn_window_table(N, S, overlap), in order -> (depth
+    [N, H, W], normal [N, 3, H, W], coefs [windows, 2]). Window 0 is stored; a later one is mapped by the least-squares (scale,
+    shift) of its first `overlap` depth frames onto the clip's (compute_scale_and_shift, all-ones mask; {1, 0} without `align`
+    or overlap), its depth clamped at 0 with clamp0, its normals (nx, ny, 1) scaled to (scale nx, scale ny, 1), the gradient of
+    the mapped depth, which the clamp does not alter; the overlap frames are cross-faded (get_interpolate_frames: the same
+    weights on depth, nx and ny), the others stored up to the end of the clip."""
+    S = len(depths[0])
+    step = S - overlap
+    f32 = np.float32
+    out_d = np.zeros((N,) + tuple(depths[0].shape[1:]), f32)
+    out_n = np.zeros((N, 3) + tuple(depths[0].shape[1:]), f32)
+    coefs = np.zeros((len(depths), 2), f32)
+    for k, (d, n) in enumerate(zip(depths, normals)):
+        d, n = d.astype(f32), n.astype(f32)
+        start = k * step
+        keep = min(S, N - start)
+        ov = overlap if k else 0
+        scale, shift = 1, 0
+        if ov and align:
+            scale, shift = compute_scale_and_shift(d[:ov], out_d[start:start + ov], np.ones_like(d[:ov]))
+        coefs[k] = scale, shift
+        scale, shift = coefs[k]
+        new_d = d * scale + shift
+        if clamp0:
+            new_d = np.maximum(new_d, f32(0))
+        new_n = np.stack([n[:, 0] * scale, n[:, 1] * scale, np.ones_like(n[:, 2])], axis=1)
+        if ov:
+            pre = [out_d[start + i] for i in range(ov)], [out_n[start + i, :2] for i in range(ov)]
+            out_d[start:start + ov] = get_interpolate_frames(pre[0], list(new_d[:ov]))
+            out_n[start:start + ov, :2] = get_interpolate_frames(pre[1], list(new_n[:ov, :2]))
+            out_n[start:start + ov, 2] = 1
+        out_d[start + ov:start + keep] = new_d[ov:keep]
+        out_n[start + ov:start + keep] = new_n[ov:keep]
+    return out_d, out_n, coefs
+
+
 # --------------------------------------------------------------------------------------------- device -> host
 _HOST_OUT = {}   # (shape, dtype) -> (pinned tensor, weakref to the ndarray handed out last time)
 

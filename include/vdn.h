@@ -582,7 +582,11 @@ int vdn_normal_colorize(const float* x, int from_depth, int bgr, uint8_t* out, i
  * Float pointers need 4-byte alignment, workspace, frame_stats, frame_counts and out 8 (VDN_EALIGN otherwise). Where H * W
  * is a multiple of 4, prediction and target are 16-byte aligned and the mask is 4-byte aligned, a lane reads four pixels
  * per load; one otherwise. VDN_EINVAL: a null required pointer, a size <= 0, scales < 0, or T < 2 with stable_scale > 0.
- * VDN_EUNSUPPORTED: H * W > INT32_MAX, B * T > 65535, scales > 4. All of these are returned before anything is launched. */
+ * VDN_EUNSUPPORTED: H * W > INT32_MAX, B * T > 65535, scales > 4. All of these are returned before anything is launched.
+ * vdn_depth_loss_trip(wide): the pixels of a frame that one trip of a criterion's sweep covers (32 blocks x 256 lanes x 4 or
+ * 1); a larger frame sends the lanes round their stride loop again. The sweeps of the backward, of the trimmed criterion and
+ * of the SSIM term have the same blocks per frame, so the figure is theirs too.                                            */
+int vdn_depth_loss_trip(int wide);
 size_t vdn_depth_loss_workspace_bytes(int B, int T);
 int vdn_depth_loss(const float* prediction, const float* target, const uint8_t* mask, int B, int T, int H, int W,
                    double alpha, int scales, double stable_scale, void* workspace, float* scale_shift,

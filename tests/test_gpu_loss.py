@@ -1,13 +1,15 @@
 """vdn.loss on the device (csrc/loss.hip) against the CPU restatement tests/loss_ref.py, on the recorded cases of
 tests/golden/loss_cases.npz: the smallest shapes at which each piece can go wrong (odd sizes and one pixel per lane, whole
 quads, grids that collapse to a point, empty frames and items, medians of exactly 0, a negative scale, targets around the
-bounds of absRel, alpha = 0, stable_scale = 0, bool and uint8 masks).
+bounds of absRel, alpha = 0, stable_scale = 0, bool and uint8 masks), and on the constructed cases of
+tests/test_loss_host.py (EXTRA): quads that span a row's end, and frames past one trip of the sweep on both paths.
 
 Bars. Both sides are fp64 over the same float32 operands and differ in summation order only: spatial_loss, stable_loss,
 absRel_loss, d1, data, every g_k and every per-frame s within 1e-9 absolute (the bar of tests/test_gpu_normals.py; the
-largest sum here has 9216 terms below 100, whose fp64 sum is good to 1e-10 in any order), total_loss within
-(1 + stable_scale) * 1e-9; every median, count and fit exactly equal. forward's float32 tensors must be the fp64 values of
-the same inputs rounded once."""
+largest sum of a recorded case has 9216 terms below 100, whose fp64 sum is good to 1e-10 in any order; a constructed case
+takes the mean of n <= 107 117 terms, which any order gives to n * 2^-53 times the mean of their magnitudes: 1.2e-11 times a
+mean that is below 10 in every term of these cases), total_loss within (1 + stable_scale) * 1e-9; every median, count and
+fit exactly equal. forward's float32 tensors must be the fp64 values of the same inputs rounded once."""
 from __future__ import annotations
 
 import functools
@@ -17,7 +19,7 @@ import pytest
 import torch
 
 import loss_ref as R
-from test_loss_host import CASES, KEYS, case_id, case_inputs
+from test_loss_host import CASES, EXTRA, EXTRA_ARGS, KEYS, case_id, case_inputs, extra
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -90,6 +92,29 @@ def test_values_match_the_restatement(i):
         assert float(v) == float(np.float32(got[k])), k        # the fp64 value rounded once
 
 
+@pytest.mark.parametrize("name", list(EXTRA))
+def test_constructed_cases_match_the_restatement(name):
+    """The values, medians, scales, counts and the fit at quads that span a row's end and past one trip of the sweep."""
+    from vdn import loss as L
+    case, want = extra(name)
+    B, T, H, W = case["pred"].shape
+    wide = H * W % 4 == 0
+    assert W % 4 != 0 and wide == (name != "two-trips-single")
+    if name != "quads-cross-rows":
+        assert H * W > L.trip_pixels(wide)                       # every lane of block 0 comes round its stride loop again
+    if wide:
+        assert all(dev(case[k]).data_ptr() % 16 == 0 for k in ("pred", "target"))   # the four-pixel path is the one that runs
+    agree(run(case, EXTRA_ARGS), want, EXTRA_ARGS["stable_scale"], name)
+    # the fit alone, on frame 1 of every item, bit for bit
+    p, t, m = (case[k][:, 1] for k in ("pred", "target", "mask"))
+    scale, shift = L.compute_scale_and_shift(dev(p), dev(t), dev(m))
+    fit = R.fit_ref(p, t, m)
+    print("scale", scale.tolist(), fit[0].tolist(), "shift", shift.tolist(), fit[1].tolist())
+    assert scale.cpu().numpy().tobytes() == fit[0].tobytes() and shift.cpu().numpy().tobytes() == fit[1].tobytes()
+    if B > 1:
+        assert fit[0][0] != fit[0][1]
+
+
 @pytest.mark.parametrize("i", [0, 9], ids=lambda i: case_id(CASES[i]))
 def test_fit_is_the_restatements_float32_pair(i):
     """compute_scale_and_shift on [B, H, W] (one frame of every item, so the items' fits differ; case 9 has an empty item)."""
@@ -115,8 +140,9 @@ def test_two_runs_give_the_same_bits():
 
 
 def test_nan_and_inf_under_dropped_pixels_change_no_bit():
-    for i in (0, 8, 9):                                           # plain, an empty frame, an empty item
-        case, _ = _case(i)
+    # plain, an empty frame, an empty item; then quads that span a row's end past one trip, where the finest grid's right-hand
+    # neighbour comes from the lane's own quad: a dropped one must reach nothing there either
+    for case, args in [(_case(i)[0], CASES[i]) for i in (0, 8, 9)] + [(extra("two-trips-quads-cross-rows")[0], EXTRA_ARGS)]:
         drop = case["mask"] == 0
         poisoned = dict(case)
         for k, vals in (("pred", (np.nan, np.inf)), ("target", (-np.inf, np.nan))):
@@ -124,7 +150,7 @@ def test_nan_and_inf_under_dropped_pixels_change_no_bit():
             a[drop] = np.where(np.arange(drop.sum()) % 2 == 0, vals[0], vals[1]).astype(np.float32)
             poisoned[k] = a
         assert drop.any() and np.isnan(poisoned["pred"]).any() and np.isinf(poisoned["target"]).any()
-        same_bits(run(case, CASES[i]), run(poisoned, CASES[i]))
+        same_bits(run(case, args), run(poisoned, args))
 
 
 def test_temporal_term_stays_inside_an_item():
@@ -181,3 +207,9 @@ def test_views_and_mask_types_give_the_same_values():
     off = [torch.empty(p.numel() + 1, device=DEV)[1:].view(p.shape).copy_(x) for x in (p, t)]
     assert all(o.data_ptr() % 16 == 4 and o.is_contiguous() for o in off)
     agree(L.depth_loss(off[0], off[1], m), want, CASES[2]["stable_scale"], "misaligned")
+    # the same past one trip, with rows that end inside what would be a quad: five trips of one pixel per lane
+    case, want = extra("two-trips-quads-cross-rows")
+    p, t, m = (dev(case[k]) for k in ("pred", "target", "mask"))
+    off = [torch.empty(p.numel() + 1, device=DEV)[1:].view(p.shape).copy_(x) for x in (p, t)]
+    assert all(o.data_ptr() % 16 == 4 and o.is_contiguous() for o in off) and p.shape[2] * p.shape[3] > L.trip_pixels(False)
+    agree(L.depth_loss(off[0], off[1], m, **EXTRA_ARGS), want, EXTRA_ARGS["stable_scale"], "misaligned two-trips-quads-cross-rows")

@@ -1,5 +1,8 @@
 """The SSIM term of the depth criterion on the device (csrc/ssim.hip, vdn.loss) against the CPU restatement tests/ssim_ref.py
-at the sizes where the kernels can go wrong, then the classes at the 161-pixel cases of tests/golden/ssim_cases.npz.
+at the sizes where the kernels can go wrong, then the classes at the 161-pixel cases of tests/golden/ssim_cases.npz. The
+sizes: frames around one tile, then (PAST_ONE_RING) frames whose inner tiles have all four neighbours, frames past one trip
+of the sweeps on either path with rows that end inside a lane's quad, more tiles than the fold has lanes, and an item's
+maximum on a lane's second trip. Tile and trip are the library's own figures (vdn.loss.ssim_tile, vdn.loss.trip_pixels).
 
 Bars.
 Value: |got - want| <= 1e-10, for the loss and every frame's cs. A cs pixel is a quotient whose denominator is at least C2 =
@@ -11,7 +14,8 @@ factor 2, as in tests/test_gpu_loss_grad.py. floor * parts is what fp64 leaves o
 sum of their magnitudes (through the fit also what the item-wide sums G0 and G1 carry of them into the pixel's correction),
 and floor is measured per case, not fixed: the restatement is evaluated in the two summation orders, H then W against W then
 H, and the largest difference relative to parts is taken (ssim_ref.fp64_floor); 8 times it is allowed. Measured on these
-cases: between 9e-16 and 8e-13, 1e-14 typically (profiles/ssim_loss.md); a case whose two orders happen to agree more closely than 2^-50 is
+cases: between 9e-16 and 8e-13, 1e-14 typically (profiles/ssim_loss.md; 2.6e-15 to 9.2e-15 on the cases of PAST_ONE_RING,
+profiles/criteria_edges.md); a case whose two orders happen to agree more closely than 2^-50 is
 given 2^-50, four ulp, the least that 121-term sums in two orders can be asked to agree to."""
 from __future__ import annotations
 
@@ -80,6 +84,42 @@ def det0_case():
     return c
 
 
+def trip(wide):
+    """The pixels of a frame that one trip of the sweeps covers: the library's own figure, which needs no device."""
+    from vdn import loss as L
+    return L.trip_pixels(wide)
+
+
+def interior_frame(dy, dx):
+    """(H, W) of 3 tiles + 10 + (dy, dx): at (1, 1) the outputs make 4 x 4 tiles with a ragged last row and column of one
+    output, at (0, 0) exactly 3 x 3; the pixels make 4 x 4 tiles either way. The inner tiles have all four neighbours: their
+    whole halo comes from inside the frame, and the adjoint's from staged outputs without a zero."""
+    th, tw = TILE
+    return 3 * th + 10 + dy, 3 * tw + 10 + dx
+
+
+def strip_shape(odd):
+    """[1, 2, H, 13] with 256 + 2 tiles in one column, outputs and pixels alike: lanes 0 and 1 of the fold that adds a frame's
+    tiles take a second row. 53 612 pixels (odd: 53 599), past one trip of either sweep, and no row holds whole quads."""
+    return (1, 2, 257 * TILE[0] + 12 - odd, 13)
+
+
+def placed(name):
+    """The frame-0 indices at which a holder case puts the item's maximum. trip + 7: block 0, lane 1, on its second trip.
+    trip - 4 * 256 + 5: the last block of the first trip, lane 1. The fold meets block 0 first; the lower index must win."""
+    second = trip(True) + 7
+    return (second,) if name == "holder-second-trip" else (trip(True) - 4 * 256 + 5, second)
+
+
+def holder_case(name):
+    c = S.make_case(66, strip_shape(0), 0.875, gain=1.5)
+    top = np.float32(4.5)
+    assert top > c["pred"].max() and top > c["target"].max()
+    for i in placed(name):
+        c["pred"][0, 0].reshape(-1)[i], c["mask"][0, 0].reshape(-1)[i] = top, True
+    return c
+
+
 #        name                 (case maker, aligned, expected holder per item, expected gated frames)
 CASES = {
     "one-output": (lambda: S.make_case(41, (1, 1, 11, 11), 0.875, gain=1.5), False, ("prediction",), 0),
@@ -96,7 +136,35 @@ CASES = {
     "clamp": (zero_item_case, False, ("clamp", "prediction"), 0),
     "tie": (tie_case, False, ("tie",), 0),
     "det-zero-aligned": (det0_case, True, None, 0),
+    # past one ring of tiles and past one trip of the sweeps (reach() states what each is there for)
+    "interior-tile": (lambda: S.make_case(61, (1, 2) + interior_frame(1, 1), 0.875, gain=1.5), False, ("prediction",), 0),
+    "interior-tile-quads-aligned": (lambda: S.make_case(62, (1, 2) + interior_frame(0, 0), 0.875, gain=1.5), True, None, 0),
+    "strip-quads-aligned": (lambda: S.make_case(63, strip_shape(0), 0.875, gain=1.5), True, None, 0),
+    "strip-single": (lambda: S.make_case(64, strip_shape(1), 0.875, gain=1.5), False, ("prediction",), 0),
+    "strip-gated-aligned": (lambda: S.make_case(65, strip_shape(0), 0.875, ((0, 1),), 1.5), True, ("prediction",), 1),
+    "holder-second-trip": (functools.partial(holder_case, "holder-second-trip"), False, ("prediction",), 0),
+    "holder-tie-across-blocks": (functools.partial(holder_case, "holder-tie-across-blocks"), False, ("prediction",), 0),
 }
+PAST_ONE_RING = [n for n in CASES if n.startswith(("interior-", "strip-", "holder-"))]
+
+
+def reach(name, shape):
+    """What a case of PAST_ONE_RING is there for, in terms of the tile and the trip the library reports: a change of either
+    fails here and cannot quietly take the coverage away."""
+    from vdn import loss as L
+    th, tw = L.ssim_tile()
+    H, W = shape[2:]
+    wide = H * W % 4 == 0
+    out, px = (-(-(H - 10) // th), -(-(W - 10) // tw)), (-(-H // th), -(-W // tw))
+    assert W % 4 != 0                                            # on the quad path a lane's quad spans a row's end
+    if name.startswith("interior-"):
+        assert wide == (name == "interior-tile-quads-aligned")
+        assert out == ((4, 4) if name == "interior-tile" else (3, 3)) and px == (4, 4)       # inner tiles have four neighbours
+        assert ((H - 10) % th, (W - 10) % tw) == ((1, 1) if name == "interior-tile" else (0, 0))
+    else:
+        assert wide == (name != "strip-single") and H * W > L.trip_pixels(wide)              # the lanes come round again
+        assert out[0] * out[1] > 256 and px[0] * px[1] > 256                                 # and so do the fold's
+        assert H * W >= L.trip_pixels(False)                                                 # every block of a frame owns pixels
 
 
 @functools.lru_cache(maxsize=None)
@@ -144,7 +212,18 @@ def test_value_and_gradient_match_the_restatement(name):
         assert f["cs"][0, 0] == 1.0 and f["max_val"][0] == np.float32(1e-8) and not r["grad"][0].any()
     if name == "inverse-frame":
         assert f["cs"][0, 1] < -0.8 and f["index"][0] == 30 * 45 + 3 * 45 + 4 and r["hold"][0] != 0
+    if name in PAST_ONE_RING:
+        reach(name, c["pred"].shape)
+    if name == "strip-gated-aligned":
+        assert f["cs"][0, 1] < 0 < f["cs"][0, 0] and r["hold"][0] != 0 and not c["mask"][0, 1].any()
+    if name.startswith("holder-"):
+        at = placed(name)
+        flat = lambda n: c[n][0, 0].reshape(-1)
+        assert all(flat("mask")[i] and flat("pred")[i].tobytes() == flat("pred")[at[0]].tobytes() for i in at)
+        assert f["index"][0] == min(at) and flat("pred")[at[0]] == f["max_val"][0] and r["hold"][0] != 0
     p, t, k = (dev(c[n]) for n in ("pred", "target", "mask"))
+    if name in PAST_ONE_RING and c["pred"][0, 0].size % 4 == 0:
+        assert p.data_ptr() % 16 == 0 and t.data_ptr() % 16 == 0     # the quad path is the one that runs
     got = L.ssim_loss(p, t, k, aligned=aligned)
     err = max(abs(got["ssim_loss"] - f["loss"]), float(np.abs(got["cs"].numpy() - f["cs"]).max()))
     print(f"[{name}] loss {got['ssim_loss']:.12f}, |value - restatement| {err:.2e}, holder {[S.HOLDERS[int(h)] for h in got['holder']][:4]}, "
@@ -169,7 +248,7 @@ def test_value_and_gradient_match_the_restatement(name):
 
 def test_two_runs_give_the_same_bits():
     from vdn import loss as L
-    for name in ("odd-width-aligned", "inverse-frame"):
+    for name in ("odd-width-aligned", "inverse-frame", "strip-quads-aligned"):
         c, _, _, _ = oracle(name)
         aligned = CASES[name][1]
         p, t, k = (dev(c[n]) for n in ("pred", "target", "mask"))
@@ -218,6 +297,49 @@ def test_accumulate_adds_to_the_prior_gradient_with_one_rounding(name):
     alone = L.ssim_loss_grad(p, t, k, aligned=aligned, coeff=0.3).cpu().numpy().astype(np.float64)
     diff = np.abs(got.cpu().numpy().astype(np.float64) - (alone + prior.astype(np.float64)))
     assert (diff <= 2.0 ** -24 * (np.abs(alone) + np.abs(prior)) * 2).all()
+
+
+def test_misaligned_prediction_past_one_trip_gives_the_same_bits():
+    """strip-quads-aligned with the prediction one float past a 16-byte boundary: the forward's maximum then reads a pixel per
+    lane and the backward four pixels per lane with scalar loads, both past one trip. A maximum has no order and the backward
+    picks its order from the shape alone, so without the fit every value and the gradient keep their bits; with the fit
+    (which vdn_depth_loss sums in another order for a misaligned tensor) the gradient keeps to the bar."""
+    from vdn import loss as L
+    c, fit, r, floor = oracle("strip-quads-aligned")
+    shape = c["pred"].shape
+    p, t, k = (dev(c[n]) for n in ("pred", "target", "mask"))
+    off = torch.empty(p.numel() + 1, dtype=torch.float32, device=DEV)[1:].view(shape)
+    off.copy_(p)
+    assert off.data_ptr() % 16 == 4 and p.data_ptr() % 16 == 0 and shape[2] * shape[3] % 4 == 0 and shape[2] * shape[3] > L.trip_pixels(True)
+    a, b = L.ssim_loss(p, t, k), L.ssim_loss(off, t, k)
+    assert a["ssim_loss"] == b["ssim_loss"] and a["gated"] == b["gated"]
+    for n in ("cs", "max_val", "holder", "index", "weight"):
+        assert a[n].numpy().tobytes() == b[n].numpy().tobytes(), n
+    same_bits(L.ssim_loss_grad(p, t, k), L.ssim_loss_grad(off, t, k))
+    worst = ratio_to_bound(L.ssim_loss_grad(off, t, k, aligned=True).cpu().numpy(), r, floor)
+    print(f"[strip-quads-aligned] misaligned prediction, through the fit: largest |got - want| / bound {worst:.3f}")
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("name", ["interior-tile-quads-aligned", "strip-quads-aligned"])
+def test_accumulate_across_row_ends_and_past_one_trip(name):
+    """The accumulating write on the quad path where a lane's quad spans a row's end, and on its second trip: a prior gradient
+    of the size a training step holds, N(0, 1), under the file's bound with its |prior| term."""
+    from vdn import loss as L
+    c, fit, _, floor = oracle(name)
+    assert CASES[name][1]
+    reach(name, c["pred"].shape)
+    prior = np.random.default_rng(17).standard_normal(c["pred"].shape).astype(np.float32)
+    r = S.ssim_grad_ref(c["pred"], c["target"], c["mask"], fit, coeff=0.85, prior=prior)
+    p, t, k = (dev(c[n]) for n in ("pred", "target", "mask"))
+    before = dev(prior)
+    got = L.ssim_loss_grad(p, t, k, aligned=True, coeff=0.85, prior=before)
+    same_bits(before, dev(prior))
+    gh = got.cpu().numpy()
+    worst = ratio_to_bound(gh, r, floor)
+    moved = float((gh != prior).mean())
+    print(f"[{name}] accumulate: largest |got - want| / bound {worst:.3f}; share of elements the term moved {moved:.3f}")
+    assert np.isfinite(gh).all() and worst <= 1.0
 
 
 # ------------------------------------------------------------------------------------------------ the classes, at 161 pixels

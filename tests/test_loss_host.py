@@ -9,6 +9,7 @@ the largest deviation per key over the recorded cases and stored it in the fixtu
 a bar above 1e-4, which would mean a wrong restatement rather than rounding."""
 from __future__ import annotations
 
+import functools
 import os
 
 import numpy as np
@@ -49,6 +50,53 @@ def case_id(c):
 
 
 CASES = list(golden_cases())
+
+# Constructed cases beside the recorded ones, for tests/test_gpu_loss.py: R.make_case(seed, shape, 0.8), alpha = 0.5,
+# stable_scale = 10, four scales; the reference is not consulted for them.
+#   quads-cross-rows            H * W is a multiple of 4 and W is not: every second quad of a lane spans a row's end, where the
+#                               finest grid's right-hand neighbour must not come from the lane's own quad;
+#   two-trips-quads-cross-rows  33 488 pixels a frame with W % 4 == 2: the same past one trip of the four-pixel sweep;
+#   two-trips-single            33 123 pixels, odd: the one-pixel sweep, which runs five trips;
+#   two-items-two-trips         two fits, and each item's temporal pairs reach into the second trip.
+EXTRA = {"quads-cross-rows": (357, (1, 2, 6, 6)), "two-trips-quads-cross-rows": (85, (1, 2, 184, 182)),
+         "two-trips-single": (83, (1, 2, 181, 183)), "two-items-two-trips": (86, (2, 2, 184, 182))}
+EXTRA_ARGS = dict(alpha=0.5, stable_scale=10)
+
+
+@functools.lru_cache(maxsize=None)
+def extra(name):
+    """Inputs and restatement of a constructed case, computed once, shared and never written."""
+    seed, shape = EXTRA[name]
+    case = R.make_case(seed, shape, 0.8)
+    for a in case.values():
+        a.setflags(write=False)
+    return case, R.depth_loss_ref(case["pred"], case["target"], case["mask"], **EXTRA_ARGS)
+
+
+@pytest.mark.parametrize("name", list(EXTRA))
+def test_constructed_cases_have_pixels_on_both_sides(name):
+    """What the device test needs of the seeds, checked where no device is: every grid keeps points, the temporal term counts
+    pairs and drops some, d1 has hits and misses, and the shapes are on the sweep they are named for."""
+    from vdn import loss as L
+    case, r = extra(name)
+    B, T, H, W = case["pred"].shape
+    kept, both = int(r["count"].sum()), int(((case["mask"][:, 1:] != 0) & (case["mask"][:, :-1] != 0)).sum())
+    print(f"[{name}] M {r['M'].tolist()} kept {kept} temporal pairs {r['stable_count']} of {both} d1 hits {r['d1_hits']} absRel {r['absrel_count']}")
+    assert (r["M"] > 0).all() and r["M"][0] == kept and 0 < r["stable_count"] < both and 0 < r["d1_hits"] < kept
+    assert r["d1_hits"] < r["absrel_count"] <= kept
+    wide = H * W % 4 == 0
+    assert wide == (name != "two-trips-single") and W % 4 != 0
+    assert (H * W > L.trip_pixels(wide)) == (name != "quads-cross-rows")
+    if name == "quads-cross-rows":
+        assert r["M"].tolist() == [63, 17, 7, 2]
+    if B > 1:
+        assert r["scale"][0] != r["scale"][1]
+
+
+def test_trip_query_is_the_sweeps_stride():
+    from vdn import _abi, loss as L
+    assert _abi.lib.vdn_depth_loss_trip(1) == 4 * _abi.lib.vdn_depth_loss_trip(0) == L.trip_pixels(True) > 0
+    assert L.trip_pixels(False) % 256 == 0
 
 
 def test_bars_are_rounding_sized():

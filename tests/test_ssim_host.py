@@ -189,6 +189,40 @@ def test_who_holds_the_maximum():
     assert float(r[0][0]) == float(np.float32(1e-8))
 
 
+def _device_cases():
+    import test_gpu_ssim as Gs
+    return Gs
+
+
+@pytest.mark.parametrize("name", _device_cases().PAST_ONE_RING)
+def test_the_device_tests_larger_inputs_are_what_they_are_named_for(name):
+    """The cases tests/test_gpu_ssim.py takes past one ring of tiles and one trip of the sweeps, checked where no device is: the
+    restatement gives the holder, index and gated count the table expects, the placed maxima are kept pixels of equal bits,
+    the shapes reach what they are there for, and the measured floor is a number."""
+    Gs = _device_cases()
+    _, aligned, holders, gated = Gs.CASES[name]
+    c, fit, r, floor = Gs.oracle(name)
+    f = r["fwd"]
+    Gs.reach(name, c["pred"].shape)
+    print(f"[{name}] holder {[S.HOLDERS[int(h)] for h in f['holder']]} index {f['index'].tolist()} gated {f['gated']} cs {f['cs'].ravel().tolist()} "
+          f"floor {floor:.2e}")
+    assert (fit is not None) == aligned and f["gated"] == gated and np.isfinite(floor) and 0 < floor < 1e-12
+    assert np.isfinite(r["grad"]).all() and r["grad"].any()
+    if holders is not None:
+        assert tuple(S.HOLDERS[int(h)] for h in f["holder"]) == holders and r["hold"][0] != 0
+    if name == "strip-gated-aligned":
+        assert f["cs"][0, 1] < 0 < f["cs"][0, 0] and not c["mask"][0, 1].any() and not r["grad"][0, 1].any()
+    if name.startswith("holder-"):
+        at = Gs.placed(name)
+        pred, keep = c["pred"][0, 0].reshape(-1), c["mask"][0, 0].reshape(-1)
+        assert len(at) == (2 if name == "holder-tie-across-blocks" else 1) and len(set(at)) == len(at) and max(at) < pred.size
+        assert all(keep[i] and pred[i].tobytes() == pred[at[0]].tobytes() for i in at)
+        assert (pred[at[0]] > np.delete(c["pred"][0].reshape(-1), at)).all() and pred[at[0]] > c["target"].max()
+        assert f["index"][0] == min(at) and f["max_val"][0] == pred[at[0]]
+        # the placed indices sit where the names say: the later one on a lane's second trip, the earlier in another block
+        assert at[-1] // Gs.trip(True) == 1 and at[0] // Gs.trip(True) == (1 if len(at) == 1 else 0)
+
+
 def test_signatures_keys_and_argument_errors():
     """Fails without the feature: the classes do not exist. Every error comes before the device is touched (this machine has
     none)."""

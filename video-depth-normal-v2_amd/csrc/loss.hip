@@ -536,6 +536,8 @@ __global__ __launch_bounds__(256) void trim_finalise_kernel(void* __restrict__ t
 
 }  // namespace
 
+extern "C" int vdn_depth_loss_trip(int wide) { return (int)(wide ? sweep_stride<DL_BPF, 4>() : sweep_stride<DL_BPF, 1>()); }
+
 extern "C" size_t vdn_depth_loss_workspace_bytes(int B, int T) {
   if (B <= 0 || T <= 0) return 0;
   return sizeof(double) * Ws::slots((size_t)B, (size_t)B * T) + select_workspace_bytes(B * T, 2);

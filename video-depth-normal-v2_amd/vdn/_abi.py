@@ -151,6 +151,7 @@ EXPORTS = {
     "vdn_normal_angle_stats_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vdn_normal_angle_stats": (C.c_int, [fp, fp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "vdn_normal_colorize": (C.c_int, [fp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "vdn_depth_loss_trip": (C.c_int, [C.c_int]),
     "vdn_depth_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "vdn_depth_loss": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, vp, fp, vp, vp, vp,
                                  vp]),

@@ -66,6 +66,13 @@ SSIM_MIN_SIDE = 160   # the library asserts min(H, W) > (11 - 1) * 2 ** 4 for it
 SSIM_HOLDERS = ("prediction", "target", "dropped", "clamp", "tie")   # who holds an item's maximum (include/vdn.h, item_max)
 
 
+def trip_pixels(wide: bool) -> int:
+    """The pixels of one frame that one trip of a criterion's sweep covers (vdn_depth_loss_trip): a larger frame sends every
+    lane round its stride loop again. wide: the four-pixel path. The SSIM term's sweeps share the figure."""
+    from . import _abi as abi
+    return int(abi.lib.vdn_depth_loss_trip(int(wide)))
+
+
 def _check(prediction, target, mask, dims: int) -> tuple:
     if not isinstance(prediction, torch.Tensor) or prediction.dim() != dims:
         want = "[B, T, H, W]" if dims == 4 else "[B, H, W]"
